@@ -3,6 +3,8 @@
 150 bp Illumina reads at -l 3, full qlts+gens+recs path, one process per GPU.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full                  # every secondary leg as well
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR      # + the last step's outputs as .npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,10 +13,13 @@ the rank's FASTQ text, which is already resident in HBM when the timed region st
 rank codes its own shard of records (weak scaling: per-GPU work fixed) and the step ends with the RCCL
 gather of the compressed streams to rank 0.  Prints ONE JSON line on rank 0.
 
-Beside the contract's fields the line carries, at N = 1: `roofline` (the base kernel: algorithmic bytes over its
-launch time, the PMC-measured HBM traffic from profiles/, the practical random-sector peak), `cpu_baseline` (the
-compiled reference, or the oracle port, on a bounded sample on one host core), `ratio_vs_reference` (same sample),
-and `decode` (the same blocks decoded in HBM after the timed steps and compared with the input; never in `value`).
+A plain run sets up, warms up, times the steps and prints the line: beside the contract's fields it carries
+`phase_ms` and `roofline` (the base kernel: algorithmic bytes over its launch time in the timed steps, the
+PMC-measured HBM traffic from profiles/, the practical random-sector peak), which take no run of their own.
+With --full the line also carries, at N = 1: `cpu_baseline` (the compiled reference, or the oracle port, on a
+bounded sample on one host core), `ratio_vs_reference` (same sample), `decode` (the same blocks decoded in HBM
+after the timed steps and compared with the input; never in `value`), `size_sweep`, `adaptive_tables`,
+`host_to_host`, `format6` and `genome_sampled`; at N = 8 `c4`.  The --no-* options switch single legs of --full off.
 """
 import argparse
 import ctypes
@@ -33,6 +38,8 @@ from slimfastq_amd import capi  # noqa: E402
 from slimfastq_amd import dist as sdist  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak (MI355X_MICROARCH.md "Chip-level parameters")
+DUMP_SAMPLE = 1 << 21        # --dump-outputs: bytes of the packed streams written (float32: 8 MiB), at seeded positions
+DUMP_SEED = 20261016
 
 
 def parse():
@@ -72,10 +79,21 @@ def parse():
     ap.add_argument("--no-size-sweep", action="store_true", help="skip the size sweep (prefixes of the same text: 0.25 / 0.5 / 1 / 2 GB and all of it, encode + decode)")
     ap.add_argument("--sweep-gb", type=str, default="0.25,0.5,1,2", help="size sweep: prefix sizes in GB (the whole text is always the last point)")
     ap.add_argument("--no-host-leg", action="store_true", help="skip the PCIe-inclusive host-to-host encode")
-    ap.add_argument("--sweep-only", action="store_true", help="debug: the size sweep alone (no decode / adaptive / cpu / format-6 / genome legs)")
+    ap.add_argument("--sweep-only", action="store_true", help="debug: the size sweep alone (no decode / adaptive / cpu / format-6 / genome legs); implies --full")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, run the secondary legs as well (decode, size sweep, adaptive tables, "
+                    "host-to-host, CPU baseline and ratio vs the reference, format 6, genome-sampled reads; C4 at N = 8)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed call returned in its last step to DIR/<name>.npy (float64 / float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.sweep_only:
+        args.full = True
         args.no_decode = args.no_adaptive_leg = args.no_cpu_baseline = args.no_format6_leg = args.no_genome_leg = args.no_host_leg = True
+    if not args.full:
+        # a plain run measures the headline only: every secondary leg belongs to --full
+        args.no_decode = args.no_adaptive_leg = args.no_cpu_baseline = args.no_format6_leg = args.no_genome_leg = args.no_host_leg = True
+        args.no_size_sweep = args.no_c4_leg = True
     if args.reads <= 0:
         args.reads = 60_000 if args.kind == 1 else 10_000_000
     if args.kind == 1:
@@ -265,6 +283,33 @@ def _varints(blob: bytes, n: int):
     return out + [0] * (n - len(out))
 
 
+def dump_outputs(path, ctx, res, d_out):
+    """--dump-outputs: what sfq_encode_blocks handed its caller in the last timed step, as .npy files -- the counts of
+    sfq_result (its timings excluded), the streams' sizes and offsets, the block index (one row per block, BlockInfo's
+    fields in order), the side blobs a decoder needs, and the packed streams: all of them up to DUMP_SAMPLE bytes, else
+    DUMP_SAMPLE bytes at positions drawn from DUMP_SEED (streams_sample_pos.npy).  Bytes are written as float32, counts
+    and offsets as float64 (exact: all are below 2^53)."""
+    os.makedirs(path, exist_ok=True)
+
+    def put(name, a, dtype):
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=dtype))
+    put("result", [res.n_records, res.n_blocks, res.total_bytes, res.first_hdr_bytes, res.n_chains], np.float64)
+    put("stream_bytes", list(res.stream_bytes), np.float64)
+    put("stream_offset", list(res.stream_offset), np.float64)
+    put("block_index", [[b.first_record, b.n_records, b.llen, b.solid, b.two_id, b.n_byte, b.gen_bits, b.extra_hi, b.first_hdr_len,
+                         b.first_hdr_off, *b.size, b.status, b.hdr_bytes] for b in ctx.index(res.n_blocks)], np.float64)
+    for name, blob in (("first_headers", ctx.first_headers(res.first_hdr_bytes)), ("qlt_prior", ctx.prior()),
+                       ("chain_index", ctx.chains()), ("rec_prior", ctx.rec_prior())):
+        put(name, np.frombuffer(blob, np.uint8), np.float32)
+    total = int(res.total_bytes)
+    if total <= DUMP_SAMPLE:
+        pos = np.arange(total, dtype=np.int64)
+    else:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_SAMPLE, dtype=np.int64))
+    put("streams_sample_pos", pos, np.float64)
+    put("streams_sample", d_out[torch.from_numpy(pos).to(d_out.device)].cpu().numpy(), np.float32)
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -383,6 +428,9 @@ def main():
         all_in, all_out = float(tot[0].item()), float(tot[1].item())
     else:
         all_in, all_out = float(nbytes), float(res.total_bytes)
+    if args.dump_outputs and rank == 0:
+        # before any leg below reuses the output buffers
+        dump_outputs(args.dump_outputs, ctx, res, d_outs[(flight["n"] - 1) % len(d_outs)])
 
     # ---- N = 8: BASELINE.json's configuration C4 beside the headline -- 100 M x 150 bp reads at -l 4, 12.5 M a rank, the same step
     #      (shared prior by all-reduce, the streams to the writer rank over RCCL), timed the same way; never part of `value`

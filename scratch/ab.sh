@@ -1,7 +1,7 @@
 #!/bin/bash
 # default bench (encode + decode), lean, for the in-tree library and every scratch/libsfq_*.so; kernel trace timelines with TRACE=1
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; cd $ROOT; TAG=${1:-ab}; mkdir -p gpurun_out/$TAG
-LEAN="--no-cpu-baseline --no-adaptive-leg --no-genome-leg --no-format6-leg"
+LEAN="--full --no-cpu-baseline --no-adaptive-leg --no-genome-leg --no-format6-leg"
 cp slimfastq_amd/libslimfastq_amd.so /tmp/lib_orig.so
 one() {
   python3 bench.py --steps 10 --warmup 3 $LEAN 2>/dev/null < /dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('   enc', d['value'], d['ms_per_step'], d['phase_ms']); print('   dec', d['decode']['value'], d['decode']['ms'], d['decode']['phase_ms'])"

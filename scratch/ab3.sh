@@ -1,7 +1,7 @@
 #!/bin/bash
 # the default bench three times alternating between the in-tree library and scratch/libsfq_OLD.so
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; cd $ROOT
-LEAN="--no-cpu-baseline --no-adaptive-leg --no-genome-leg --no-format6-leg"
+LEAN="--full --no-cpu-baseline --no-adaptive-leg --no-genome-leg --no-format6-leg"
 cp slimfastq_amd/libslimfastq_amd.so /tmp/lib_new.so
 for i in 1 2 3; do
   for v in new OLD; do

@@ -4,8 +4,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$1; shift
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --kernel-trace --output-format csv -d $OUT/p1 -- python3 $ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-adaptive-leg "$@" > $OUT/p1.log 2>&1
-rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum SQ_INSTS_LDS SQ_INST_LEVEL_VMEM SQ_WAVES --kernel-trace --output-format csv -d $OUT/p2 -- python3 $ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-adaptive-leg "$@" > $OUT/p2.log 2>&1
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --kernel-trace --output-format csv -d $OUT/p1 -- python3 $ROOT/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-adaptive-leg "$@" > $OUT/p1.log 2>&1
+rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum SQ_INSTS_LDS SQ_INST_LEVEL_VMEM SQ_WAVES --kernel-trace --output-format csv -d $OUT/p2 -- python3 $ROOT/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-adaptive-leg "$@" > $OUT/p2.log 2>&1
 python3 - <<PY
 import csv, glob, collections
 agg=collections.defaultdict(lambda: [0,0.0]); dur=collections.defaultdict(list)

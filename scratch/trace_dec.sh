@@ -2,7 +2,7 @@
 # scratch/trace_dec.sh: kernel trace of the default DECODE call -> the last decode call's kernels over 0.1 ms
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/trdec; mkdir -p $OUT
-LEAN="--steps 2 --warmup 1 --no-cpu-baseline --no-genome-leg --no-format6-leg --no-adaptive-leg --no-size-sweep --no-host-leg"
+LEAN="--full --steps 2 --warmup 1 --no-cpu-baseline --no-genome-leg --no-format6-leg --no-adaptive-leg --no-size-sweep --no-host-leg"
 ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --output-format csv -d $OUT/prof -- python3 $ROOT/bench.py $LEAN "$@" > $OUT/prof.json 2> $OUT/prof.log < /dev/null )
 f=$(find $OUT/prof -name "*kernel_trace.csv" | head -1)
 python3 - "$f" <<'PY'

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the other workloads, one summary line each (round 3: the default line carries the genome / format-6 / adaptive legs itself)
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; cd $ROOT; mkdir -p gpurun_out/wl
-X="--no-genome-leg --no-format6-leg --no-adaptive-leg --no-cpu-baseline"
+X="--full --no-genome-leg --no-format6-leg --no-adaptive-leg --no-cpu-baseline"
 run() { name=$1; shift; python3 bench.py --steps 5 --warmup 2 $X "$@" 2>gpurun_out/wl/$name.err < /dev/null | tail -1 > gpurun_out/wl/$name.json
   python3 -c "
 import json; d=json.load(open('gpurun_out/wl/$name.json')); print('$name', d['value'], d['ms_per_step'], d.get('ratio'), 'dec', (d.get('decode') or {}).get('value'), (d.get('decode') or {}).get('round_trip_identical'))"; }

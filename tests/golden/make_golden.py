@@ -25,6 +25,8 @@ from oracle import oracle as O  # noqa: E402
 
 SAMPLES = ["small", "tstb", "tstc", "tstd", "badsprintf", "badqlt", "solid", "tsta", "tst1", "tst3", "fast5.to"]
 INPUT_ONLY = ["tst7"]          # the reference's largest sample: kept as an input (ratio measurements), no reference streams stored
+# the reference's other samples, kept as inputs for test_oracle_vs_compiled_reference_all_samples (tst6.fq is a copy of small.fq)
+INPUT_ONLY += ["tst2", "tst4", "tst5"]
 
 
 def edge_cases():

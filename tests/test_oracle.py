@@ -1,6 +1,5 @@
 """CPU: the oracle (oracle/sfq_oracle.c) against the reference's golden vectors, and -- when the
 compiled reference is present (build container) -- against the reference itself."""
-import glob
 import os
 
 import numpy as np
@@ -112,11 +111,15 @@ def test_rice_exception_lists_hold_the_references_positions():
     assert list(O.exc_rice_decode(ns)) == [80 * 150 + 1] and len(ns) == 11        # 32 + 40 bits, then the end: a zero bit and thirteen more
 
 
-@pytest.mark.skipif(O.ref_binary() is None or not os.path.isdir("/root/reference/samples"),
-                    reason="compiled reference / samples only exist in the build container")
+# every sample input the reference ships (its samples/*.fq, stored under tests/golden/; tst6.fq is a copy of small.fq)
+REFERENCE_SAMPLES = ["badqlt", "badsprintf", "fast5.to", "small", "solid", "tst1", "tst2", "tst3", "tst4", "tst5", "tst7", "tsta", "tstb",
+                     "tstc", "tstd"]
+
+
+@pytest.mark.skipif(O.ref_binary() is None, reason="compiled reference only exists in the build container")
 def test_oracle_vs_compiled_reference_all_samples():
-    for f in sorted(glob.glob("/root/reference/samples/*.fq")):
-        fq = open(f, "rb").read()
+    for f in REFERENCE_SAMPLES:
+        fq = util.golden_fastq(f)
         if len(fq) > 1_000_000:
             levels = (3,)
         else:
