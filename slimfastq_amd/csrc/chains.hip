@@ -5,7 +5,7 @@
 //   k_hot_*             (optional) the rows the sample saw most, as an LDS image for the quality kernels' workgroups
 //   k_qlt_encode_c      QltSave::save_1/2/3's symbol walk (qlts.cpp:74-136), one chain per lane, rows frozen
 //   k_qlt_decode_c      QltLoad::load_1/2/3 (qlts.cpp:163-234), likewise
-//   k_gen_count / k_gen_rows / k_gen_encode_c / k_gen_decode_c   bases: see the section below
+//   k_gen_count / k_gen_rows / k_gen_encode_c / k_gen_pack_raw / k_gen_decode_c   bases: see the section below
 //   k_rec_count(_f) / k_rec_frozen_rows                          the header prior's counting pass and rows
 //   k_rec_tokens -> k_rec_code                                   headers: a record per lane makes the symbols, a chain per lane codes them
 //   k_rec_encode_f / k_rec_encode_c                              headers, a chain per lane all the way (what the token step leaves)
@@ -1011,30 +1011,6 @@ __global__ __launch_bounds__(THREADS) void k_gen_encode_c(ChainArgs a, u32 c0, u
     rc.init(ring, threadIdx.x, outp, cap);
     const u32* rows = (!FLAT && live) ? gen_rows_of(a, cp.b) : nullptr;
     u32 illegal = 0;
-    if (a.flat_raw && (FLAT || !__any(rows != nullptr))) {
-        // no model, no coder (round 5b, block format 10): a base is two bits whatever comes before it, and a range coder that is told so writes a byte per four
-        // bases -- after a shift, a multiply, a renormalisation step and its carry test.  The chain's bases, four a byte (the first in the low bits), across
-        // its records' ends; the last byte padded with zeros.  N-like bases code as 0, as with the coder (the exception lists restore them).
-        rc.init_raw(ring, threadIdx.x, outp, cap);
-        u32 acc = 0, nb = 0;
-        illegal = walk_bases_q(a, cp.r0, cp.nrec, live ? d->solid : 0u, lut,
-            [&](u32 sym, u32 k) {
-                acc |= (sym & ((1u << (2u * k)) - 1u)) << nb;                 // (nb <= 6, 2 k <= 8: within 14 bits)
-                nb += 2u * k;
-                const u32 full = nb >= 8u ? ~0u : 0u;
-                rc.put_if(full, acc & 0xffu);
-                acc >>= 8u & full; nb -= 8u & full;
-                rc.drain();
-            },
-            a.exc_flag, cp.sub_lo, cp.sub_len);
-        if (live) {
-            if (nb) rc.put_if(~0u, acc & 0xffu);
-            a.csz[c] = rc.finish_raw();
-            if (rc.err & 2) atomicMax(&a.m.blocks[cp.b].status, (u32)(-SFQ_E_OVERFLOW));
-            if (illegal) atomicMax(&a.m.blocks[cp.b].status, (u32)(-SFQ_E_GENCHAR));
-        }
-        return;
-    }
     if (a.flat_quads && (FLAT || !__any(rows != nullptr))) {
         // no model, four bases a symbol (round 5): a shift, a multiply and ONE renormalisation step per four bases -- a byte leaves per full
         // quad, exactly -- where the initial row's 3 of 12 took a divide and a step per base (0.94e9 of the default call's 6.6e9 wave instructions)
@@ -1072,11 +1048,161 @@ __global__ __launch_bounds__(THREADS) void k_gen_encode_c(ChainArgs a, u32 c0, u
         if (illegal) atomicMax(&a.m.blocks[cp.b].status, (u32)(-SFQ_E_GENCHAR));
     }
 }
+// ---- bases without a model, packed by a wavefront per chain (block format 10, "chn.idx" flag bit 7) ----------------------------
+// The chain's bases two bits each, four a byte (the first in the low bits), across its records' ends; the last byte padded with
+// zeros; N-like, illegal and lowercase characters code as gen_code_of(c) & 3.  Lane i of the wave owns output dword t = i + 64 j:
+// bases 16 t .. 16 t + 15 of the concatenation.  It finds the record of its first base in the prefix of the line lengths, takes its
+// sixteen bytes from that record and the ones behind it (one, or two where a line ends inside the dword), and the wave stores 256
+// contiguous bytes.  Records come 64 at a time; a dword that straddles two such chunks is carried over in a register.
+// A byte position j of a dword's sixteen as a byte mask over a uint4: the bytes [0, n), n in [0, 16]
+__device__ __forceinline__ uint4 gp_below(u32 n) {
+    const u64 lo = n >= 8u ? ~0ull : (1ull << (8u * n)) - 1ull;
+    const u64 hi = n >= 16u ? ~0ull : n <= 8u ? 0ull : (1ull << (8u * (n - 8u))) - 1ull;
+    return make_uint4((u32)lo, (u32)(lo >> 32), (u32)hi, (u32)(hi >> 32));
+}
+// 16 bytes at any offset, those outside [0, nbytes) read as zero
+__device__ __forceinline__ uint4 gp_load16(const u8* buf, u64 nbytes, long long at) {
+    if (at >= 0 && (u64)at + 16u <= nbytes) return load16(buf, nbytes, (u64)at);
+    u32 w[4] = {0, 0, 0, 0};
+    for (u32 i = 0; i < 16; i++) { const long long p = at + (long long)i; if (p >= 0 && (u64)p < nbytes) w[i >> 2] |= (u32)buf[p] << ((i & 3) * 8); }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+// four bytes -> their codes (a byte each), the bytes of `valid` that are not an upper-case ACGT in `odd` (bit 7 of the byte), illegal ones in `ill`
+__device__ __forceinline__ u32 gp_codes(u32 w, u32 valid, u32& odd, u32& ill) {
+    const u32 s1 = w >> 1;
+    u32 cd = (s1 ^ (w >> 2)) & 0x03030303u;                                               // A C G T (a c g t) -> 0 1 2 3
+    const u32 want = __builtin_amdgcn_perm(0u, 0x47544341u, s1 & 0x03030303u);            // "ACTG"[(c >> 1) & 3]: the letter c should be, if it is one
+    odd = 0; ill = 0;
+    if ((want ^ w) & valid) {                                                             // (rare: N, lowercase, SOLiD digits, anything else)
+        cd = 0;
+#pragma unroll
+        for (u32 i = 0; i < 4; i++) {
+            const u32 ch = (w >> (8u * i)) & 0xffu, g = gen_code_of(ch);
+            cd |= (g & 3u) << (8u * i);
+            if ((valid >> (8u * i)) & 0xffu) {
+                if (g > 3u || is_lower_base(ch)) odd |= 0x80u << (8u * i);
+                if (g & 0x10u) ill = 1;
+            }
+        }
+    }
+    return cd & valid & 0x03030303u;
+}
+// codes of bases 4 d .. 4 d + 3 (a byte each) -> bits 0-3 and 16-19
+__device__ __forceinline__ u32 gp_fold(u32 cd) { return cd | (cd >> 6); }
+// bit 7 of each byte of four dwords -> a bit per byte of the sixteen
+__device__ __forceinline__ u32 gp_nib(u32 t) { return ((t >> 7) * 0x01020408u) >> 24; }
+__device__ __forceinline__ u32 gp_bits16(u32 o0, u32 o1, u32 o2, u32 o3) { return gp_nib(o0) | gp_nib(o1) << 4 | gp_nib(o2) << 8 | gp_nib(o3) << 12; }
+__global__ __launch_bounds__(256) void k_gen_pack_raw(ChainArgs a, u32 c0, u32 c1) {
+    const u32 lane = threadIdx.x & 63u;
+    const u32 c = c0 + blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (c >= c1) return;                                                                  // (the whole wave)
+    ChainPos cp = chain_pos(a, c); chain_seg_encode(a, cp);
+    const u32 solid = a.m.blocks[cp.b].solid;
+    u32 cap = 0;
+    u32* out = reinterpret_cast<u32*>(chain_region(a, cp, SFQ_S_GEN, 3, 4, cap));
+    const u8* buf = a.st_off ? a.st_buf : a.m.fq;
+    const u64 nbytes = a.st_off ? a.st_bytes : a.nbytes;
+    u32 done = 0;          // bases of the chunks before this one
+    u32 carry = 0;         // the codes of the dword the previous chunk ended inside
+    u32 illegal = 0;
+    for (u32 k0 = 0; k0 < cp.nrec; k0 += 64u) {
+        // the chunk's base lines (LineWalk::bounds)
+        const u32 k = k0 + lane;
+        u64 b0 = 0, b1 = 0;
+        if (k < cp.nrec) {
+            const u64 r = cp.r0 + k;
+            if (a.st_off) { b0 = a.st_off[r]; b1 = b0 + a.st_len[r]; }
+            else { b0 = a.m.line_off[4 * r + 1] + solid; b1 = a.m.line_off[4 * r + 2] - 1; }
+            if (cp.sub_len) {
+                if (b1 < b0) b1 = b0;
+                const u64 lo = b0 + cp.sub_lo;
+                b0 = lo < b1 ? lo : b1;
+                b1 = b0 + cp.sub_len < b1 ? b0 + cp.sub_len : b1;
+            }
+            if (b1 < b0) b1 = b0;
+        }
+        const u32 len = (u32)(b1 - b0);
+        u32 inc = len;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const u32 o = (u32)__shfl_up((int)inc, d, 64); if (lane >= (u32)d) inc += o; }
+        const u32 st = inc - len;                                                         // the record's first base in the chunk
+        const u32 tot = (u32)__shfl((int)inc, 63, 64);
+        const u32 end = done + tot;
+        const bool last_chunk = k0 + 64u >= cp.nrec;
+        const u32 t0 = done >> 4, t1 = (end + 15u) >> 4;                                  // the dwords the chunk touches
+        for (u32 tb = t0; tb < t1; tb += 64u) {
+            const u32 t = tb + lane;
+            const u32 d0 = 16u * t;
+            const u32 lo = d0 > done ? d0 : done, hi = d0 + 16u < end ? d0 + 16u : end;   // this lane's bases [lo, hi) (lo >= hi: none)
+            // the record of base lo: the last one that starts at or before it (a record of no bases starts where the next one does)
+            u32 kr = 0;
+#pragma unroll
+            for (u32 s = 32; s > 0; s >>= 1) { const u32 sk = (u32)__shfl((int)st, (int)(kr + s), 64); if (sk + done <= lo) kr += s; }
+            uint4 w = make_uint4(0, 0, 0, 0);
+            u32 pos = lo;
+            while (__any(pos < hi)) {                                                     // one record a round: one round, two where a line ends inside the dword
+                const u32 ks = kr & 63u;
+                const u32 sk = (u32)__shfl((int)st, (int)ks, 64) + done, lk = (u32)__shfl((int)len, (int)ks, 64);
+                const u64 bk = (u64)__shfl((unsigned long long)b0, (int)ks, 64);
+                const u32 e = sk + lk < hi ? sk + lk : hi;
+                if (pos < hi && e > pos) {
+                    const u32 j = pos - d0;                                               // the piece is bytes [j, j + e - pos) of the dword
+                    const uint4 v = gp_load16(buf, nbytes, (long long)(bk + (pos - sk)) - (long long)j);
+                    const uint4 m0 = gp_below(j), m1 = gp_below(j + (e - pos));
+                    w.x = (w.x & ~(m1.x & ~m0.x)) | (v.x & m1.x & ~m0.x);
+                    w.y = (w.y & ~(m1.y & ~m0.y)) | (v.y & m1.y & ~m0.y);
+                    w.z = (w.z & ~(m1.z & ~m0.z)) | (v.z & m1.z & ~m0.z);
+                    w.w = (w.w & ~(m1.w & ~m0.w)) | (v.w & m1.w & ~m0.w);
+                    pos = e;
+                }
+                kr++;
+            }
+            const bool any = lo < hi;
+            const uint4 va = gp_below(any ? hi - d0 : 0u), vb = gp_below(any ? lo - d0 : 0u);
+            const uint4 vm = make_uint4(va.x & ~vb.x, va.y & ~vb.y, va.z & ~vb.z, va.w & ~vb.w);
+            u32 o0, o1, o2, o3, i0, i1, i2, i3;
+            const u32 f0 = gp_fold(gp_codes(w.x, vm.x, o0, i0)), f1 = gp_fold(gp_codes(w.y, vm.y, o1, i1));
+            const u32 f2 = gp_fold(gp_codes(w.z, vm.z, o2, i2)), f3 = gp_fold(gp_codes(w.w, vm.w, o3, i3));
+            illegal |= i0 | i1 | i2 | i3;
+            // bytes (c0 | c1 << 2, c2 | c3 << 2) of two dwords side by side, then the high nibbles folded down: a byte per four bases
+            u32 p01 = __builtin_amdgcn_perm(f1, f0, 0x06020400u), p23 = __builtin_amdgcn_perm(f3, f2, 0x06020400u);
+            p01 |= p01 >> 12; p23 |= p23 >> 12;
+            u32 code = __builtin_amdgcn_perm(p23, p01, 0x05040100u);
+            if (t == t0) code |= carry;                                                   // (the bases of the chunk before, below `done`)
+            // an N, a lowercase base or an illegal character marks its record for the pass over the exceptions (k_gen_exc_w)
+            u32 odd = gp_bits16(o0, o1, o2, o3);
+            if (a.exc_flag) {
+                while (__any(odd != 0u)) {
+                    const u32 jb = odd ? (u32)__builtin_ctz(odd) : 0u;
+                    u32 ko = 0;
+#pragma unroll
+                    for (u32 s = 32; s > 0; s >>= 1) { const u32 sk = (u32)__shfl((int)st, (int)(ko + s), 64); if (sk + done <= d0 + jb) ko += s; }
+                    const u32 ke = (u32)__shfl((int)inc, (int)ko, 64) + done;              // the record's end
+                    if (odd) {
+                        a.exc_flag[cp.r0 + k0 + ko] = 1;
+                        odd &= ke - d0 >= 16u ? 0u : ~((1u << (ke - d0)) - 1u);
+                    }
+                }
+            }
+            const bool held = t == t1 - 1u && (end & 15u) && !last_chunk;               // finished by the next chunk
+            if (t < t1 && !held && 4u * t < cap) out[t] = code;
+            if (!last_chunk) carry = (end & 15u) ? (u32)__shfl((int)code, (int)((t1 - 1u - tb) & 63u), 64) : 0u;
+        }
+        done = end;
+    }
+    if (lane == 0) {
+        const u32 n = (done + 3u) >> 2;
+        a.csz[c] = n;
+        if (n > cap) atomicMax(&a.m.blocks[cp.b].status, (u32)(-SFQ_E_OVERFLOW));
+    }
+    if (__any(illegal != 0u) && lane == 0) atomicMax(&a.m.blocks[cp.b].status, (u32)(-SFQ_E_GENCHAR));
+}
 // the base chains [c0, c1) (c1 = 0: all of them); flat: every one of them codes with the initial row
 void launch_gen_encode_c(const ChainArgs& a, hipStream_t st, u32 c0, u32 c1, bool flat) {
     constexpr int T = 256;
     if (!c1 || c1 > a.geo.nchains) c1 = a.geo.nchains;
     if (c1 <= c0) return;
+    if (a.flat_raw) { hipLaunchKernelGGL(k_gen_pack_raw, dim3((c1 - c0 + 3) / 4), dim3(256), 0, st, a, c0, c1); return; }
     const dim3 grid((c1 - c0 + T - 1) / T);
     if (flat) hipLaunchKernelGGL((k_gen_encode_c<T, true>), grid, dim3(T), 0, st, a, c0, c1);
     else hipLaunchKernelGGL((k_gen_encode_c<T, false>), grid, dim3(T), 0, st, a, c0, c1);
