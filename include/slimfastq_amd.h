@@ -258,12 +258,33 @@ int sfq_decode_blocks_host(sfq_ctx* ctx, const sfq_params* params, const sfq_blo
 
 /* ---- the ".sfq" container (host only) ----------------------------------------------------------
  * Replaces FilerSave + the info page (filer.cpp:217-242, config.cpp:334-347) for hosts that assemble an archive
- * themselves, e.g. the writer rank of a multi-GPU job (slimfastq_amd/dist_compress.py): info_text is the info
- * page ("key=value\n" lines), then n_streams named byte streams (names of at most 8 bytes: filer.cpp:42-47). */
+ * themselves: info_text is the info page ("key=value\n" lines), then n_streams named byte streams (names of at most
+ * 8 bytes: filer.cpp:42-47).  A block-format archive of several calls' results: sfq_archive_write_segments below. */
 int sfq_archive_write(const char* path, const char* info_text, uint32_t n_streams,
                       const char* const* names, const uint8_t* const* data, const uint64_t* sizes);
 /* The "blk.idx" stream of a block-format archive from a block index; returns its size (out == NULL: size only). */
 int64_t sfq_pack_block_index(const sfq_block_info* blocks, uint32_t n, uint8_t* out, uint64_t cap);
+
+/* One encode call's results, as they are to be stored: ONE SEGMENT of a block-format archive.
+ * Every pointer may be NULL where its size is 0. */
+typedef struct sfq_segment {
+    const uint8_t* streams[SFQ_NSTREAMS];  /* the call's part of every stream (sfq_result.stream_offset / stream_bytes) */
+    uint64_t stream_bytes[SFQ_NSTREAMS];
+    const sfq_block_info* blocks;          /* sfq_get_block_index */
+    uint32_t n_blocks, reserved;
+    const uint8_t* first_hdrs;  uint64_t first_hdr_bytes;       /* sfq_get_first_headers */
+    const uint8_t* qlt_prior;   uint64_t qlt_prior_bytes;       /* sfq_get_qlt_prior ("qlt.pri") */
+    const uint8_t* chain_index; uint64_t chain_index_bytes;     /* sfq_get_chain_index ("chn.idx") */
+    const uint8_t* rec_prior;   uint64_t rec_prior_bytes;       /* sfq_get_rec_prior ("rec.pri") */
+    uint64_t raw_bytes;                    /* bytes of FASTQ text the call coded */
+} sfq_segment;
+/* A block-format archive of n segments, in order (the writer rank of a multi-GPU job: one segment per slab of every rank);
+ * the layout, info keys and index streams the CLI writes.  tables: SFQ_TABLES_FROZEN or SFQ_TABLES_ADAPTIVE, as the calls
+ * coded; shared_prior != 0: a segment without priors of its own decodes from the previous segment's (info key
+ * "seg.shared_prior").  Segments without blocks are left out; SFQ_E_ARG if none is left, or if a segment's stream bytes
+ * are not what its blocks say. */
+int sfq_archive_write_segments(const char* path, const char* orig_name, int level, uint32_t tables, int shared_prior,
+                               uint32_t n, const sfq_segment* segs);
 
 /* ---- utilities (host only, no GPU) ----------------------------------------------------------- */
 /* Deterministic synthetic FASTQ. kind 0 = 150 bp-style Illumina reads of

@@ -26,6 +26,7 @@ EXPORTS = [
     "sfq_decode_blocks_host", "sfq_synth_fastq", "sfq_abi_version", "sfq_get_qlt_prior", "sfq_set_qlt_prior",
     "sfq_archive_write", "sfq_pack_block_index", "sfq_ctx_device_memory", "sfq_get_chain_index", "sfq_set_chain_index", "sfq_get_rec_prior", "sfq_set_rec_prior", "sfq_build_priors",
     "sfq_host_alloc", "sfq_host_free", "sfq_count_priors", "sfq_prior_counts_words", "sfq_get_prior_counts", "sfq_set_prior_counts",
+    "sfq_archive_write_segments",
 ]
 
 
@@ -47,6 +48,14 @@ class Result(C.Structure):
                 ("stream_bytes", C.c_uint64 * NSTREAMS), ("stream_offset", C.c_uint64 * NSTREAMS),
                 ("total_bytes", C.c_uint64), ("first_hdr_bytes", C.c_uint64), ("n_chains", C.c_uint32), ("reserved", C.c_uint32),
                 ("kernel_ms", C.c_double * 8), ("coder_ms", C.c_double * 4)]
+
+
+class Segment(C.Structure):
+    _fields_ = [("streams", C.c_void_p * NSTREAMS), ("stream_bytes", C.c_uint64 * NSTREAMS),
+                ("blocks", C.POINTER(BlockInfo)), ("n_blocks", C.c_uint32), ("reserved", C.c_uint32),
+                ("first_hdrs", C.c_void_p), ("first_hdr_bytes", C.c_uint64), ("qlt_prior", C.c_void_p), ("qlt_prior_bytes", C.c_uint64),
+                ("chain_index", C.c_void_p), ("chain_index_bytes", C.c_uint64), ("rec_prior", C.c_void_p), ("rec_prior_bytes", C.c_uint64),
+                ("raw_bytes", C.c_uint64)]
 
 
 class SfqError(RuntimeError):
@@ -129,6 +138,7 @@ def lib():
         L.sfq_archive_write.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(u64)]
         L.sfq_pack_block_index.argtypes = [C.POINTER(BlockInfo), C.c_uint32, u8p, u64]
         L.sfq_pack_block_index.restype = C.c_int64
+        L.sfq_archive_write_segments.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(Segment)]
         _lib = L
     return _lib
 
@@ -144,6 +154,32 @@ def synth_fastq(n_reads, read_len=150, seed=1, kind=0, first_read=0) -> bytes:
     if got != need:
         raise SfqError(got, "synth")
     return buf.tobytes()
+
+
+def archive_write_segments(path: str, parts, level: int, orig_name: str, tables=TABLES_FROZEN, shared_prior=False):
+    """One block-format archive, a segment per part, in order (sfq_archive_write_segments).  parts: dicts of one encode call's
+    results: streams=[bytes] * NSTREAMS, blocks=[BlockInfo], first=bytes, prior=bytes, chains=bytes, rec_prior=bytes, raw=int."""
+    keep = []
+
+    def ptr(b):
+        if not len(b):
+            return None
+        keep.append(np.frombuffer(b, np.uint8))                      # (no copy: the bytes stay where they are)
+        return keep[-1].ctypes.data
+    segs = (Segment * len(parts))()
+    for g, p in zip(segs, parts):
+        for s in range(NSTREAMS):
+            g.streams[s] = ptr(p["streams"][s]); g.stream_bytes[s] = len(p["streams"][s])
+        keep.append((BlockInfo * len(p["blocks"]))(*p["blocks"]))
+        g.blocks = C.cast(keep[-1], C.POINTER(BlockInfo)); g.n_blocks = len(p["blocks"])
+        g.first_hdrs = ptr(p["first"]); g.first_hdr_bytes = len(p["first"])
+        g.qlt_prior = ptr(p["prior"]); g.qlt_prior_bytes = len(p["prior"])
+        g.chain_index = ptr(p["chains"]); g.chain_index_bytes = len(p["chains"])
+        g.rec_prior = ptr(p["rec_prior"]); g.rec_prior_bytes = len(p["rec_prior"])
+        g.raw_bytes = p["raw"]
+    rc = lib().sfq_archive_write_segments(path.encode(), orig_name.encode(), level, tables, int(shared_prior), len(parts), segs)
+    if rc:
+        raise SfqError(rc, "cannot write " + path)
 
 
 class Encoded:

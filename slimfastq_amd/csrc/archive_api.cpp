@@ -36,4 +36,31 @@ int64_t sfq_pack_block_index(const sfq_block_info* blocks, uint32_t n, uint8_t* 
     return (int64_t)v.size();
 }
 
+int sfq_archive_write_segments(const char* path, const char* orig_name, int level, uint32_t tables, int shared_prior,
+                               uint32_t n, const sfq_segment* segs) {
+    if (!path || !orig_name || (n && !segs) || (tables != SFQ_TABLES_FROZEN && tables != SFQ_TABLES_ADAPTIVE)) return SFQ_E_ARG;
+    sfqc::SegmentedIndex idx;
+    std::vector<uint8_t> streams[SFQ_NSTREAMS];
+    for (uint32_t i = 0; i < n; i++) {
+        const sfq_segment& g = segs[i];
+        if (!g.n_blocks) continue;
+        if (!g.blocks) return SFQ_E_ARG;
+        for (int s = 0; s < SFQ_NSTREAMS; s++) {
+            uint64_t want = 0;
+            for (uint32_t b = 0; b < g.n_blocks; b++) want += g.blocks[b].size[s];
+            if (g.stream_bytes[s] != want || (want && !g.streams[s])) return SFQ_E_ARG;
+            streams[s].insert(streams[s].end(), g.streams[s], g.streams[s] + want);
+        }
+        idx.add(g);
+    }
+    if (idx.segs.empty()) return SFQ_E_ARG;                 // (an archive of no blocks does not decode)
+    const bool frozen = tables == SFQ_TABLES_FROZEN;
+    sfqc::Archive a;
+    a.info = idx.info(level, orig_name, frozen, shared_prior != 0);
+    for (int s = 0; s < SFQ_NSTREAMS; s++) if (!streams[s].empty()) a.add(sfq_stream_name(s), std::move(streams[s]));
+    for (auto& s : idx.streams(frozen)) a.add(s.first, std::move(s.second));
+    std::string err;
+    return sfqc::write_file(path, a, err) ? SFQ_OK : SFQ_E_ARG;
+}
+
 }  // extern "C"

@@ -22,11 +22,8 @@
 #include "container.h"
 
 static const int   kInternalVersion = 6;      // config.cpp:41
-static const int   kBlockVersion = 10;         // 7: block format, the reference's quirks kept; 8: lossless ("gen.lc", 14 stream sizes per index entry);
-                                                // 9: "chn.idx" may carry flag bits 2-5 (difference-coded lists, segments, Rice-coded base exceptions, the bases' match
-                                                //    model): a reader of version 8 did not look at flags it did not know, so what sets them says 9 and is refused there
-                                                // 10: flag bit 7 (bases without a model as two bits each, no coder): a reader of version 9 refuses the flag, so what sets it says 10
-static const int   kBlockVersionMin = 7;
+using sfqc::kBlockVersion;                       // the block format's "version" (container.h)
+using sfqc::kBlockVersionMin;
 static const char* kUserVersion = "2.04-amd";
 
 static bool g_encode = true;
@@ -113,16 +110,6 @@ struct Opts {
     long chain_reads = 0;                                              // -C
 };
 
-// "seg.idx": an archive is a sequence of SEGMENTS, each the result of one library call (one slab of a large
-// input, or one rank of a multi-GPU job): its blocks, its share of every stream, its own quality prior.
-struct Segment { uint64_t nblocks, prior_bytes, raw_bytes, chain_bytes, recpri_bytes; };
-static void put_v(std::vector<uint8_t>& o, uint64_t v) { while (v >= 0x80) { o.push_back((uint8_t)(v | 0x80)); v >>= 7; } o.push_back((uint8_t)v); }
-static bool get_v(const std::vector<uint8_t>& b, size_t& p, uint64_t& v) {
-    v = 0;
-    for (int sh = 0; sh < 64; sh += 7) { if (p >= b.size()) return false; const uint8_t c = b[p++]; v |= (uint64_t)(c & 0x7f) << sh; if (!(c & 0x80)) return true; }
-    return false;
-}
-
 // Growable byte buffer that never zero-fills (a std::vector would touch gigabytes just to size them).
 struct Bytes {
     uint8_t* p = nullptr; size_t n = 0, cap = 0, touched = 0;
@@ -152,14 +139,32 @@ static bool fill(FILE* f, Bytes& buf, size_t want, bool& eof) {
     }
     return !ferror(f);
 }
-// Bytes of [p, p+n) that hold whole records (a record is four lines), given that p starts at a record.
-static size_t whole_records(const uint8_t* p, size_t n) {
-    size_t nl = 0;
-    for (size_t i = 0; i < n; i++) nl += p[i] == '\n';
-    size_t drop = nl & 3, end = n;
-    while (end > 0 && p[end - 1] != '\n') end--;                    // the partial last line
+// Bytes of [p, p+n) that hold whole records (a record is four lines), given that p starts at a record and [p, p+n) holds nl
+// newlines: the partial last line goes, and nl % 4 lines more.
+static size_t whole_records(const uint8_t* p, size_t n, uint64_t nl) {
+    size_t drop = (size_t)(nl & 3), end = n;
+    while (end > 0 && p[end - 1] != '\n') end--;
     while (drop && end > 0) { end--; while (end > 0 && p[end - 1] != '\n') end--; drop--; }
     return end;
+}
+
+// One finished library call (a segment of raw bytes of text) into the archive's index.
+static void collect(sfq_ctx* ctx, const sfq_result& res, uint64_t raw, sfqc::SegmentedIndex& idx) {
+    std::vector<sfq_block_info> blocks(res.n_blocks);
+    sfq_get_block_index(ctx, blocks.data(), res.n_blocks);
+    std::vector<uint8_t> first((size_t)res.first_hdr_bytes + 1);
+    sfq_get_first_headers(ctx, first.data(), res.first_hdr_bytes);
+    auto blob = [ctx](int64_t (*get)(sfq_ctx*, uint8_t*, uint64_t)) {
+        std::vector<uint8_t> v((size_t)std::max<int64_t>(0, get(ctx, nullptr, 0)));
+        if (!v.empty()) get(ctx, v.data(), v.size());
+        return v;
+    };
+    const std::vector<uint8_t> pri = blob(sfq_get_qlt_prior), chn = blob(sfq_get_chain_index), rpr = blob(sfq_get_rec_prior);
+    sfq_segment g; memset(&g, 0, sizeof g);
+    g.blocks = blocks.data(); g.n_blocks = res.n_blocks; g.first_hdrs = first.data(); g.first_hdr_bytes = res.first_hdr_bytes;
+    g.qlt_prior = pri.data(); g.qlt_prior_bytes = pri.size(); g.chain_index = chn.data(); g.chain_index_bytes = chn.size();
+    g.rec_prior = rpr.data(); g.rec_prior_bytes = rpr.size(); g.raw_bytes = raw;
+    idx.add(g);
 }
 
 static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, const std::string& fil) {
@@ -182,10 +187,8 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     p.tables = frozen ? SFQ_TABLES_FROZEN : SFQ_TABLES_ADAPTIVE;
     p.chain_reads = (uint32_t)std::max(0l, o.chain_reads);
 
-    std::vector<uint8_t> streams[SFQ_NSTREAMS], first_all, prior_all, chain_all, recpri_all;
-    std::vector<sfq_block_info> blocks_all;
-    std::vector<Segment> segs;
-    uint64_t total_in = 0, total_records = 0;
+    std::vector<uint8_t> streams[SFQ_NSTREAMS];
+    sfqc::SegmentedIndex idx;                                          // one segment per library call
     // (Mapping the file and handing the mapping to the library was measured: the copy engine pins page-cache pages one
     //  by one, 4-10x slower than reading into an ordinary buffer first.)
     size_t file_left = SIZE_MAX;                                       // bytes not yet read, when the input is a regular file
@@ -290,11 +293,8 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             const bool last = off >= fsize;
             uint8_t* text = buf[cur];
             size_t use = have[cur];
-            if (!last) {                                                // whole records only: drop the partial last line and nl % 4 lines more
-                size_t drop = (size_t)(nls[cur] & 3), end = use;
-                while (end > 0 && text[end - 1] != '\n') end--;
-                while (drop && end > 0) { end--; while (end > 0 && text[end - 1] != '\n') end--; drop--; }
-                use = end;
+            if (!last) {                                                // whole records only
+                use = whole_records(text, use, nls[cur]);
                 if (use == 0) croak("a record longer than the slab (%zu MiB): raise -S", slab >> 20);
             }
             // the next slab: the carried-over tail, then file bytes read by the threads while this one is coded
@@ -304,7 +304,7 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             size_t len = 0;
             if (carry > (64u << 20)) croak("a record longer than 64 MiB next to a slab boundary: raise -S");
             memcpy(buf[nxt], text + use, carry);
-            uint64_t carry_nl = 0; for (size_t i = 0; i < carry; i++) carry_nl += buf[nxt][i] == '\n';
+            const uint64_t carry_nl = (uint64_t)std::count(buf[nxt], buf[nxt] + carry, (uint8_t)'\n');
             if (!last) { len = std::min(slab, fsize - off); start_read(r, buf[nxt] + carry, off, len); }
             sfq_result res;
             uint8_t* outp = pinned[2 + ob];
@@ -317,14 +317,8 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             }
             if (rc) croak("%s", sfq_last_error(ctx));
             tick("sfq_encode_blocks_host");
-            const size_t b0 = blocks_all.size();
-            blocks_all.resize(b0 + res.n_blocks);
-            sfq_get_block_index(ctx, blocks_all.data() + b0, res.n_blocks);
-            for (size_t b = b0; b < blocks_all.size(); b++) { blocks_all[b].first_record += total_records; blocks_all[b].first_hdr_off += first_all.size(); }
-            const size_t f0 = first_all.size();
-            first_all.resize(f0 + (size_t)res.first_hdr_bytes + 1);
-            sfq_get_first_headers(ctx, first_all.data() + f0, res.first_hdr_bytes);
-            first_all.resize(f0 + (size_t)res.first_hdr_bytes);
+            collect(ctx, res, use, idx);
+            tick("collect slab");
             writer.join();
             {
                 const sfq_result rr = res; sfqc::PagedWriter* w = &pw; int* ids = sid; const uint8_t* src = outp;
@@ -336,16 +330,6 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
                 });
                 if (outp == big_out.p) writer.join(); else ob ^= 1;
             }
-            Segment sg{res.n_blocks, 0, use, 0, 0};
-            const int64_t pn = sfq_get_qlt_prior(ctx, nullptr, 0);
-            if (pn > 0) { const size_t q0 = prior_all.size(); prior_all.resize(q0 + (size_t)pn); sfq_get_qlt_prior(ctx, prior_all.data() + q0, (uint64_t)pn); sg.prior_bytes = (uint64_t)pn; }
-            const int64_t cn = sfq_get_chain_index(ctx, nullptr, 0);
-            if (cn > 0) { const size_t q0 = chain_all.size(); chain_all.resize(q0 + (size_t)cn); sfq_get_chain_index(ctx, chain_all.data() + q0, (uint64_t)cn); sg.chain_bytes = (uint64_t)cn; }
-            const int64_t rn = sfq_get_rec_prior(ctx, nullptr, 0);
-            if (rn > 0) { const size_t q0 = recpri_all.size(); recpri_all.resize(q0 + (size_t)rn); sfq_get_rec_prior(ctx, recpri_all.data() + q0, (uint64_t)rn); sg.recpri_bytes = (uint64_t)rn; }
-            segs.push_back(sg);
-            total_in += use; total_records += res.n_records;
-            tick("collect slab");
             join_read(r);
             tick("wait for the next slab");
             have[nxt] = carry + len; nls[nxt] = carry_nl + r.nl; off += len;
@@ -367,7 +351,7 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         tick("read slab");
         if (legacy && !eof) continue;
         size_t use = fq.n;
-        if (!eof) { use = whole_records(fq.p, fq.n); if (use == 0) continue; }
+        if (!eof) { use = whole_records(fq.p, fq.n, (uint64_t)std::count(fq.p, fq.p + fq.n, (uint8_t)'\n')); if (use == 0) continue; }
         const uint8_t* text = fq.p;
         if (use == 0) break;
         decide_tables(eof ? use : (64ull << 20));                          // (a pipe: more than one slab of text is a big file)
@@ -378,72 +362,35 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         const int rc = sfq_encode_blocks_host(ctx, text, use, &p, out.p, bound, &res);
         if (rc) croak("%s", sfq_last_error(ctx));
         tick("sfq_encode_blocks_host");
-        const size_t b0 = blocks_all.size();
-        blocks_all.resize(b0 + res.n_blocks);
-        sfq_get_block_index(ctx, blocks_all.data() + b0, res.n_blocks);
-        for (size_t b = b0; b < blocks_all.size(); b++) { blocks_all[b].first_record += total_records; blocks_all[b].first_hdr_off += first_all.size(); }
-        const size_t f0 = first_all.size();
-        first_all.resize(f0 + (size_t)res.first_hdr_bytes + 1);
-        sfq_get_first_headers(ctx, first_all.data() + f0, res.first_hdr_bytes);
-        first_all.resize(f0 + (size_t)res.first_hdr_bytes);
+        collect(ctx, res, use, idx);
         for (int s = 0; s < SFQ_NSTREAMS; s++)
             streams[s].insert(streams[s].end(), out.p + res.stream_offset[s], out.p + res.stream_offset[s] + res.stream_bytes[s]);
-        Segment sg{res.n_blocks, 0, use, 0, 0};
-        if (!legacy) {
-            const int64_t pn = sfq_get_qlt_prior(ctx, nullptr, 0);
-            if (pn > 0) { const size_t q0 = prior_all.size(); prior_all.resize(q0 + (size_t)pn); sfq_get_qlt_prior(ctx, prior_all.data() + q0, (uint64_t)pn); sg.prior_bytes = (uint64_t)pn; }
-            const int64_t cn = sfq_get_chain_index(ctx, nullptr, 0);
-            if (cn > 0) { const size_t q0 = chain_all.size(); chain_all.resize(q0 + (size_t)cn); sfq_get_chain_index(ctx, chain_all.data() + q0, (uint64_t)cn); sg.chain_bytes = (uint64_t)cn; }
-            const int64_t rn = sfq_get_rec_prior(ctx, nullptr, 0);
-            if (rn > 0) { const size_t q0 = recpri_all.size(); recpri_all.resize(q0 + (size_t)rn); sfq_get_rec_prior(ctx, recpri_all.data() + q0, (uint64_t)rn); sg.recpri_bytes = (uint64_t)rn; }
-        }
-        segs.push_back(sg);
-        total_in += use; total_records += res.n_records;
         memmove(fq.p, fq.p + use, fq.n - use); fq.n -= use;               // keep the partial record for the next slab
     }
     if (in != stdin) fclose(in);
-    if (segs.empty()) croak("fastq file: empty input");
+    if (idx.segs.empty()) croak("fastq file: empty input");
     tick("collect streams");
 
-    sfqc::Archive a;                                                   // info keys in the reference's order (config.cpp:334-347, usrs.cpp:262-266, recs.cpp:71, gens.cpp:104, usrs.cpp:405)
-    a.set("whoami", "slimfastq");
-    a.set("version", legacy ? kInternalVersion : kBlockVersion);
-    a.set("config.level", o.level);
-    a.set("orig.filename", usr.empty() ? "<< stdin >>" : usr);
-    if (!usr.empty() || !legacy) a.set("orig.size", (long long)total_in);
-    if (legacy) {
-        const sfq_block_info& b = blocks_all[0];
-        if (first_all.size() >= 400) croak("first header too long for the reference's info page (recs.cpp:30)");
+    const std::string orig_name = usr.empty() ? "<< stdin >>" : usr;
+    sfqc::Archive a;
+    if (legacy) {                                                      // info keys in the reference's order (config.cpp:334-347, usrs.cpp:262-266, recs.cpp:71, gens.cpp:104, usrs.cpp:405)
+        const sfq_block_info& b = idx.blocks[0];
+        if (idx.first.size() >= 400) croak("first header too long for the reference's info page (recs.cpp:30)");
+        a.set("whoami", "slimfastq");
+        a.set("version", kInternalVersion);
+        a.set("config.level", o.level);
+        a.set("orig.filename", orig_name);
+        if (!usr.empty()) a.set("orig.size", (long long)idx.raw);
         if (b.solid) a.set("usr.solid", 1);
         a.set("llen", b.llen);
         a.set("usr.2id", b.two_id);
-        a.set("rec.first", std::string(first_all.begin(), first_all.end()));
+        a.set("rec.first", std::string(idx.first.begin(), idx.first.end()));
         if (b.n_byte && b.n_byte != 'N') a.set("gen.N_byte", b.n_byte);
-        a.set("num_records", (long long)total_records);
+        a.set("num_records", (long long)idx.records);
         if (!o.quiet && b.extra_hi) a.set("qlt.extra.hi", b.extra_hi);
-    } else {
-        a.set("blk.reads", (long long)blocks_all[0].n_records);            // of the first segment (each segment carries its own in the index)
-        a.set("blk.count", (long long)blocks_all.size());
-        a.set("num_records", (long long)total_records);
-        if (segs.size() > 1) a.set("seg.count", (long long)segs.size());
-        if (frozen) a.set("blk.tables", 1);                                // frozen tables: chn.idx / rec.pri per segment
-    }
+    } else a.info = idx.info(o.level, orig_name, frozen, false);
     if (streamed) {
-        auto add = [&](const char* name, const std::vector<uint8_t>& v) { const int id = pw.stream(name); pw.append(id, v.data(), v.size()); };
-        add("blk.idx", sfqc::pack_block_index(blocks_all));
-        add("blk.hdr", first_all);
-        if (!prior_all.empty()) add("qlt.pri", prior_all);
-        if (!chain_all.empty()) add("chn.idx", chain_all);
-        if (!recpri_all.empty()) add("rec.pri", recpri_all);
-        if (segs.size() > 1) {
-            std::vector<uint8_t> si;
-            put_v(si, segs.size());
-            for (auto& g : segs) {
-                put_v(si, g.nblocks); put_v(si, g.prior_bytes); put_v(si, g.raw_bytes);
-                if (frozen) { put_v(si, g.chain_bytes); put_v(si, g.recpri_bytes); }
-            }
-            add("seg.idx", si);
-        }
+        for (auto& s : idx.streams(frozen)) pw.append(pw.stream(s.first), s.second.data(), s.second.size());
         std::string werr;
         if (!pw.finish(a.info, werr)) croak("%s", werr.c_str());
         g_partial.clear();
@@ -451,22 +398,7 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         return;
     }
     for (int s = 0; s < SFQ_NSTREAMS; s++) if (!streams[s].empty()) a.add(sfq_stream_name(s), std::move(streams[s]));
-    if (!legacy) {
-        a.add("blk.idx", sfqc::pack_block_index(blocks_all));
-        a.add("blk.hdr", first_all);
-        if (!prior_all.empty()) a.add("qlt.pri", prior_all);
-        if (!chain_all.empty()) a.add("chn.idx", chain_all);
-        if (!recpri_all.empty()) a.add("rec.pri", recpri_all);
-        if (segs.size() > 1) {
-            std::vector<uint8_t> si;
-            put_v(si, segs.size());
-            for (auto& g : segs) {
-                put_v(si, g.nblocks); put_v(si, g.prior_bytes); put_v(si, g.raw_bytes);
-                if (frozen) { put_v(si, g.chain_bytes); put_v(si, g.recpri_bytes); }
-            }
-            a.add("seg.idx", si);
-        }
-    }
+    if (!legacy) for (auto& s : idx.streams(frozen)) a.add(s.first, std::move(s.second));
     std::string err;
     tick("build archive");
     if (!sfqc::write_file(fil, a, err)) croak("%s", err.c_str());
@@ -484,7 +416,7 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     const int level = clamp_level((int)a.get_long("config.level", 2));       // config.cpp:359
     std::vector<sfq_block_info> blocks;
     std::vector<uint8_t> first;
-    std::vector<Segment> segs;
+    std::vector<sfqc::Segment> segs;
     const std::vector<uint8_t>* pri = a.find("qlt.pri");
     const std::vector<uint8_t>* chn = a.find("chn.idx");
     const std::vector<uint8_t>* rpr = a.find("rec.pri");
@@ -499,15 +431,8 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         if (!idx || !sfqc::unpack_block_index(*idx, blocks, version >= 8 ? SFQ_NSTREAMS : 10)) croak("bad block index");
         if (const std::vector<uint8_t>* h = a.find("blk.hdr")) first = *h;
         if (const std::vector<uint8_t>* si = a.find("seg.idx")) {
-            size_t q = 0; uint64_t n = 0;
-            if (!get_v(*si, q, n) || n == 0 || n > blocks.size()) croak("bad segment index");
-            segs.resize((size_t)n);
-            for (auto& g : segs) {
-                g.chain_bytes = g.recpri_bytes = 0;
-                if (!get_v(*si, q, g.nblocks) || !get_v(*si, q, g.prior_bytes) || !get_v(*si, q, g.raw_bytes)) croak("bad segment index");
-                if (frozen && (!get_v(*si, q, g.chain_bytes) || !get_v(*si, q, g.recpri_bytes))) croak("bad segment index");
-            }
-        } else segs.push_back(Segment{blocks.size(), pri ? pri->size() : 0, (uint64_t)a.get_long("orig.size", 0), chn ? chn->size() : 0, rpr ? rpr->size() : 0});
+            if (!sfqc::unpack_segment_index(*si, segs, frozen) || segs.size() > blocks.size()) croak("bad segment index");
+        } else segs.push_back(sfqc::Segment{blocks.size(), pri ? pri->size() : 0, (uint64_t)a.get_long("orig.size", 0), chn ? chn->size() : 0, rpr ? rpr->size() : 0});
         if (blocks.empty()) croak("bad block index (no blocks)");
     } else {
         sfq_block_info b; memset(&b, 0, sizeof b);
@@ -526,7 +451,7 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             b.size[s] = v->size();
         }
         blocks.push_back(b);
-        segs.push_back(Segment{1, 0, (uint64_t)a.get_long("orig.size", 0), 0, 0});
+        segs.push_back(sfqc::Segment{1, 0, (uint64_t)a.get_long("orig.size", 0), 0, 0});
     }
     FILE* of = stdout;
     if (!usr.empty()) {
@@ -551,7 +476,7 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     // page-locked buffers (kept for the life of the process, like the encoder's)
     static uint8_t* opin[2] = { nullptr, nullptr }; static size_t opin_cap = 0;
     size_t max_raw = 0; bool sized = segs.size() > 1;
-    for (const Segment& g : segs) { max_raw = std::max<size_t>(max_raw, (size_t)g.raw_bytes); if (!g.raw_bytes) sized = false; }
+    for (const sfqc::Segment& g : segs) { max_raw = std::max<size_t>(max_raw, (size_t)g.raw_bytes); if (!g.raw_bytes) sized = false; }
     if (sized && opin_cap < max_raw + 64) {
         for (auto& q : opin) { if (q) sfq_host_free(ctx, q); q = nullptr; }
         opin[0] = (uint8_t*)sfq_host_alloc(ctx, max_raw + 64); opin[1] = (uint8_t*)sfq_host_alloc(ctx, max_raw + 64);
@@ -561,7 +486,7 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     }
     std::atomic<int> wbad{0}; int ob = 0;
     Joiner writer;                                                      // (declared after what its thread uses: joined first when the scope unwinds)
-    for (const Segment& g : segs) {
+    for (const sfqc::Segment& g : segs) {
         if (g.nblocks == 0 || g.nblocks > blocks.size() - b0) croak("bad segment index");
         if (pri ? g.prior_bytes > pri->size() - pri_off : g.prior_bytes != 0) croak("bad segment index");
         if (chn ? g.chain_bytes > chn->size() - chn_off : g.chain_bytes != 0) croak("bad segment index");

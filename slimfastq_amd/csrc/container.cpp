@@ -326,4 +326,69 @@ bool unpack_block_index(const std::vector<uint8_t>& bytes, std::vector<sfq_block
     return true;
 }
 
+// ---- segments -------------------------------------------------------------------------------------------
+std::vector<uint8_t> pack_segment_index(const std::vector<Segment>& segs, bool frozen) {
+    std::vector<uint8_t> o;
+    put_v(o, segs.size());
+    for (auto& g : segs) {
+        put_v(o, g.nblocks); put_v(o, g.prior_bytes); put_v(o, g.raw_bytes);
+        if (frozen) { put_v(o, g.chain_bytes); put_v(o, g.recpri_bytes); }
+    }
+    return o;
+}
+bool unpack_segment_index(const std::vector<uint8_t>& bytes, std::vector<Segment>& segs, bool frozen) {
+    size_t p = 0; uint64_t n;
+    if (!get_v(bytes, p, n) || n == 0 || n > bytes.size() / 3) return false;        // (a segment takes three bytes or more)
+    segs.assign((size_t)n, Segment{0, 0, 0, 0, 0});
+    for (auto& g : segs) {
+        if (!get_v(bytes, p, g.nblocks) || !get_v(bytes, p, g.prior_bytes) || !get_v(bytes, p, g.raw_bytes)) return false;
+        if (frozen && (!get_v(bytes, p, g.chain_bytes) || !get_v(bytes, p, g.recpri_bytes))) return false;
+    }
+    return true;
+}
+
+void SegmentedIndex::add(const sfq_segment& s) {
+    if (!s.n_blocks) return;
+    const size_t b0 = blocks.size();
+    blocks.insert(blocks.end(), s.blocks, s.blocks + s.n_blocks);
+    for (size_t b = b0; b < blocks.size(); b++) {
+        blocks[b].first_record += records; blocks[b].first_hdr_off += first.size();
+        records += blocks[b].n_records;
+    }
+    auto cat = [](std::vector<uint8_t>& v, const uint8_t* p, uint64_t n) { if (n) v.insert(v.end(), p, p + n); };
+    cat(first, s.first_hdrs, s.first_hdr_bytes);
+    cat(prior, s.qlt_prior, s.qlt_prior_bytes);
+    cat(chains, s.chain_index, s.chain_index_bytes);
+    cat(recpri, s.rec_prior, s.rec_prior_bytes);
+    segs.push_back(Segment{s.n_blocks, s.qlt_prior_bytes, s.raw_bytes, s.chain_index_bytes, s.rec_prior_bytes});
+    raw += s.raw_bytes;
+}
+
+std::vector<std::pair<std::string, std::string>> SegmentedIndex::info(int level, const std::string& orig_name, bool frozen, bool shared_prior) const {
+    Archive a;                                                               // the reference's keys in its order (config.cpp:334-347), then the block format's
+    a.set("whoami", "slimfastq");
+    a.set("version", kBlockVersion);
+    a.set("config.level", level);
+    a.set("orig.filename", orig_name);
+    a.set("orig.size", (long long)raw);
+    a.set("blk.reads", blocks.empty() ? 0ll : (long long)blocks[0].n_records);  // of the first segment (each carries its own in the index)
+    a.set("blk.count", (long long)blocks.size());
+    a.set("num_records", (long long)records);
+    if (segs.size() > 1) a.set("seg.count", (long long)segs.size());
+    if (segs.size() > 1 && shared_prior) a.set("seg.shared_prior", 1);
+    if (frozen) a.set("blk.tables", 1);                                      // frozen tables: chn.idx / rec.pri per segment
+    return a.info;
+}
+
+std::vector<std::pair<std::string, std::vector<uint8_t>>> SegmentedIndex::streams(bool frozen) const {
+    std::vector<std::pair<std::string, std::vector<uint8_t>>> out;
+    out.emplace_back("blk.idx", pack_block_index(blocks));
+    out.emplace_back("blk.hdr", first);
+    if (!prior.empty()) out.emplace_back("qlt.pri", prior);
+    if (!chains.empty()) out.emplace_back("chn.idx", chains);
+    if (!recpri.empty()) out.emplace_back("rec.pri", recpri);
+    if (segs.size() > 1) out.emplace_back("seg.idx", pack_segment_index(segs, frozen));
+    return out;
+}
+
 }  // namespace sfqc

@@ -66,4 +66,34 @@ private:
 std::vector<uint8_t> pack_block_index(const std::vector<sfq_block_info>& blocks);
 bool unpack_block_index(const std::vector<uint8_t>& bytes, std::vector<sfq_block_info>& blocks, int nstreams = SFQ_NSTREAMS);
 
+// The block format's "version" info key.  7: block format, the reference's quirks kept; 8: lossless ("gen.lc", 14 stream sizes per
+// index entry); 9: "chn.idx" may carry flag bits 2-5 (difference-coded lists, segments, Rice-coded base exceptions, the bases' match
+// model): a reader of version 8 did not look at flags it did not know, so what sets them says 9 and is refused there; 10: flag bit 7
+// (bases without a model as two bits each, no coder): a reader of version 9 refuses the flag, so what sets it says 10
+const int kBlockVersion = 10;
+const int kBlockVersionMin = 7;
+
+// "seg.idx": an archive of the block format is a sequence of SEGMENTS, each the result of one library call (one slab of a large
+// input, or one slab of one rank of a multi-GPU job): its blocks, its share of every stream, its own priors and chain index.
+// Frozen tables ("blk.tables=1") list chain_bytes and recpri_bytes too.
+struct Segment { uint64_t nblocks, prior_bytes, raw_bytes, chain_bytes, recpri_bytes; };
+std::vector<uint8_t> pack_segment_index(const std::vector<Segment>& segs, bool frozen);
+bool unpack_segment_index(const std::vector<uint8_t>& bytes, std::vector<Segment>& segs, bool frozen);
+
+// The block format's index, collected one library call at a time: the calls' blocks (first_record / first_hdr_off re-based
+// onto the archive), first headers, "qlt.pri" / "chn.idx" / "rec.pri" blobs and segments.  A call without blocks adds nothing.
+// The payload streams are the caller's: it writes them, in the calls' order, beside the index streams this hands back.
+struct SegmentedIndex {
+    std::vector<sfq_block_info> blocks;
+    std::vector<uint8_t> first, prior, chains, recpri;
+    std::vector<Segment> segs;
+    uint64_t records = 0, raw = 0;
+
+    void add(const sfq_segment& s);                   // reads everything but the payload streams
+    // info keys of the archive, in the order they are written
+    std::vector<std::pair<std::string, std::string>> info(int level, const std::string& orig_name, bool frozen, bool shared_prior) const;
+    // "blk.idx", "blk.hdr", "qlt.pri", "chn.idx", "rec.pri", "seg.idx" (each where the archive has one)
+    std::vector<std::pair<std::string, std::vector<uint8_t>>> streams(bool frozen) const;
+};
+
 }  // namespace sfqc

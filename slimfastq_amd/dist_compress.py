@@ -65,75 +65,6 @@ def shard_bytes(buf, rank: int, world: int):
     return lo, hi
 
 
-def put_v(out: bytearray, v: int):
-    while v >= 0x80:
-        out.append((v & 0x7f) | 0x80)
-        v >>= 7
-    out.append(v)
-
-
-def assemble(parts, level: int, block_reads: int, orig_name: str, frozen=True, shared_prior=False):
-    """parts: per rank, in rank order: dict(streams=[bytes] * NSTREAMS, blocks=BlockInfo array, first=bytes,
-    prior=bytes, chains=bytes, rec_prior=bytes, raw=int, records=int).  With shared_prior only the first part carries
-    the priors.  Returns (info_text, [(name, bytes)])."""
-    L = capi.lib()
-    parts = [p for p in parts if p["records"]]
-    nblocks = sum(len(p["blocks"]) for p in parts)
-    allb = (capi.BlockInfo * nblocks)()
-    k, rec, hoff = 0, 0, 0
-    for p in parts:
-        for b in p["blocks"]:
-            C.memmove(C.byref(allb[k]), C.byref(b), C.sizeof(capi.BlockInfo))
-            allb[k].first_record = rec
-            allb[k].first_hdr_off = hoff
-            rec += b.n_records
-            hoff += b.first_hdr_len
-            k += 1
-    need = L.sfq_pack_block_index(allb, nblocks, None, 0)
-    idx = (C.c_uint8 * need)()
-    L.sfq_pack_block_index(allb, nblocks, idx, need)
-    info = [("whoami", "slimfastq"), ("version", "10"), ("config.level", str(level)), ("orig.filename", orig_name),
-            ("orig.size", str(sum(p["raw"] for p in parts))), ("blk.reads", str(block_reads)), ("blk.count", str(nblocks)),
-            ("num_records", str(rec))]
-    streams = []
-    for s, name in enumerate(capi.STREAM_NAMES):
-        data = b"".join(p["streams"][s] for p in parts)
-        if data:
-            streams.append((name, data))
-    streams.append(("blk.idx", bytes(idx)))
-    streams.append(("blk.hdr", b"".join(p["first"] for p in parts)))
-    for key, name in (("prior", "qlt.pri"), ("chains", "chn.idx"), ("rec_prior", "rec.pri")):
-        data = b"".join(p[key] for p in parts)
-        if data:
-            streams.append((name, data))
-    if frozen:
-        info.append(("blk.tables", "1"))
-    if len(parts) > 1:
-        info.append(("seg.count", str(len(parts))))
-        if shared_prior:
-            info.append(("seg.shared_prior", "1"))
-        si = bytearray()
-        put_v(si, len(parts))
-        for p in parts:
-            put_v(si, len(p["blocks"])); put_v(si, len(p["prior"])); put_v(si, p["raw"])
-            if frozen:
-                put_v(si, len(p["chains"])); put_v(si, len(p["rec_prior"]))
-        streams.append(("seg.idx", bytes(si)))
-    return "".join("%s=%s\n" % kv for kv in info), streams
-
-
-def write_archive(path: str, info_text: str, streams):
-    L = capi.lib()
-    n = len(streams)
-    names = (C.c_char_p * n)(*[s[0].encode() for s in streams])
-    bufs = [np.frombuffer(s[1], np.uint8) if len(s[1]) else np.zeros(1, np.uint8) for s in streams]
-    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    sizes = (C.c_uint64 * n)(*[len(s[1]) for s in streams])
-    rc = L.sfq_archive_write(path.encode(), info_text.encode(), n, names, ptrs, sizes)
-    if rc:
-        raise capi.SfqError(rc, "cannot write " + path)
-
-
 META_WORDS = capi.NSTREAMS + 7        # stream sizes, then: blocks, first, prior, chains, rec_prior bytes, raw bytes, records
 
 
@@ -273,13 +204,9 @@ def main(argv=None):
     else:
         parts = split_parts(part_t.cpu().numpy().tobytes())
     if rank == 0:
-        first = [p for p in parts if p["records"]]
-        info, streams = assemble(parts, args.level, int(first[0]["blocks"][0].n_records) if first else 0, args.fastq,
-                                 frozen=not args.adaptive, shared_prior=shared)
-        write_archive(args.sfq, info, streams)
-        raw = sum(p["raw"] for p in parts)
-        print("%s: %d bytes -> %s: %d bytes of streams, %d segment(s)" % (args.fastq, raw, args.sfq, sum(len(s[1]) for s in streams),
-                                                                          len([p for p in parts if p["records"]])))
+        capi.archive_write_segments(args.sfq, parts, args.level, args.fastq, tables=tables, shared_prior=shared)
+        print("%s: %d bytes -> %s: %d bytes, %d segment(s)" % (args.fastq, sum(p["raw"] for p in parts), args.sfq, os.path.getsize(args.sfq),
+                                                               len([p for p in parts if p["blocks"]])))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -31,6 +31,7 @@ def test_struct_layouts_match_header():
     assert ctypes.sizeof(capi.Params) == 40
     assert ctypes.sizeof(capi.BlockInfo) == 8 + 4 + 4 + 4 + 4 + 4 + 4 + 8 + 8 * 14 + 4 + 4
     assert ctypes.sizeof(capi.Result) == 8 + 4 + 4 + 112 + 112 + 8 + 8 + 4 + 4 + 64 + 32
+    assert ctypes.sizeof(capi.Segment) == 112 + 112 + 8 + 4 + 4 + 4 * (8 + 8) + 8
     assert [capi.lib().sfq_stream_name(i).decode() for i in range(capi.NSTREAMS)] == capi.STREAM_NAMES
 
 

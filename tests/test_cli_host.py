@@ -83,10 +83,10 @@ def test_dist_compress_shards_on_record_boundaries():
         assert p >= pos and (p in starts or p == len(fq))
 
 
-def test_dist_compress_assembles_a_segmented_archive(cli, tmp_path):
-    """The writer rank's part: per-rank results -> one archive with a segment per rank (host only; the streams here
-    are placeholders, the layout is what is checked -- `slimfastq-amd -s` walks it)."""
-    from slimfastq_amd import capi, dist_compress as dc
+def _rank_parts(chains=True):
+    """Three ranks' results of two blocks each (placeholder streams: the layout is what is checked), then a rank with no
+    records, in the exchange form of slimfastq_amd.dist_compress."""
+    from slimfastq_amd import capi
     parts = []
     for r in range(3):
         blocks = (capi.BlockInfo * 2)()
@@ -95,17 +95,28 @@ def test_dist_compress_assembles_a_segmented_archive(cli, tmp_path):
             for s in range(3):
                 blocks[k].size[s] = 4 + s
         streams = [bytes([r]) * (2 * (4 + s)) if s < 3 else b"" for s in range(capi.NSTREAMS)]
-        parts.append(dict(streams=streams, blocks=list(blocks), first=b"hdr_%d" % r * 2, prior=b"P" * (r + 1), chains=b"C" * r, rec_prior=b"",
-                          raw=1000 + r, records=21))
-    parts.append(dict(streams=[b""] * capi.NSTREAMS, blocks=[], first=b"", prior=b"", chains=b"", rec_prior=b"", raw=0, records=0))   # a rank with no records
-    info, streams = dc.assemble(parts, 3, 1024, "x.fq")
+        parts.append(dict(streams=streams, blocks=list(blocks), first=b"hdr_%d" % r * 2, prior=b"P" * (r + 1),
+                          chains=b"C" * r if chains else b"", rec_prior=b"", raw=1000 + r, records=21))
+    parts.append(dict(streams=[b""] * capi.NSTREAMS, blocks=[], first=b"", prior=b"", chains=b"", rec_prior=b"", raw=0, records=0))
+    return parts
+
+
+def test_dist_compress_assembles_a_segmented_archive(cli, tmp_path):
+    """The writer rank's part: per-rank results -> one archive with a segment per rank, through the CLI's own writer
+    (sfq_archive_write_segments; host only -- `slimfastq-amd -s` walks it)."""
+    from slimfastq_amd import capi, dist_compress as dc
     f = tmp_path / "seg.sfq"
-    dc.write_archive(str(f), info, streams)
+    capi.archive_write_segments(str(f), _rank_parts(), 3, "x.fq")
     p = subprocess.run([cli, "-s", "-f", str(f)], capture_output=True)
     text = p.stderr.decode()
     assert p.returncode == 0 and "seg.count" in text and "= 3" in text and "blk.count" in text and "= 6" in text
-    d = dict(streams)
+    a = O.parse(f.read_bytes())
+    assert a.info["seg.count"] == "3" and a.info["blk.count"] == "6" and a.info["num_records"] == "63"
+    d = a.streams
     assert d["qlt.pri"] == b"PPPPPP" and d["chn.idx"] == b"CCC" and len(d["rec"]) == 3 * 8 and d["seg.idx"][0] == 3
+    blocks = (capi.BlockInfo * 2)()
+    for k in range(2):
+        blocks[k].n_records = 10 + k
     # the flat exchange form of one rank's part (no pickle): streams, index parts, int64 trailer
     import numpy as np
     import torch
@@ -117,3 +128,36 @@ def test_dist_compress_assembles_a_segmented_archive(cli, tmp_path):
     assert u["streams"][0] == b"abc" and u["streams"][2] == b"de" and u["first"] == b"first" and u["prior"] == b"prior" and u["chains"] == b"chains"
     assert u["rec_prior"] == b"rp" and u["raw"] == 1234 and u["records"] == 21 and len(u["blocks"]) == 2 and u["blocks"][1].n_records == 11
     assert "num_records      = 63" in text
+
+
+@pytest.mark.parametrize("frozen", [True, False])
+def test_segment_writer_writes_the_block_formats_index(tmp_path, frozen):
+    """sfq_archive_write_segments against hand-computed bytes: the info keys in their one order, the stream order, and
+    "seg.idx" as varints (frozen tables add chain_bytes and recpri_bytes per segment)."""
+    from slimfastq_amd import capi
+    f = tmp_path / "seg.sfq"
+    capi.archive_write_segments(str(f), _rank_parts(chains=frozen), 3, "x.fq", tables=capi.TABLES_FROZEN if frozen else capi.TABLES_ADAPTIVE,
+                                shared_prior=frozen)
+    img = f.read_bytes()
+    a = O.parse(img)
+    keys = [("whoami", "slimfastq"), ("version", "10"), ("config.level", "3"), ("orig.filename", "x.fq"), ("orig.size", "3003"),
+            ("blk.reads", "10"), ("blk.count", "6"), ("num_records", "63"), ("seg.count", "3")]
+    keys += [("seg.shared_prior", "1"), ("blk.tables", "1")] if frozen else []
+    keys += [("comp.size", str(len(img)))]
+    assert [tuple(l.split("=", 1)) for l in a.streams["<info>"].decode().splitlines()] == keys
+    assert a.order == ["<info>", "rec", "gen", "qlt", "blk.idx", "blk.hdr", "qlt.pri"] + (["chn.idx"] if frozen else []) + ["seg.idx"]
+    assert a.streams["rec"] == b"\0" * 8 + b"\1" * 8 + b"\2" * 8 and a.streams["blk.hdr"] == b"hdr_0hdr_0hdr_1hdr_1hdr_2hdr_2"
+    # per segment: blocks, prior bytes, raw bytes (1000 = 0xe8 0x07) [, chain bytes, rec.pri bytes]
+    if frozen:
+        assert util._vints(a.streams["seg.idx"]) == [3, 2, 1, 1000, 0, 0, 2, 2, 1001, 1, 0, 2, 3, 1002, 2, 0]
+        assert a.streams["seg.idx"] == bytes([3, 2, 1, 0xe8, 7, 0, 0, 2, 2, 0xe9, 7, 1, 0, 2, 3, 0xea, 7, 2, 0])
+    else:
+        assert a.streams["seg.idx"] == bytes([3, 2, 1, 0xe8, 7, 2, 2, 0xe9, 7, 2, 3, 0xea, 7])
+    # refused: no segment with blocks (such an archive does not decode), stream bytes that are not what the blocks say
+    with pytest.raises(capi.SfqError) as e:
+        capi.archive_write_segments(str(tmp_path / "none.sfq"), _rank_parts()[3:], 3, "x.fq")
+    assert e.value.code == -1
+    bad = _rank_parts()
+    bad[1]["streams"][0] = bad[1]["streams"][0][:-1]
+    with pytest.raises(capi.SfqError):
+        capi.archive_write_segments(str(tmp_path / "bad.sfq"), bad, 3, "x.fq")

@@ -609,7 +609,6 @@ def test_cli_batch_worker_survives_a_damaged_second_segment(tmp_path):
     running: the worker must answer 'fail' for the job (the stack unwinds through guards that join the thread; an unjoined
     std::thread would call std::terminate) and go on to the next job."""
     import subprocess
-    from slimfastq_amd import dist_compress as dc
     cli = _cli()
     fq = capi.synth_fastq(12000, 150, seed=23)
     src = tmp_path / "big.fq"; src.write_bytes(fq)
@@ -621,10 +620,10 @@ def test_cli_batch_worker_survives_a_damaged_second_segment(tmp_path):
     v[1 + 5 + 4] += 1 << 20                                      # the second segment claims a megabyte more of "rec.pri" than there is
     si = bytearray()
     for x in v:
-        dc.put_v(si, x)
+        util.put_v(si, x)
     info = "".join(l + "\n" for l in a.streams["<info>"].decode("latin1").split("\n") if l and not l.startswith("comp.size="))
     bad = tmp_path / "bad.sfq"
-    dc.write_archive(str(bad), info, [(k, bytes(si) if k == "seg.idx" else d) for k, d in a.streams.items() if k != "<info>"])
+    util.write_archive(str(bad), info, [(k, bytes(si) if k == "seg.idx" else d) for k, d in a.streams.items() if k != "<info>"])
     jobs = "%s\t%s\n%s\t%s\n" % (bad, tmp_path / "bad.out", good, tmp_path / "good.out")
     p = subprocess.run([cli, "-b", "-d", "-O"], input=jobs.encode(), capture_output=True)
     lines = p.stdout.decode().splitlines()

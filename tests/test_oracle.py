@@ -150,7 +150,7 @@ def test_pre5_header_stream_is_what_the_reference_decodes():
     """The oracle's pre-version-5 "rec" encoder (sfqo_rec_encode_pre5) is derived from RecLoad::load_pre5 (recs.cpp:463-510),
     the only statement of that layout the reference still has.  Pin it: an archive that says version=4 and holds that stream
     beside the reference's other streams must decode, with the COMPILED REFERENCE, to the text."""
-    from slimfastq_amd import capi, dist_compress as dc
+    from slimfastq_amd import capi
     import tempfile
     fq = capi.synth_fastq(1200, 100, seed=44)
     starts, lens = util.line_table(fq)
@@ -162,7 +162,7 @@ def test_pre5_header_stream_is_what_the_reference_decodes():
     streams = [(k, rec4 if k == "rec" else v) for k, v in ref.streams.items() if k != "<info>"]
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "v4.sfq")
-        dc.write_archive(path, info, streams)
+        util.write_archive(path, info, streams)
         img = open(path, "rb").read()
     assert O.parse(img).info["version"] == "4"
     assert O.ref_decompress(img) == fq                       # the reference itself, through load_pre5

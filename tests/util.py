@@ -105,6 +105,28 @@ def _vints(blob: bytes):
     return out
 
 
+def put_v(out: bytearray, v: int):
+    """Append v as a LEB128 varint (the block format's integers)."""
+    while v >= 0x80:
+        out.append((v & 0x7f) | 0x80)
+        v >>= 7
+    out.append(v)
+
+
+def write_archive(path: str, info_text: str, streams):
+    """An archive of exactly these info lines and [(name, bytes)] streams (sfq_archive_write): forged archives for the tests."""
+    import ctypes as C
+    from slimfastq_amd import capi
+    n = len(streams)
+    names = (C.c_char_p * n)(*[s[0].encode() for s in streams])
+    bufs = [np.frombuffer(s[1], np.uint8) if len(s[1]) else np.zeros(1, np.uint8) for s in streams]
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    sizes = (C.c_uint64 * n)(*[len(s[1]) for s in streams])
+    rc = capi.lib().sfq_archive_write(path.encode(), info_text.encode(), n, names, ptrs, sizes)
+    if rc:
+        raise capi.SfqError(rc, "cannot write " + path)
+
+
 def unpack_chains(blob: bytes, nblocks=None):
     """"chn.idx" -> dict(chain_reads, flags, qlt, gen [, seg_len, seg_blocks] [, rec_chain_reads, rec, rec_hdr_bytes]); mirrors api.cpp.
     flags bit 2: every list of sizes is stored as zigzag differences to the entry before it; bit 3: the chains are SEGMENTS of one
