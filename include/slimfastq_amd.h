@@ -256,6 +256,28 @@ int sfq_decode_blocks_host(sfq_ctx* ctx, const sfq_params* params, const sfq_blo
                            const uint8_t* h_streams, uint64_t streams_bytes, const uint64_t stream_offset[SFQ_NSTREAMS],
                            uint8_t* h_fastq_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* result);
 
+/* ---- checksums ------------------------------------------------------------------------------------------------------
+ * CRC-32 (IEEE 802.3, reflected, polynomial 0xEDB88320, init and final XOR 0xFFFFFFFF: the value of zlib's crc32) computed
+ * on the device (crc.hip).  The reference has none: its usage() (config.cpp:191-193) asks users to keep an md5sum.
+ * sfq_crc32: the CRC of every range [h_bounds[i], h_bounds[i+1]) of d_data, i < n_ranges, into h_crc[i] (bounds non-decreasing).
+ * The pass reads whole aligned 16-byte units: up to 15 bytes before d_data + h_bounds[0] and after d_data + h_bounds[n_ranges]
+ * are read (never used), within the aligned 16-byte units of the first and last byte -- so never across a page, but possibly
+ * outside the caller's allocation.  The encode and decode passes below read their text the same way. */
+int sfq_crc32(sfq_ctx* ctx, const uint8_t* d_data, const uint64_t* h_bounds, uint32_t n_ranges, uint32_t* h_crc);
+/* zlib's crc32_combine: the CRC of A followed by B from crc(A), crc(B) and the length of B (host only, no GPU). */
+uint32_t sfq_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+/* on != 0: every encode call computes one CRC per block -- block b covers the input from its first record's header line up to
+ * the next block's first record (to the end of the text for the last block) -- and the CRC of its whole text, on a stream of its
+ * own; every decode call computes them of its output.  Default off: no pass, no event, no buffer. */
+int sfq_ctx_set_checksums(sfq_ctx* ctx, int on);
+/* The last call's per-block CRCs (if cap allows) and the CRC of its whole text; returns the number of blocks (0: the call
+ * computed none). */
+int sfq_get_checksums(sfq_ctx* ctx, uint32_t* h_block_crc, uint32_t cap, uint32_t* h_text_crc);
+/* The expected CRCs of the blocks of the NEXT decode call, consumed by it: that call checks its output against them and returns
+ * SFQ_E_CORRUPT on a mismatch (sfq_last_error names the first bad block; the text stays in the output buffer, and
+ * sfq_get_checksums lists what was computed); n must equal its n_blocks, or it returns SFQ_E_ARG. */
+int sfq_set_block_checksums(sfq_ctx* ctx, const uint32_t* h_crc, uint32_t n);
+
 /* ---- the ".sfq" container (host only) ----------------------------------------------------------
  * Replaces FilerSave + the info page (filer.cpp:217-242, config.cpp:334-347) for hosts that assemble an archive
  * themselves: info_text is the info page ("key=value\n" lines), then n_streams named byte streams (names of at most

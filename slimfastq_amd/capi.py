@@ -26,7 +26,8 @@ EXPORTS = [
     "sfq_decode_blocks_host", "sfq_synth_fastq", "sfq_abi_version", "sfq_get_qlt_prior", "sfq_set_qlt_prior",
     "sfq_archive_write", "sfq_pack_block_index", "sfq_ctx_device_memory", "sfq_get_chain_index", "sfq_set_chain_index", "sfq_get_rec_prior", "sfq_set_rec_prior", "sfq_build_priors",
     "sfq_host_alloc", "sfq_host_free", "sfq_count_priors", "sfq_prior_counts_words", "sfq_get_prior_counts", "sfq_set_prior_counts",
-    "sfq_archive_write_segments",
+    "sfq_archive_write_segments", "sfq_crc32", "sfq_crc32_combine", "sfq_ctx_set_checksums", "sfq_get_checksums",
+    "sfq_set_block_checksums",
 ]
 
 
@@ -139,6 +140,13 @@ def lib():
         L.sfq_pack_block_index.argtypes = [C.POINTER(BlockInfo), C.c_uint32, u8p, u64]
         L.sfq_pack_block_index.restype = C.c_int64
         L.sfq_archive_write_segments.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(Segment)]
+        u32p = C.POINTER(C.c_uint32)
+        L.sfq_crc32.argtypes = [vp, u8p, C.POINTER(u64), C.c_uint32, u32p]
+        L.sfq_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, u64]
+        L.sfq_crc32_combine.restype = C.c_uint32
+        L.sfq_ctx_set_checksums.argtypes = [vp, C.c_int]
+        L.sfq_get_checksums.argtypes = [vp, u32p, C.c_uint32, u32p]
+        L.sfq_set_block_checksums.argtypes = [vp, u32p, C.c_uint32]
         _lib = L
     return _lib
 
@@ -182,12 +190,19 @@ def archive_write_segments(path: str, parts, level: int, orig_name: str, tables=
         raise SfqError(rc, "cannot write " + path)
 
 
-class Encoded:
-    """Host copy of one sfq_encode_blocks result."""
+def crc32_combine(crc_a, crc_b, len_b):
+    """zlib's crc32_combine: the CRC-32 of A followed by B from crc(A), crc(B) and len(B) (host only)."""
+    return int(lib().sfq_crc32_combine(crc_a & 0xFFFFFFFF, crc_b & 0xFFFFFFFF, int(len_b)))
 
-    def __init__(self, res, blocks, first_hdrs, data, prior=b"", chains=b"", rec_prior=b""):
+
+class Encoded:
+    """Host copy of one sfq_encode_blocks result.  crcs / text_crc: the CRC-32 of every block's text and of the whole text,
+    where the context had checksums on (else None)."""
+
+    def __init__(self, res, blocks, first_hdrs, data, prior=b"", chains=b"", rec_prior=b"", crcs=None, text_crc=None):
         self.res, self.blocks, self.first_hdrs, self.data, self.prior, self.chains = res, blocks, first_hdrs, data, prior, chains
         self.rec_prior = rec_prior
+        self.crcs, self.text_crc = crcs, text_crc
 
     def clone(self):
         """A deep copy (the tests damage copies)."""
@@ -196,7 +211,8 @@ class Encoded:
         res = Result()
         C.memmove(C.byref(res), C.byref(self.res), C.sizeof(Result))
         data = self.data.copy() if isinstance(self.data, np.ndarray) else bytes(self.data)
-        return Encoded(res, blocks, bytes(self.first_hdrs), data, bytes(self.prior), bytes(self.chains), bytes(self.rec_prior))
+        return Encoded(res, blocks, bytes(self.first_hdrs), data, bytes(self.prior), bytes(self.chains), bytes(self.rec_prior),
+                       None if self.crcs is None else list(self.crcs), self.text_crc)
 
     def stream(self, s, block=None) -> bytes:
         """Bytes of stream s (an id or a name): the whole concatenation, or one block's part."""
@@ -246,6 +262,36 @@ class Context:
     @property
     def handle(self):
         return self._h
+
+    def set_checksums(self, on=True):
+        """Checksums on: every call computes the CRC-32 of each block's text and of the whole text (checksums())."""
+        self._check(lib().sfq_ctx_set_checksums(self._h, 1 if on else 0))
+
+    def checksums(self):
+        """(per-block CRCs, CRC of the whole text) of the last call; ([], 0) where it computed none."""
+        L = lib()
+        text = C.c_uint32()
+        n = L.sfq_get_checksums(self._h, None, 0, C.byref(text))
+        if n < 0:
+            self._check(n)
+        buf = (C.c_uint32 * max(n, 1))()
+        L.sfq_get_checksums(self._h, buf, n, None)
+        return list(buf)[:n], text.value
+
+    def set_block_checksums(self, crcs):
+        """The expected CRCs of the next decode call's blocks (consumed by it)."""
+        arr = (C.c_uint32 * max(len(crcs), 1))(*[c & 0xFFFFFFFF for c in crcs])
+        self._check(lib().sfq_set_block_checksums(self._h, arr, len(crcs)))
+
+    def crc32(self, d_ptr, bounds):
+        """zlib.crc32 of every range [bounds[i], bounds[i+1]) of the device buffer at d_ptr."""
+        n = len(bounds) - 1
+        if n <= 0:
+            return []
+        b = (C.c_uint64 * len(bounds))(*[int(x) for x in bounds])
+        out = (C.c_uint32 * n)()
+        self._check(lib().sfq_crc32(self._h, C.c_void_p(d_ptr), b, n, out))
+        return list(out)
 
     def index(self, n_blocks):
         blocks = (BlockInfo * n_blocks)()
@@ -323,7 +369,10 @@ class Context:
         self._check(L.sfq_encode_blocks_host(self._h, src.ctypes.data_as(C.c_void_p), len(fastq), C.byref(p),
                                              out.ctypes.data_as(C.c_void_p), cap, C.byref(res)))
         blocks = self.index(res.n_blocks)
-        return Encoded(res, blocks, self.first_headers(res.first_hdr_bytes), out[:res.total_bytes].copy(), self.prior(), self.chains(), self.rec_prior())
+        crcs, text_crc = self.checksums()
+        on = len(crcs) == res.n_blocks and res.n_blocks > 0
+        return Encoded(res, blocks, self.first_headers(res.first_hdr_bytes), out[:res.total_bytes].copy(), self.prior(), self.chains(), self.rec_prior(),
+                       crcs if on else None, text_crc if on else None)
 
     def encode_device(self, d_ptr, nbytes, d_out, out_cap, level=3, block_reads=0, gen_bits=0, models=0, kernel=0, qlt_only=False,
                       prior_step=0, tables=0, chain_reads=0, lds_rows=0):
@@ -355,9 +404,11 @@ class Context:
         """Decode an Encoded (or a (blocks, first_hdrs, data, stream_offset) tuple) back to FASTQ text."""
         L = lib()
         prior = chains = rec_prior = b""
+        crcs = None
         if isinstance(enc_or_parts, Encoded):
             blocks, first, data, prior, chains = enc_or_parts.blocks, enc_or_parts.first_hdrs, enc_or_parts.data, enc_or_parts.prior, enc_or_parts.chains
             rec_prior = enc_or_parts.rec_prior
+            crcs = enc_or_parts.crcs
             soff = (C.c_uint64 * NSTREAMS)(*list(enc_or_parts.res.stream_offset))
         else:
             blocks, first, data, so = enc_or_parts[:4]
@@ -374,6 +425,8 @@ class Context:
         data = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8)) if not isinstance(data, np.ndarray) else data
         p = Params(level, 0, 0, 0, kernel, version, 0, 0, 0, lds_rows)
         res = Result()
+        if crcs is not None:
+            self.set_block_checksums(crcs)
         if out_cap is None:
             out_cap = 64 * len(data) + (1 << 20)
         out = np.empty(out_cap, np.uint8)

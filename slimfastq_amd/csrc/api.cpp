@@ -129,6 +129,14 @@ struct sfq_ctx {
     // last encode, host copies
     std::vector<sfq_block_info> index;
     std::vector<u8> first_hdrs;
+    // checksums (crc.hip): nothing of this exists until a caller turns them on or installs expected values
+    bool crc_on = false;
+    hipStream_t st_crc = nullptr;          // an encode's pass runs here, beside the models
+    hipEvent_t crc_ev[2] = {};
+    DevBuf crc_tab, crc_tiles, crc_grps, crc_bounds, crc_out;
+    void* crc_pin = nullptr; size_t crc_pin_cap = 0;
+    std::vector<u32> crcs; u32 text_crc = 0;          // the last call's: per block, whole text
+    std::vector<u32> crc_expect; bool crc_expect_set = false;   // sfq_set_block_checksums, for the next decode
 };
 
 namespace {
@@ -771,6 +779,44 @@ int text_fingerprint(sfq_ctx* ctx, const u8* d_text, u64 nbytes, hipStream_t st,
     return SFQ_OK;
 }
 
+// checksums (crc.hip): the stream, events and tables, made the first time they are wanted
+int crc_ready(sfq_ctx* ctx) {
+    if (!ctx->st_crc) HIPC(hipStreamCreateWithFlags(&ctx->st_crc, hipStreamNonBlocking));
+    for (auto& e : ctx->crc_ev) if (!e) HIPC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (!ctx->crc_tab.p) {
+        std::vector<u32> t(crc_table_words());
+        crc_build_tables(t.data());
+        int rc;
+        if ((rc = reserve(ctx, ctx->crc_tab, t.size() * 4))) return rc;
+        HIPC(hipMemcpy(ctx->crc_tab.p, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+    }
+    return SFQ_OK;
+}
+// room for a pass over [d + lo, d + hi) in n ranges (and the whole span): device scratch and the page-locked words it returns
+int crc_reserve(sfq_ctx* ctx, const u8* d, u64 lo, u64 hi, u32 n) {
+    int rc;
+    if ((rc = crc_ready(ctx))) return rc;
+    const CrcScratch w = crc_scratch_words(lo, hi, d);
+    if ((rc = reserve(ctx, ctx->crc_tiles, (size_t)w.ntiles * 4 + 16))) return rc;
+    if ((rc = reserve(ctx, ctx->crc_grps, (size_t)w.ngroups * 4 + 16))) return rc;
+    if ((rc = reserve(ctx, ctx->crc_bounds, ((size_t)n + 1) * 8))) return rc;
+    if ((rc = reserve(ctx, ctx->crc_out, ((size_t)n + 1) * 4))) return rc;
+    if ((rc = reserve_pinned_buf(ctx, ctx->crc_pin, ctx->crc_pin_cap, ((size_t)n + 1) * 4))) return rc;
+    return SFQ_OK;
+}
+// queue the pass over a call's n blocks (bounds in ctx->crc_bounds) and the copy of the n + 1 values home
+int crc_queue(sfq_ctx* ctx, const u8* d, u64 total, u32 n, hipStream_t st) {
+    launch_crc32(d, (const u64*)ctx->crc_bounds.p, n, 1, 0, total, (u32*)ctx->crc_tiles.p, (u32*)ctx->crc_grps.p, (u32*)ctx->crc_out.p,
+                 (const u32*)ctx->crc_tab.p, st);
+    HIPC(hipMemcpyAsync(ctx->crc_pin, ctx->crc_out.p, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, st));
+    return SFQ_OK;
+}
+void crc_take(sfq_ctx* ctx, u32 n) {
+    const u32* v = (const u32*)ctx->crc_pin;
+    ctx->crcs.assign(v, v + n);
+    ctx->text_crc = v[n];
+}
+
 // pieces of a page-locked buffer, handed out front to back
 struct Bump {
     u8* p; size_t off, cap;
@@ -838,10 +884,14 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
         &ctx->hist, &ctx->rows66, &ctx->prior_w, &ctx->prior_wovf, &ctx->prior_ls, &ctx->prior_lh, &ctx->tickets,
         &ctx->hcnt, &ctx->hfreq, &ctx->rrows, &ctx->rdec, &ctx->rmap, &ctx->rflags, &ctx->rtok, &ctx->ptmp, &ctx->qrows, &ctx->qdec, &ctx->qesc, &ctx->qw, &ctx->csz, &ctx->coff, &ctx->gcnt, &ctx->grows, &ctx->glog, &ctx->gcost, &ctx->gbins, &ctx->gfill, &ctx->gm_T, &ctx->gm_slen, &ctx->gm_boff, &ctx->gm_soff, &ctx->gm_scan, &ctx->gm_stage, &ctx->gm_tok, &ctx->gm_csz, &ctx->gm_idx, &ctx->excf, &ctx->cflags, &ctx->segn, &ctx->segoff, &ctx->segrec, &ctx->pslot, &ctx->plist, &ctx->chn_len, &ctx->chn_off, &ctx->chn_out,
         &ctx->oflags, &ctx->okbytes, &ctx->ofpos, &ctx->okoff, &ctx->ofilt, &ctx->orecmap, &ctx->olist, &ctx->line_off_o, &ctx->ono, &ctx->opiece,
-        &ctx->otxt[0], &ctx->otxt[1], &ctx->otxt[2], &ctx->osize_all, &ctx->oroff_all, &ctx->oroff_k, &ctx->ocnt };
+        &ctx->otxt[0], &ctx->otxt[1], &ctx->otxt[2], &ctx->osize_all, &ctx->oroff_all, &ctx->oroff_k, &ctx->ocnt,
+        &ctx->crc_tab, &ctx->crc_tiles, &ctx->crc_grps, &ctx->crc_bounds, &ctx->crc_out };
     for (DevBuf* b : all) release(*b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->pin2) (void)hipHostFree(ctx->pin2);
+    if (ctx->crc_pin) (void)hipHostFree(ctx->crc_pin);
+    for (auto& e : ctx->crc_ev) if (e) (void)hipEventDestroy(e);
+    if (ctx->st_crc) (void)hipStreamDestroy(ctx->st_crc);
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
     for (auto& s : ctx->st_aux) if (s) (void)hipStreamDestroy(s);
     if (ctx->st) (void)hipStreamDestroy(ctx->st);
@@ -892,6 +942,7 @@ static int encode_impl(sfq_ctx* ctx, const u8* d_fastq, u64 nbytes, const sfq_pa
     if (nbytes == 0) return fail(ctx, SFQ_E_FORMAT, "empty input");
     HIPC(hipSetDevice(ctx->dev));
     Settle settle(ctx);
+    ctx->crcs.clear(); ctx->text_crc = 0;
     const int rc = encode_body(ctx, d_fastq, nbytes, pp, d_out, out_cap, res, force_models, priors_only);
     settle.ok = rc == SFQ_OK;
     if (rc == SFQ_OK && !priors_only) ctx->blobs_from_encode = true;       // (sfq_build_priors leaves installed priors: SFQ_PRIOR_GIVEN reads them)
@@ -1077,6 +1128,17 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     if (g_bits < 2 || g_bits > 26 ) return fail(ctx, SFQ_E_ARG, "gen_bits %d out of range", g_bits);
     if ((rc = reserve(ctx, ctx->blocks, (size_t)nblocks * sizeof(BlockDesc)))) return rc;
     launch_block_prepare(d_fastq, (const u64*)ctx->line_off.p, nrec, block_reads, (BlockDesc*)ctx->blocks.p, nblocks, nbytes, p.level, g_bits, st);
+    // checksums: the CRC of every block's text (format 6: the whole file, oversize records included) on a stream of its own, from
+    // the line index; taken in at the end of the call
+    const bool crc_pass = ctx->crc_on && !priors_only;
+    if (crc_pass) {
+        if ((rc = crc_reserve(ctx, d_fastq_in, 0, nbytes_in, nblocks))) return rc;
+        HIPC(hipEventRecord(ctx->crc_ev[0], st));
+        HIPC(hipStreamWaitEvent(ctx->st_crc, ctx->crc_ev[0], 0));
+        launch_crc_block_bounds((const u64*)ctx->line_off.p, 4ull * block_reads, nblocks, nbytes_in, (u64*)ctx->crc_bounds.p, ctx->st_crc);
+        if ((rc = crc_queue(ctx, d_fastq_in, nbytes_in, nblocks, ctx->st_crc))) return rc;
+        HIPC(hipEventRecord(ctx->crc_ev[1], ctx->st_crc));
+    }
     // (format 6 with oversize records: three more regions behind the block's, for "usr.lrec" / "usr.lgen" / "usr.lqlt")
     const u64 arena_main = (((u64)nbytes * 17 / 2 + (u64)nblocks * 1024 + 4096) + 15) & ~15ull;      // frame.hip k_block_prepare
     const u64 over_bytes = n_over ? nbytes_in - nbytes : 0;
@@ -1730,6 +1792,10 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     } else {                                       // one persistent kernel per model: the phase is the kernel
         res->coder_ms[0] = res->kernel_ms[SFQ_T_QLT]; res->coder_ms[1] = res->kernel_ms[SFQ_T_GEN]; res->coder_ms[2] = res->kernel_ms[SFQ_T_REC];
     }
+    if (crc_pass) {
+        HIPC(hipEventSynchronize(ctx->crc_ev[1]));
+        crc_take(ctx, nblocks);
+    }
     return SFQ_OK;
 }
 
@@ -1861,24 +1927,43 @@ int sfq_set_chain_index(sfq_ctx* ctx, const uint8_t* h_blob, uint64_t n) {
 static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info* h_blocks, uint32_t nblocks,
                        const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
                        const uint8_t* d_streams, const uint64_t stream_offset[SFQ_NSTREAMS],
-                       uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* res);
-int sfq_decode_blocks(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info* h_blocks, uint32_t nblocks,
-                      const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
-                      const uint8_t* d_streams, const uint64_t stream_offset[SFQ_NSTREAMS],
-                      uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* res) {
-    if (!ctx || !pp || !h_blocks || !nblocks || !d_streams || !stream_offset || !d_out || !out_bytes)
+                       uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* res, const u32* expect);
+// The checksums installed with sfq_set_block_checksums belong to the decode call that follows, whatever it returns: both entry
+// points take them before anything else, so that no early return leaves them for the call after.
+struct Expected {
+    std::vector<u32> crc; bool set = false;
+    explicit Expected(sfq_ctx* ctx) { crc.swap(ctx->crc_expect); set = ctx->crc_expect_set; ctx->crc_expect_set = false; }
+};
+static int decode_device(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info* h_blocks, uint32_t nblocks,
+                         const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
+                         const uint8_t* d_streams, const uint64_t stream_offset[SFQ_NSTREAMS],
+                         uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* res, const Expected& ex) {
+    if (!pp || !h_blocks || !nblocks || !d_streams || !stream_offset || !d_out || !out_bytes)
         return fail(ctx, SFQ_E_ARG, "null argument");
     HIPC(hipSetDevice(ctx->dev));
     Settle settle(ctx);
     drop_encode_blobs(ctx);                             // whatever an encode left behind is not this archive's
-    const int rc = decode_body(ctx, pp, h_blocks, nblocks, h_first_hdrs, first_hdr_bytes, d_streams, stream_offset, d_out, out_cap, out_bytes, res);
+    ctx->crcs.clear(); ctx->text_crc = 0;
+    const bool check = ex.set;
+    const std::vector<u32>& expect = ex.crc;
+    if (check && expect.size() != nblocks) return fail(ctx, SFQ_E_ARG, "%zu block checksums installed for a call of %u blocks", expect.size(), nblocks);
+    const int rc = decode_body(ctx, pp, h_blocks, nblocks, h_first_hdrs, first_hdr_bytes, d_streams, stream_offset, d_out, out_cap, out_bytes, res,
+                               check ? expect.data() : nullptr);
     settle.ok = rc == SFQ_OK;
     return rc;
+}
+int sfq_decode_blocks(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info* h_blocks, uint32_t nblocks,
+                      const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
+                      const uint8_t* d_streams, const uint64_t stream_offset[SFQ_NSTREAMS],
+                      uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* res) {
+    if (!ctx) return SFQ_E_ARG;
+    const Expected ex(ctx);
+    return decode_device(ctx, pp, h_blocks, nblocks, h_first_hdrs, first_hdr_bytes, d_streams, stream_offset, d_out, out_cap, out_bytes, res, ex);
 }
 static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info* h_blocks, uint32_t nblocks,
                        const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
                        const uint8_t* d_streams, const uint64_t stream_offset[SFQ_NSTREAMS],
-                       uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* res) {
+                       uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* res, const u32* expect) {
     sfq_params p = *pp;
     HostTimes ht;
     p.level = clamp_level(p.level);
@@ -2496,12 +2581,27 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
     *out_bytes = total;
     if (total > out_cap) return fail(ctx, SFQ_E_OVERFLOW, "decoded text needs %llu bytes, caller gave %llu", (unsigned long long)total, (unsigned long long)out_cap);
     ht.mark("sizes known");
+    const bool crc_pass = ctx->crc_on || expect;
+    if (crc_pass && (rc = crc_reserve(ctx, d_out, 0, total, nblocks))) return rc;
     launch_assemble(da, nrec, d_roff, d_out, st);
     if (n_over) launch_over_place(n_over, (const u64*)ctx->ono.p, (const u64*)ctx->opiece.p, (const u8*)ctx->otxt[0].p, (const u8*)ctx->otxt[1].p, (const u8*)ctx->otxt[2].p,
                                   (const u64*)ctx->oroff_all.p, d_out, st);
     HIPC(hipEventRecord(ctx->ev[6], st));
+    if (crc_pass) {                                        // checksums: the output blocks end where the next block's first record starts
+        launch_crc_block_bounds(d_roff, block_reads, nblocks, total, (u64*)ctx->crc_bounds.p, st);
+        if ((rc = crc_queue(ctx, d_out, total, nblocks, st))) return rc;
+    }
     HIPC(hipStreamSynchronize(st));
     ht.mark("assembled");
+    if (crc_pass) {
+        crc_take(ctx, nblocks);
+        if (expect)
+            for (u32 b = 0; b < nblocks; b++)
+                if (ctx->crcs[b] != expect[b])
+                    return fail(ctx, SFQ_E_CORRUPT, "checksum: block %u (records %llu..%llu) decodes to text of CRC-32 %08x, the archive says %08x",
+                                b, (unsigned long long)((u64)b * block_reads), (unsigned long long)((u64)b * block_reads + h_blocks[b].n_records - 1),
+                                ctx->crcs[b], expect[b]);
+    }
     res->n_records = nrec_file; res->n_blocks = nblocks; res->total_bytes = total;
     res->kernel_ms[SFQ_T_USR] = ev_ms(ctx->ev[0], ctx->ev[1]);
     res->kernel_ms[SFQ_T_QLT] = ev_ms(ctx->ev[2], ctx->ev[3]);
@@ -2516,7 +2616,9 @@ int sfq_decode_blocks_host(sfq_ctx* ctx, const sfq_params* params, const sfq_blo
                            const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
                            const uint8_t* h_streams, uint64_t streams_bytes, const uint64_t stream_offset[SFQ_NSTREAMS],
                            uint8_t* h_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* result) {
-    if (!ctx || !h_streams || !h_out || !h_blocks || !stream_offset) return fail(ctx, SFQ_E_ARG, "null argument");
+    if (!ctx) return SFQ_E_ARG;
+    const Expected ex(ctx);
+    if (!h_streams || !h_out || !h_blocks || !stream_offset) return fail(ctx, SFQ_E_ARG, "null argument");
     HIPC(hipSetDevice(ctx->dev));
     int rc;
     // the index is untrusted: every stream's blocks must lie inside the bytes handed over (the device entry point cannot
@@ -2531,11 +2633,49 @@ int sfq_decode_blocks_host(sfq_ctx* ctx, const sfq_params* params, const sfq_blo
     if ((rc = reserve(ctx, ctx->in_stage, (size_t)streams_bytes + 16))) return rc;
     if ((rc = reserve(ctx, ctx->out_stage, (size_t)out_cap + 16))) return rc;
     HIPC(hipMemcpyAsync(ctx->in_stage.p, h_streams, (size_t)streams_bytes, hipMemcpyHostToDevice, ctx->st));
-    rc = sfq_decode_blocks(ctx, params, h_blocks, n_blocks, h_first_hdrs, first_hdr_bytes, (const u8*)ctx->in_stage.p,
-                           stream_offset, (u8*)ctx->out_stage.p, out_cap, out_bytes, result);
+    rc = decode_device(ctx, params, h_blocks, n_blocks, h_first_hdrs, first_hdr_bytes, (const u8*)ctx->in_stage.p,
+                       stream_offset, (u8*)ctx->out_stage.p, out_cap, out_bytes, result, ex);
     if (rc) return rc;
     HIPC(hipMemcpyAsync(h_out, ctx->out_stage.p, (size_t)*out_bytes, hipMemcpyDeviceToHost, ctx->st));
     HIPC(hipStreamSynchronize(ctx->st));
+    return SFQ_OK;
+}
+
+int sfq_crc32(sfq_ctx* ctx, const uint8_t* d_data, const uint64_t* h_bounds, uint32_t n_ranges, uint32_t* h_crc) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!n_ranges) return SFQ_OK;
+    if (!d_data || !h_bounds || !h_crc) return fail(ctx, SFQ_E_ARG, "null argument");
+    for (u32 i = 0; i < n_ranges; i++)
+        if (h_bounds[i + 1] < h_bounds[i]) return fail(ctx, SFQ_E_ARG, "crc32: bounds[%u] = %llu after bounds[%u] = %llu", i + 1,
+                                                       (unsigned long long)h_bounds[i + 1], i, (unsigned long long)h_bounds[i]);
+    HIPC(hipSetDevice(ctx->dev));
+    Settle settle(ctx);
+    int rc;
+    if ((rc = crc_reserve(ctx, d_data, h_bounds[0], h_bounds[n_ranges], n_ranges))) return rc;
+    HIPC(hipMemcpyAsync(ctx->crc_bounds.p, h_bounds, ((size_t)n_ranges + 1) * 8, hipMemcpyHostToDevice, ctx->st));
+    launch_crc32(d_data, (const u64*)ctx->crc_bounds.p, n_ranges, 0, h_bounds[0], h_bounds[n_ranges], (u32*)ctx->crc_tiles.p, (u32*)ctx->crc_grps.p,
+                 (u32*)ctx->crc_out.p, (const u32*)ctx->crc_tab.p, ctx->st);
+    HIPC(hipMemcpyAsync(h_crc, ctx->crc_out.p, (size_t)n_ranges * 4, hipMemcpyDeviceToHost, ctx->st));
+    HIPC(hipStreamSynchronize(ctx->st));
+    settle.ok = true;
+    return SFQ_OK;
+}
+uint32_t sfq_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) { return crc32_combine_host(crc_a, crc_b, len_b); }
+int sfq_ctx_set_checksums(sfq_ctx* ctx, int on) {
+    if (!ctx) return SFQ_E_ARG;
+    ctx->crc_on = on != 0;
+    return SFQ_OK;
+}
+int sfq_get_checksums(sfq_ctx* ctx, uint32_t* h_block_crc, uint32_t cap, uint32_t* h_text_crc) {
+    if (!ctx) return SFQ_E_ARG;
+    if (h_block_crc && cap >= ctx->crcs.size() && !ctx->crcs.empty()) memcpy(h_block_crc, ctx->crcs.data(), ctx->crcs.size() * 4);
+    if (h_text_crc) *h_text_crc = ctx->text_crc;
+    return (int)ctx->crcs.size();
+}
+int sfq_set_block_checksums(sfq_ctx* ctx, const uint32_t* h_crc, uint32_t n) {
+    if (!ctx || (n && !h_crc)) return SFQ_E_ARG;
+    ctx->crc_expect.assign(h_crc, h_crc + n);
+    ctx->crc_expect_set = true;
     return SFQ_OK;
 }
 

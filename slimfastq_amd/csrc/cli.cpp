@@ -6,6 +6,7 @@
 //   -A        : adaptive tables (every block runs the reference's per-symbol table updates) instead of the default
 //               frozen tables (rows built by counting passes, one chain per GPU lane)
 //   -g dev    : HIP device
+//   -K        : store the CRC-32 of every block's text ("blk.crc") and of the file (info key "crc32"); a decode checks them
 // All model / coder work happens in libslimfastq_amd.so on the GPU; this file parses arguments, reads and
 // writes files and fills the info page.
 #include <sys/stat.h>
@@ -80,6 +81,8 @@ static void usage() {
            "                   default: -F from 64 MiB of text on, -A in blocks of 65536 reads below that (the priors\n"
            "                   frozen tables transmit weigh too much on a small file)\n"
            "-C reads         : frozen tables: records per chain (default: automatic)\n"
+           "-K               : checksums: store the CRC-32 of every block's text and of the whole file (computed on the GPU);\n"
+           "                   decoding checks them and fails on a mismatch (needs the block format: not with -B 0)\n"
            "-S mbytes        : input is compressed in slabs of this many MiB, one archive segment each (default 512 for a\n"
            "                   regular file, read ahead while the GPU codes the slab before; 2048 for a pipe)\n"
            "-t threads       : threads reading a slab (default 6)\n"
@@ -108,6 +111,7 @@ struct Opts {
     bool adaptive = false;                                             // -A
     bool force_frozen = false;                                         // -F
     long chain_reads = 0;                                              // -C
+    bool checksum = false;                                             // -K
 };
 
 // Growable byte buffer that never zero-fills (a std::vector would touch gigabytes just to size them).
@@ -149,7 +153,7 @@ static size_t whole_records(const uint8_t* p, size_t n, uint64_t nl) {
 }
 
 // One finished library call (a segment of raw bytes of text) into the archive's index.
-static void collect(sfq_ctx* ctx, const sfq_result& res, uint64_t raw, sfqc::SegmentedIndex& idx) {
+static void collect(sfq_ctx* ctx, const sfq_result& res, uint64_t raw, sfqc::SegmentedIndex& idx, bool checksum) {
     std::vector<sfq_block_info> blocks(res.n_blocks);
     sfq_get_block_index(ctx, blocks.data(), res.n_blocks);
     std::vector<uint8_t> first((size_t)res.first_hdr_bytes + 1);
@@ -164,7 +168,13 @@ static void collect(sfq_ctx* ctx, const sfq_result& res, uint64_t raw, sfqc::Seg
     g.blocks = blocks.data(); g.n_blocks = res.n_blocks; g.first_hdrs = first.data(); g.first_hdr_bytes = res.first_hdr_bytes;
     g.qlt_prior = pri.data(); g.qlt_prior_bytes = pri.size(); g.chain_index = chn.data(); g.chain_index_bytes = chn.size();
     g.rec_prior = rpr.data(); g.rec_prior_bytes = rpr.size(); g.raw_bytes = raw;
-    idx.add(g);
+    std::vector<uint32_t> crc;
+    uint32_t text_crc = 0;
+    if (checksum) {                                                    // -K: the call's checksums (sfq_ctx_set_checksums in encode_file)
+        crc.resize(res.n_blocks + 1);
+        if (sfq_get_checksums(ctx, crc.data(), res.n_blocks, &text_crc) != (int)res.n_blocks) croak("checksums: the library returned none for this call");
+    }
+    idx.add(g, checksum ? crc.data() : nullptr, text_crc);
 }
 
 static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, const std::string& fil) {
@@ -178,6 +188,7 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         fprintf(stderr, "Can't read file '%s'\n", usr.c_str()); exit(1);
     }
     const bool legacy = o.block_reads == 0;
+    if (sfq_ctx_set_checksums(ctx, o.checksum ? 1 : 0)) croak("%s", sfq_last_error(ctx));
     sfq_params p; memset(&p, 0, sizeof p);
     p.level = o.level; p.block_reads = o.block_reads < 0 ? SFQ_BLOCK_AUTO : (uint32_t)o.block_reads;
     p.prior_step = legacy ? 0 : SFQ_PRIOR_AUTO;                        // warm start needs the block format
@@ -317,7 +328,7 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             }
             if (rc) croak("%s", sfq_last_error(ctx));
             tick("sfq_encode_blocks_host");
-            collect(ctx, res, use, idx);
+            collect(ctx, res, use, idx, o.checksum);
             tick("collect slab");
             writer.join();
             {
@@ -362,7 +373,7 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         const int rc = sfq_encode_blocks_host(ctx, text, use, &p, out.p, bound, &res);
         if (rc) croak("%s", sfq_last_error(ctx));
         tick("sfq_encode_blocks_host");
-        collect(ctx, res, use, idx);
+        collect(ctx, res, use, idx, o.checksum);
         for (int s = 0; s < SFQ_NSTREAMS; s++)
             streams[s].insert(streams[s].end(), out.p + res.stream_offset[s], out.p + res.stream_offset[s] + res.stream_bytes[s]);
         memmove(fq.p, fq.p + use, fq.n - use); fq.n -= use;               // keep the partial record for the next slab
@@ -417,6 +428,7 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     std::vector<sfq_block_info> blocks;
     std::vector<uint8_t> first;
     std::vector<sfqc::Segment> segs;
+    std::vector<uint32_t> crcs;                                        // "blk.crc" (archives written with -K)
     const std::vector<uint8_t>* pri = a.find("qlt.pri");
     const std::vector<uint8_t>* chn = a.find("chn.idx");
     const std::vector<uint8_t>* rpr = a.find("rec.pri");
@@ -434,6 +446,9 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             if (!sfqc::unpack_segment_index(*si, segs, frozen) || segs.size() > blocks.size()) croak("bad segment index");
         } else segs.push_back(sfqc::Segment{blocks.size(), pri ? pri->size() : 0, (uint64_t)a.get_long("orig.size", 0), chn ? chn->size() : 0, rpr ? rpr->size() : 0});
         if (blocks.empty()) croak("bad block index (no blocks)");
+        if (const std::vector<uint8_t>* c = a.find("blk.crc")) {
+            if (!sfqc::unpack_block_checksums(*c, blocks.size(), crcs)) croak("bad block checksums (blk.crc: %zu bytes for %zu blocks)", c->size(), blocks.size());
+        }
     } else {
         sfq_block_info b; memset(&b, 0, sizeof b);
         b.n_records = (uint32_t)a.get_long("num_records");
@@ -467,6 +482,8 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     }
     sfq_params p; memset(&p, 0, sizeof p);
     p.level = level; p.version = version >= kBlockVersionMin ? kInternalVersion : (uint32_t)version;
+    // (a -b worker keeps its context from job to job: a -K encode before this job left the pass on; installed checksums run it)
+    if (sfq_ctx_set_checksums(ctx, 0)) croak("%s", sfq_last_error(ctx));
     // walk the segments: each one's blocks, its slice of every stream (streams are segment-major), its prior
     size_t b0 = 0, pri_off = 0, chn_off = 0, rpr_off = 0;
     uint64_t spos[SFQ_NSTREAMS] = {0};
@@ -524,11 +541,16 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
                 out.touch((size_t)cap);
                 dst = out.p;
             }
+            // (the expected checksums are consumed by the call they are installed for)
+            if (!crcs.empty() && sfq_set_block_checksums(ctx, crcs.data() + b0, (uint32_t)sb.size())) croak("%s", sfq_last_error(ctx));
             rc = sfq_decode_blocks_host(ctx, &p, sb.data(), (uint32_t)sb.size(), first.data() + h0, hbytes,
                                         data.data(), data.size(), soff, dst, cap, &got, &res);
             if (rc != SFQ_E_OVERFLOW || got <= cap) break;
             cap = got;                                                 // the call reports the size it needs
         }
+        if (rc && segs.size() > 1)                                     // (the library numbers the blocks of its call: one segment)
+            croak("segment %zu of %zu (archive blocks %zu..%zu): %s", (size_t)(&g - segs.data()), segs.size(), b0, b0 + (size_t)g.nblocks - 1,
+                  sfq_last_error(ctx));
         if (rc) croak("%s", sfq_last_error(ctx));
         tick("sfq_decode_blocks_host");
         writer.join();
@@ -551,7 +573,7 @@ int main(int argc, char** argv) {
     Opts o;
     bool statistics = false;
     if (argc == 1) usage();
-    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAF1234u:f:l:B:g:S:T:C:t:")) != -1;) {
+    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFK1234u:f:l:B:g:S:T:C:t:")) != -1;) {
         switch (opt) {
         case 'u': g_usr = optarg; break;
         case 'f': fil = optarg; break;
@@ -569,6 +591,7 @@ int main(int argc, char** argv) {
         case 'z': g_timing = true; break;
         case 'A': o.adaptive = true; break;
         case 'F': o.force_frozen = true; break;
+        case 'K': o.checksum = true; break;
         case 'C': o.chain_reads = strtol(optarg, 0, 0); break;
         case 't': o.io_threads = std::min(64, std::max(1, atoi(optarg))); break;
         case 'v': printf("Version %s\nInternal format version=%u (block format %u)\n", kUserVersion, kInternalVersion, kBlockVersion); exit(0);
@@ -578,6 +601,10 @@ int main(int argc, char** argv) {
         }
     }
     o.level = clamp_level(o.level);                                    // clamp at parse time (the reference records the clamped value only)
+    if (o.checksum && o.block_reads == 0) {
+        fprintf(stderr, "slimfastq: -K (checksums) needs the block format: -B 0 writes the reference's own format-6 file, which has no place for them\n");
+        return 1;
+    }
 
     if (g_batch) {
         sfq_ctx* ctx = nullptr;

@@ -347,8 +347,27 @@ bool unpack_segment_index(const std::vector<uint8_t>& bytes, std::vector<Segment
     return true;
 }
 
-void SegmentedIndex::add(const sfq_segment& s) {
+std::vector<uint8_t> pack_block_checksums(const std::vector<uint32_t>& crcs) {
+    std::vector<uint8_t> o(crcs.size() * 4);
+    for (size_t i = 0; i < crcs.size(); i++)
+        for (int k = 0; k < 4; k++) o[4 * i + k] = (uint8_t)(crcs[i] >> (8 * k));
+    return o;
+}
+bool unpack_block_checksums(const std::vector<uint8_t>& bytes, size_t nblocks, std::vector<uint32_t>& crcs) {
+    if (bytes.size() != nblocks * 4) return false;
+    crcs.assign(nblocks, 0);
+    for (size_t i = 0; i < nblocks; i++)
+        for (int k = 0; k < 4; k++) crcs[i] |= (uint32_t)bytes[4 * i + k] << (8 * k);
+    return true;
+}
+
+void SegmentedIndex::add(const sfq_segment& s, const uint32_t* block_crc, uint32_t call_crc) {
     if (!s.n_blocks) return;
+    if (!block_crc) crc_all = false;
+    if (crc_all) {
+        crcs.insert(crcs.end(), block_crc, block_crc + s.n_blocks);
+        text_crc = sfq_crc32_combine(text_crc, call_crc, s.raw_bytes);
+    }
     const size_t b0 = blocks.size();
     blocks.insert(blocks.end(), s.blocks, s.blocks + s.n_blocks);
     for (size_t b = b0; b < blocks.size(); b++) {
@@ -377,6 +396,10 @@ std::vector<std::pair<std::string, std::string>> SegmentedIndex::info(int level,
     if (segs.size() > 1) a.set("seg.count", (long long)segs.size());
     if (segs.size() > 1 && shared_prior) a.set("seg.shared_prior", 1);
     if (frozen) a.set("blk.tables", 1);                                      // frozen tables: chn.idx / rec.pri per segment
+    if (crc_all && !segs.empty()) {                                          // the whole original file's CRC-32
+        char h[16]; snprintf(h, sizeof h, "%08x", text_crc);
+        a.set("crc32", h);
+    }
     return a.info;
 }
 
@@ -388,6 +411,7 @@ std::vector<std::pair<std::string, std::vector<uint8_t>>> SegmentedIndex::stream
     if (!chains.empty()) out.emplace_back("chn.idx", chains);
     if (!recpri.empty()) out.emplace_back("rec.pri", recpri);
     if (segs.size() > 1) out.emplace_back("seg.idx", pack_segment_index(segs, frozen));
+    if (crc_all && !segs.empty()) out.emplace_back("blk.crc", pack_block_checksums(crcs));
     return out;
 }
 

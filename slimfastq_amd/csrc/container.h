@@ -80,6 +80,10 @@ struct Segment { uint64_t nblocks, prior_bytes, raw_bytes, chain_bytes, recpri_b
 std::vector<uint8_t> pack_segment_index(const std::vector<Segment>& segs, bool frozen);
 bool unpack_segment_index(const std::vector<uint8_t>& bytes, std::vector<Segment>& segs, bool frozen);
 
+// "blk.crc": the CRC-32 of every block's text (sfq_get_checksums), one little-endian u32 per block in archive block order
+std::vector<uint8_t> pack_block_checksums(const std::vector<uint32_t>& crcs);
+bool unpack_block_checksums(const std::vector<uint8_t>& bytes, size_t nblocks, std::vector<uint32_t>& crcs);
+
 // The block format's index, collected one library call at a time: the calls' blocks (first_record / first_hdr_off re-based
 // onto the archive), first headers, "qlt.pri" / "chn.idx" / "rec.pri" blobs and segments.  A call without blocks adds nothing.
 // The payload streams are the caller's: it writes them, in the calls' order, beside the index streams this hands back.
@@ -88,11 +92,14 @@ struct SegmentedIndex {
     std::vector<uint8_t> first, prior, chains, recpri;
     std::vector<Segment> segs;
     uint64_t records = 0, raw = 0;
+    // checksums: kept while every call with blocks came with them ("blk.crc" and info key "crc32", the whole text's)
+    std::vector<uint32_t> crcs; uint32_t text_crc = 0; bool crc_all = true;
 
-    void add(const sfq_segment& s);                   // reads everything but the payload streams
+    // reads everything but the payload streams; block_crc / text_crc: the call's checksums (block_crc NULL: it has none)
+    void add(const sfq_segment& s, const uint32_t* block_crc = nullptr, uint32_t text_crc = 0);
     // info keys of the archive, in the order they are written
     std::vector<std::pair<std::string, std::string>> info(int level, const std::string& orig_name, bool frozen, bool shared_prior) const;
-    // "blk.idx", "blk.hdr", "qlt.pri", "chn.idx", "rec.pri", "seg.idx" (each where the archive has one)
+    // "blk.idx", "blk.hdr", "qlt.pri", "chn.idx", "rec.pri", "seg.idx", "blk.crc" (each where the archive has one)
     std::vector<std::pair<std::string, std::vector<uint8_t>>> streams(bool frozen) const;
 };
 

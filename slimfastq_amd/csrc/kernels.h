@@ -239,3 +239,16 @@ void launch_prior_rows(const u32* hist, u32 q_rows, u32* rows66, u32* w_rows, u3
 void launch_prior_list(const u32* rows66, u32 q_rows, u32* slot, u32* list, hipStream_t st);
 void launch_prior_scatter(const u32* ctxs, const u32* rows /* [n][66] */, u32 n, u32* rows66 /* zeroed */, hipStream_t st);
 void launch_prior_spread(const u32* rows66, u32 q_rows, u32* w_rows, u32* w_ovf, u32* l_slots, RowHdr* l_hdr, hipStream_t st);
+
+// CRC-32 of ranges of a device buffer (crc.hip): zlib.crc32 of [d + bounds[i], d + bounds[i+1]) into out[i], i < n_ranges, and with
+// whole != 0 of [d + bounds[0], d + bounds[n_ranges]) into out[n_ranges].  lo / hi = bounds[0] / bounds[n_ranges] (non-decreasing
+// bounds); tile_crc / grp_crc: scratch of crc_scratch_words(lo, hi, d) words; tab: crc_table_words() words from crc_build_tables.
+struct CrcScratch { u64 ntiles = 0, ngroups = 0; };
+CrcScratch crc_scratch_words(u64 lo, u64 hi, const u8* d);
+u32  crc_table_words();
+void crc_build_tables(u32* tab);
+u32  crc32_combine_host(u32 crc_a, u32 crc_b, u64 len_b);
+void launch_crc32(const u8* d, const u64* d_bounds, u32 n_ranges, u32 whole, u64 lo, u64 hi, u32* tile_crc, u32* grp_crc, u32* out,
+                  const u32* tab, hipStream_t st);
+// bounds[0..nblocks] of a call's blocks: 0, offs[b * stride] (0 < b < nblocks), total
+void launch_crc_block_bounds(const u64* offs, u64 stride, u32 nblocks, u64 total, u64* bounds, hipStream_t st);
