@@ -84,11 +84,11 @@ typedef struct sfq_params {
                               slow, the cross-check of the default kernels; adaptive tables); 2 = the default kernels, but
                               with frozen tables the base exceptions (gen.Ns / gen.Nn / gen.lc) keep the reference's own
                               coding -- XFile streams through adaptive PowerRanger rows, what archives written before
-                              round 4 hold -- instead of Rice-coded gap lists ("chn.idx" flag bit 4), and the
+                              round 4 hold -- instead of Rice-coded gap lists ("chn.idx" flag CHN_EXC_RICE -- csrc/kernels.h ChnFlag --), and the
                               BASES keep round 4's coding: generation tables of Base2 rows where they pay, the initial row's 3 of 12
-                              a base where they do not -- instead of the generation match model ("chn.idx" flag bit 5: a chain
+                              a base where they do not -- instead of the generation match model ("chn.idx" flag CHN_GEN_MATCH: a chain
                               follows a pointer into the earlier generations' bases, gm.hip) and, where they have nothing to learn, two bits a
-                              base without a coder (bit 7, block format 10)   */
+                              base without a coder (CHN_FLAT_RAW, block format 10)   */
     uint32_t version;      /* decode only: archive "version" info key (config.cpp:373); 0 = current (6).
                               Versions < 5 take RecLoad::load_pre5 (recs.cpp:400-401)                      */
     uint32_t prior_step;   /* encode, block mode only: 0 = cold blocks (each block == the reference run on that block);
@@ -101,7 +101,7 @@ typedef struct sfq_params {
                               is coded -- qualities from the transmitted prior, bases from the counts of the earlier
                               generations of the same call (round 5: read as such -- the match model, DESIGN.md 4.3 --, not
                               counted into a table) -- one chain per LANE                              */
-    uint32_t chain_reads;  /* frozen tables: records per chain; 0 = automatic (about 205 000 chains a call, of 4 KiB of text or more; long
+    uint32_t chain_reads;  /* frozen tables: records per chain; 0 = automatic (about 262 144 chains a call -- csrc/api.cpp SFQ_CHAINS_WANT --, of 4 KiB of text or more; long
                               reads -- fewer than 204 800 records, each a chain's worth or more -- are cut into SEGMENTS of one record);
                               SFQ_CHAIN_SEGMENT(n): chains of (at most) n quality symbols / bases of ONE record                     */
     uint32_t lds_rows;     /* frozen tables: quality rows staged in LDS by every workgroup of the quality chains.  Encode: the N most used

@@ -78,14 +78,53 @@ struct HostWorker {
         if (th.joinable()) th.join();
     }
 };
+// The events of a call, by name: indices into sfq_ctx::ev.  An encode and a decode never overlap on a context, so the two
+// directions share the array.  Every record and every wait of a call names its event here.
+enum {                     // ---- encode
+    EE_BEGIN,              // the call starts (the context's stream)
+    EE_HEAD_END,           // the head of the call is queued -- framing, the priors, the dense quality rows: SFQ_T_FRAME ends here (recorded
+                           // again whenever the head grows); the adaptive kernels' streams fork behind it
+    EE_M0_BEGIN, EE_M0_END, EE_M1_BEGIN, EE_M1_END, EE_M2_BEGIN, EE_M2_END, EE_M3_BEGIN, EE_M3_END,
+                           // the phase of model stream m (mst[m] in encode_body): ev_model_begin(ctx, m) / ev_model_end(ctx, m)
+    EE_PACK_BEGIN, EE_PACK_END,                    // SFQ_T_PACK
+    EE_FRAME_K_BEGIN,      // in front of the framing kernel (its end: EE_FRAME_K_END)
+    EE_TEXT_FORK,          // frozen tables: behind the quality sample's histogram; everything that reads only the text forks here
+    EE_QLT_CODE_BEGIN, EE_QLT_CODE_END,            // frozen tables: the chain coders alone, for sfq_result.coder_ms
+    EE_GEN_CODE_BEGIN, EE_GEN_CODE_END,
+    EE_REC_CODE_BEGIN,     // (also: the header prior's passes are through; the quality chains of short records wait for it)
+    EE_NEVER_READ,         // recorded where EE_REC_CODE_END has been recorded already, inside the header coder; nothing waits for it or reads it
+    EE_QLT_LIST_HOME,      // the quality prior's listed rows are in page-locked memory (qlt_prior_blob_now waits)
+    EE_QLT_ROWS_BUILT,     // the quality prior's rows stand; the listing forks to a stream of its own
+    EE_LINES_INDEXED,      // the line index stands; the per-record checks fork to their stream
+    EE_FRAME_K_END,
+    EE_REC_FREQS_HOME,     // the header prior's frequencies are in page-locked memory (rec_prior_copy_back records, rec_prior_blob_now waits)
+    EE_REC_CODE_END,       // behind the headers' token step (chains.hip launch_rec_encode_c records it), or behind the general kernel
+    EE_COUNT
+};
+enum {                     // ---- decode
+    ED_BEGIN,
+    ED_HEAD_END,           // the usr streams are decoded, the line lengths scanned: SFQ_T_USR
+    ED_FORK,               // the base and header decoders' streams fork from the context's
+    ED_QLT_END,
+    ED_GEN_END,            // the base decoder's stream joins
+    ED_REC_END,            // every decoder is through; the layout of the records starts
+    ED_END,
+    ED_GEN_BEGIN,
+    ED_OVER_FORK,          // format 6's oversize records: their base and quality lines fork to a stream of their own ...
+    ED_OVER_LINES_END,     // ... and join before the records are laid out
+    ED_LISTS_COPIED,       // the base and header chains' lists of "chn.idx" are on the device (queued on the base decoder's stream, the headers' waits)
+    ED_COUNT
+};
+enum { EV_COUNT = EE_COUNT > ED_COUNT ? (int)EE_COUNT : (int)ED_COUNT };
+enum { CRC_EV_FORK, CRC_EV_DONE, CRC_EV_COUNT };      // sfq_ctx::crc_ev: the checksum stream forks from the context's; its pass is through
 struct sfq_ctx {
     int dev = 0;
     HostWorker worker;
     hipStream_t st = nullptr;
     hipStream_t st_aux[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev[28] = {};
+    hipEvent_t ev[EV_COUNT] = {};
     bool rec_copy_pending = false;     // the header prior's frequencies are still to be copied to the host (rec_prior_copy_back)
-    bool rec_blob_pending = false;     // "rec.pri" is still to be packed from the frequencies behind ev[24]
+    bool rec_blob_pending = false;     // "rec.pri" is still to be packed from the frequencies behind EE_REC_FREQS_HOME
     std::string err;
     u64 table_budget = 0;
     u64 dev_total = 0;
@@ -93,7 +132,7 @@ struct sfq_ctx {
     u32 epoch_base = 0;
     Tables tab;
     // scratch (grow-only)
-    DevBuf chunk_counts, chunk_base, scan_tmp, line_off, status, blocks, arena, blk_stream_off, stream_total,
+    DevBuf chunk_base, scan_tmp, line_off, status, blocks, arena, blk_stream_off, stream_total,
            lens, blob_off, blob, in_stage, out_stage;
     // decode scratch
     DevBuf slen, qlen, pfg, pfq, soff, qoff, seq_stage, qual_stage, hdr_stage, hlen, hoff, hso, hsc, rsize, roff, d_first;
@@ -132,7 +171,7 @@ struct sfq_ctx {
     // checksums (crc.hip): nothing of this exists until a caller turns them on or installs expected values
     bool crc_on = false;
     hipStream_t st_crc = nullptr;          // an encode's pass runs here, beside the models
-    hipEvent_t crc_ev[2] = {};
+    hipEvent_t crc_ev[CRC_EV_COUNT] = {};
     DevBuf crc_tab, crc_tiles, crc_grps, crc_bounds, crc_out;
     void* crc_pin = nullptr; size_t crc_pin_cap = 0;
     std::vector<u32> crcs; u32 text_crc = 0;          // the last call's: per block, whole text
@@ -531,7 +570,7 @@ int rec_prior_begin(sfq_ctx* ctx, const ModelArgs& a, u64 nrec, bool given, bool
 // "qlt.pri" from the listed rows in page-locked memory (h: the list's head; the rows behind the first PRIOR_LIST_EAGER are
 // fetched here, if there are any)
 int qlt_prior_blob_now(sfq_ctx* ctx, u32* h, u32 q_rows, hipStream_t st) {
-    HIPC(hipEventSynchronize(ctx->ev[20]));
+    HIPC(hipEventSynchronize(ctx->ev[EE_QLT_LIST_HOME]));
     const u32 n = h[0];
     if (n > q_rows) return fail(ctx, SFQ_E_HIP, "quality prior: %u rows listed of %u", n, q_rows);
     if (n > PRIOR_LIST_EAGER) {
@@ -545,7 +584,7 @@ int qlt_prior_blob_now(sfq_ctx* ctx, u32* h, u32 q_rows, hipStream_t st) {
 int rec_prior_blob_now(sfq_ctx* ctx) {
     if (!ctx->rec_blob_pending) return SFQ_OK;
     ctx->rec_blob_pending = false;
-    HIPC(hipEventSynchronize(ctx->ev[24]));
+    HIPC(hipEventSynchronize(ctx->ev[EE_REC_FREQS_HOME]));
     ctx->rec_prior_blob = pack_rec_prior_f((const u32*)((const u8*)ctx->pin + PIN_REC_OFF));
     return SFQ_OK;
 }
@@ -575,7 +614,7 @@ int rec_prior_copy_back(sfq_ctx* ctx, hipStream_t st) {
     if (!ctx->rec_copy_pending) return SFQ_OK;
     ctx->rec_copy_pending = false;
     HIPC(hipMemcpyAsync((u8*)ctx->pin + PIN_REC_OFF, ctx->hfreq.p, (size_t)PR_REC_ROWS * 256 * 4, hipMemcpyDeviceToHost, st));
-    HIPC(hipEventRecord(ctx->ev[24], st));
+    HIPC(hipEventRecord(ctx->ev[EE_REC_FREQS_HOME], st));
     ctx->rec_blob_pending = true;
     return SFQ_OK;
 }
@@ -684,6 +723,10 @@ u32 gm_table_bits(u64 nbytes) {          // an entry per eight bases of the call
 #ifndef GM_CHAIN_WANT
 #define GM_CHAIN_WANT 819200ull       /* base chains a call under the match model aims at ... */
 #define GM_CHAIN_FLOOR 2048ull        /* ... of this much text or more each */
+#endif
+#ifndef ADAPT_GEN_PCT
+#define ADAPT_GEN_PCT 33              /* adaptive tables, all three models on: the share of the chip's wave slots the base kernel keeps to ... */
+#define ADAPT_QLT_PCT 33              /* ... and the quality kernel's */
 #endif
 struct GmPlan { u32 ngen = 0; u32 bound[GEN_MAX_GENERATIONS + 1]; u32 tb = 0; u64 cap = 0; u64 r2 = 0; ChainArgs cg; ChainGeoArgs ggeo; u32* gcsz = nullptr; };
 // the stage of records [0, n): line lengths, their scan, the places, the letters
@@ -823,6 +866,9 @@ struct Bump {
     template <typename T> T* take(size_t n) { off = (off + 15) & ~(size_t)15; T* r = reinterpret_cast<T*>(p + off); off += n * sizeof(T); return off <= cap ? r : nullptr; }
 };
 float ev_ms(hipEvent_t a, hipEvent_t b) { float ms = 0; (void)hipEventElapsedTime(&ms, a, b); return ms; }
+// an encode's model stream m (encode_body mst[m]): the events around its phase
+hipEvent_t ev_model_begin(const sfq_ctx* ctx, int m) { const int i = EE_M0_BEGIN + 2 * m; return ctx->ev[i]; }
+hipEvent_t ev_model_end(const sfq_ctx* ctx, int m) { const int i = EE_M0_END + 2 * m; return ctx->ev[i]; }
 
 }  // namespace
 
@@ -855,11 +901,9 @@ int sfq_ctx_create(sfq_ctx** out, int hip_device) {
     if ((prio_hi != prio_lo ? hipStreamCreateWithPriority(&ctx->st, hipStreamNonBlocking, prio_hi) : hipStreamCreateWithFlags(&ctx->st, hipStreamNonBlocking)) != hipSuccess) { delete ctx; return SFQ_E_HIP; }
     // (the runtime maps streams of one priority onto three hardware queues: the framing stream shares one with the base
     //  model's, and two streams that share a queue run one after the other -- keep long kernels off the framing stream)
-    for (int i = 0; i < 3; i++) {
-        const char* px = getenv("SFQ_EXP_PRIO");          /* scratch experiments: a mask of auxiliary streams created at the higher priority (default 1: the headers') */
-        const int pm = px ? atoi(px) : 1;
-        const hipError_t e = (((pm >> i) & 1) && prio_hi != prio_lo) ? hipStreamCreateWithPriority(&ctx->st_aux[i], hipStreamNonBlocking, prio_hi)
-                                                              : hipStreamCreateWithFlags(&ctx->st_aux[i], hipStreamNonBlocking);
+    for (int i = 0; i < 3; i++) {                          // (the first auxiliary stream, the headers', at the higher priority; the others at the default)
+        const hipError_t e = (i == 0 && prio_hi != prio_lo) ? hipStreamCreateWithPriority(&ctx->st_aux[i], hipStreamNonBlocking, prio_hi)
+                                                            : hipStreamCreateWithFlags(&ctx->st_aux[i], hipStreamNonBlocking);
         if (e != hipSuccess) { delete ctx; return SFQ_E_HIP; }
     }
     for (auto& e : ctx->ev) if (hipEventCreate(&e) != hipSuccess) { delete ctx; return SFQ_E_HIP; }
@@ -877,7 +921,7 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
     (void)hipSetDevice(ctx->dev);
     (void)hipStreamSynchronize(ctx->st);
     DevBuf* all[] = { &ctx->tab.q_slots, &ctx->tab.q_hdr, &ctx->tab.p_slots, &ctx->tab.p_hdr, &ctx->tab.g_tab,
-        &ctx->chunk_counts, &ctx->chunk_base, &ctx->scan_tmp, &ctx->line_off, &ctx->status, &ctx->blocks, &ctx->arena,
+        &ctx->chunk_base, &ctx->scan_tmp, &ctx->line_off, &ctx->status, &ctx->blocks, &ctx->arena,
         &ctx->blk_stream_off, &ctx->stream_total, &ctx->lens, &ctx->blob_off, &ctx->blob, &ctx->in_stage, &ctx->out_stage,
         &ctx->slen, &ctx->qlen, &ctx->pfg, &ctx->pfq, &ctx->soff, &ctx->qoff, &ctx->seq_stage, &ctx->qual_stage,
         &ctx->hdr_stage, &ctx->hlen, &ctx->hoff, &ctx->hso, &ctx->hsc, &ctx->rsize, &ctx->roff, &ctx->d_first,
@@ -973,7 +1017,7 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     if (p.prior_step != SFQ_PRIOR_COUNTS) ctx->counts.valid = false;      // this call may sample into hist / hcnt itself
 
     // ---- framing -------------------------------------------------------------------------------
-    HIPC(hipEventRecord(ctx->ev[0], st));
+    HIPC(hipEventRecord(ctx->ev[EE_BEGIN], st));
     if ((rc = reserve(ctx, ctx->status, 256))) return rc;
     // the quality sample's counters (16 MiB) are cleared here, ahead of the framing kernels: behind them the memset sat on
     // the quality model's critical path for a millisecond (it shares the chip with the counting passes by then)
@@ -1010,9 +1054,9 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
             HIPC(hipMemsetAsync(ctx->status.p, 0, 256, st));
             HIPC(hipMemsetAsync(ctx->chunk_base.p, 0, (size_t)tiles * 8, st));
             void* d_fo = (u8*)ctx->status.p + 224;                                   // (status bytes 224..239: nothing else lives there)
-            HIPC(hipEventRecord(ctx->ev[12], st));
+            HIPC(hipEventRecord(ctx->ev[EE_FRAME_K_BEGIN], st));
             launch_frame(d_fastq, nbytes, (u64*)ctx->chunk_base.p, (u64*)ctx->line_off.p, cap, (u32*)ctx->status.p, want_marks ? (u8*)ctx->excf.p : nullptr, ecap, d_fo, st);
-            HIPC(hipEventRecord(ctx->ev[23], st));
+            HIPC(hipEventRecord(ctx->ev[EE_FRAME_K_END], st));
             struct { u64 nlines; u32 tripped, pad; } fo = {0, 0, 0};
             u8 last_byte = 0;
             HIPC(hipMemcpyAsync(&fo, d_fo, 16, hipMemcpyDeviceToHost, st));
@@ -1033,7 +1077,7 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
         // oversize streams
         // (the block format: the per-record checks run on a stream of their own, beside the block descriptors and the quality sample's
         //  histogram)
-        if (vst != st) { HIPC(hipEventRecord(ctx->ev[22], st)); HIPC(hipStreamWaitEvent(vst, ctx->ev[22], 0)); }
+        if (vst != st) { HIPC(hipEventRecord(ctx->ev[EE_LINES_INDEXED], st)); HIPC(hipStreamWaitEvent(vst, ctx->ev[EE_LINES_INDEXED], 0)); }
         launch_validate_lines((const u64*)ctx->line_off.p, nrec, legacy ? 0x3ffffffeu : 0x1ffeu, 0x3ffffffeu, (u32*)ctx->status.p, vst);
         return SFQ_OK;
     };
@@ -1133,11 +1177,11 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     const bool crc_pass = ctx->crc_on && !priors_only;
     if (crc_pass) {
         if ((rc = crc_reserve(ctx, d_fastq_in, 0, nbytes_in, nblocks))) return rc;
-        HIPC(hipEventRecord(ctx->crc_ev[0], st));
-        HIPC(hipStreamWaitEvent(ctx->st_crc, ctx->crc_ev[0], 0));
+        HIPC(hipEventRecord(ctx->crc_ev[CRC_EV_FORK], st));
+        HIPC(hipStreamWaitEvent(ctx->st_crc, ctx->crc_ev[CRC_EV_FORK], 0));
         launch_crc_block_bounds((const u64*)ctx->line_off.p, 4ull * block_reads, nblocks, nbytes_in, (u64*)ctx->crc_bounds.p, ctx->st_crc);
         if ((rc = crc_queue(ctx, d_fastq_in, nbytes_in, nblocks, ctx->st_crc))) return rc;
-        HIPC(hipEventRecord(ctx->crc_ev[1], ctx->st_crc));
+        HIPC(hipEventRecord(ctx->crc_ev[CRC_EV_DONE], ctx->st_crc));
     }
     // (format 6 with oversize records: three more regions behind the block's, for "usr.lrec" / "usr.lgen" / "usr.lqlt")
     const u64 arena_main = (((u64)nbytes * 17 / 2 + (u64)nblocks * 1024 + 4096) + 15) & ~15ull;      // frame.hip k_block_prepare
@@ -1212,7 +1256,7 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
         prior_step = (u32)std::min<u64>((u64)prior_step * std::max<u32>(1u, ctx->sample_scale), 0x7FFFFFFFull);
     // The histogram of the quality sample goes FIRST and alone: its workgroups take 64 KiB of LDS each, and beside the other models'
     // early passes -- thousands of small workgroups that keep every CU's LDS in use -- they wait for room: 0.5 ms alone, 6.7 ms
-    // beside them, and the quality chains wait for it.  Everything else forks behind it (ev[13] below).
+    // beside them, and the quality chains wait for it.  Everything else forks behind it (EE_TEXT_FORK below).
     bool hist_launched = false;
     if (frozen && !given && !counted && prior_step && (models & SFQ_M_QLT)) {
         if ((rc = ensure_prior_buffers(ctx, q_rows))) return rc;
@@ -1222,7 +1266,7 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     }
     u32 h_status2[5] = {0, 0, 0, 0, 0};
     HIPC(hipMemcpyAsync(h_status2, ctx->status.p, 20, hipMemcpyDeviceToHost, vst));
-    HIPC(hipEventRecord(ctx->ev[1], st));
+    HIPC(hipEventRecord(ctx->ev[EE_HEAD_END], st));
     if (vst != st) HIPC(hipStreamSynchronize(vst));
     else HIPC(hipStreamSynchronize(st));
     const u32 h_status = h_status2[0], max_hdr = h_status2[1], max_line = h_status2[2], min_hdr = ~h_status2[4];      // (k_validate_lines keeps the shortest header as a maximum)
@@ -1332,9 +1376,9 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
         // k_write_newlines: the text is in registers there anyway) and runs beside the counting passes, while the chip is
         // mostly idle.  (Round 2 had the quality and base chains mark them -- the pass then ran BEHIND the chains, 2.5 ms at
         // the call's tail; a marking pass of its own over the text was measured too: it costs more than those 2.5 ms.)
-        HIPC(hipEventRecord(ctx->ev[13], st));
+        HIPC(hipEventRecord(ctx->ev[EE_TEXT_FORK], st));
         if (!priors_only) {
-            for (int m = 1; m < 4; m++) { HIPC(hipStreamWaitEvent(mst[m], ctx->ev[13], 0)); HIPC(hipEventRecord(ctx->ev[2 + 2 * m], mst[m])); }
+            for (int m = 1; m < 4; m++) { HIPC(hipStreamWaitEvent(mst[m], ctx->ev[EE_TEXT_FORK], 0)); HIPC(hipEventRecord(ev_model_begin(ctx, m), mst[m])); }
             a.batch0 = 0; a.nbatch = std::min(slots, nblocks_r);
             ca.m = a;
             if (models & SFQ_M_REC) { if ((rc = rec_prior_begin(ctx, a, nrec, given, counted, mst[1], max_hdr))) return rc; }
@@ -1345,7 +1389,7 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
             // (the pass over the exceptions and the framing exceptions are queued behind the chains' launches below: beside the two
             //  counting passes the host waits for they made those take 1.7-1.9 ms instead of 0.3)
         } else if (models & SFQ_M_REC) {                    // sfq_build_priors: the header sample beside the quality sample
-            HIPC(hipStreamWaitEvent(mst[1], ctx->ev[13], 0));
+            HIPC(hipStreamWaitEvent(mst[1], ctx->ev[EE_TEXT_FORK], 0));
             if ((rc = rec_prior_begin(ctx, a, nrec, given, counted, mst[1], max_hdr))) return rc;
         }
     }
@@ -1354,7 +1398,7 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
         if ((rc = ensure_prior_buffers(ctx, q_rows))) return rc;
         if (!hist_cleared) HIPC(hipMemsetAsync(ctx->hist.p, 0, (size_t)q_rows * 64 * 4, st));          // (no sample of its own: LDS staging has nothing to rank by)
         if ((rc = upload_prior(ctx, q_rows, st, !frozen))) return rc;
-        HIPC(hipEventRecord(ctx->ev[1], st));
+        HIPC(hipEventRecord(ctx->ev[EE_HEAD_END], st));
         ctx->prior_on = true;
     } else if (prior_step && (models & SFQ_M_QLT)) {
         if ((rc = ensure_prior_buffers(ctx, q_rows))) return rc;
@@ -1385,12 +1429,12 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
         if ((rc = reserve_pinned(ctx, PIN_BYTES + ((size_t)PRIOR_LIST_HEAD + (size_t)q_rows * PRIOR_LIST_ROW) * 4))) return rc;
         h_rows66 = (u32*)((u8*)ctx->pin + PIN_BYTES);
         // (on a stream of its own: nothing on the device waits for the list)
-        HIPC(hipEventRecord(ctx->ev[21], st));
-        HIPC(hipStreamWaitEvent(mst[2], ctx->ev[21], 0));
+        HIPC(hipEventRecord(ctx->ev[EE_QLT_ROWS_BUILT], st));
+        HIPC(hipStreamWaitEvent(mst[2], ctx->ev[EE_QLT_ROWS_BUILT], 0));
         launch_prior_list((const u32*)ctx->rows66.p, q_rows, (u32*)ctx->pslot.p, (u32*)ctx->plist.p, mst[2]);
         HIPC(hipMemcpyAsync(h_rows66, ctx->plist.p, ((size_t)PRIOR_LIST_HEAD + (size_t)std::min<u32>(q_rows, PRIOR_LIST_EAGER) * PRIOR_LIST_ROW) * 4, hipMemcpyDeviceToHost, mst[2]));
-        HIPC(hipEventRecord(ctx->ev[20], mst[2]));
-        HIPC(hipEventRecord(ctx->ev[1], st));      // the model streams fork after the prior is built
+        HIPC(hipEventRecord(ctx->ev[EE_QLT_LIST_HOME], mst[2]));
+        HIPC(hipEventRecord(ctx->ev[EE_HEAD_END], st));      // the model streams fork after the prior is built
         ctx->prior_on = true;
     }
     // frozen tables: dense quality rows
@@ -1417,7 +1461,7 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
                 launch_hot_rows((const u32*)ctx->hist.p, (const u32*)ctx->rows66.p, (const u32*)ctx->qrows.p, q_rows, want_hot, ctot, img, info, st);
                 ca.q_hot = want_hot; ca.qh_img = img; ca.qh_info = info;
             }
-            HIPC(hipEventRecord(ctx->ev[1], st));
+            HIPC(hipEventRecord(ctx->ev[EE_HEAD_END], st));
         }
     }
     if (!frozen) { if ((rc = setup_tables())) return rc; }
@@ -1434,14 +1478,13 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     }
     u32 gen_on = 0;
     const bool exc_rice = frozen && !exc_classic;
-    bool side_late = false;                            // the exception pass is still running when the packing starts
     if (frozen) {
         // The two host decisions first (the shorter counting pass, the headers', before the base tables' verdict), each followed by
         // its chains; the quality chains LAST: their row gathers keep every CU's vector memory path full, and whatever small pass
         // runs beside them crawls -- with the quality chains ahead of them the base tables' 0.1 ms row kernel took 3.5 ms and the
         // base chains started 8 ms into the call.
         a.batch0 = 0; a.nbatch = std::min(slots, nblocks_r);
-        HIPC(hipEventRecord(ctx->ev[2], st));
+        HIPC(hipEventRecord(ev_model_begin(ctx, 0), st));
         if (models & SFQ_M_REC) {
             if ((rc = rec_prior_finish(ctx, given, mst[1]))) return rc;
             ca.m = a; ca.rrows = (const u32*)ctx->rrows.p; ca.rdec = (const u16*)ctx->rdec.p;
@@ -1450,13 +1493,13 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
             if ((rc = reserve(ctx, ctx->rtok, rec_token_bytes(nrec)))) return rc;
             HIPC(hipMemsetAsync(ctx->rflags.p, 0, (size_t)nsub * 4 * 2, mst[1]));
             ca.csz = (u32*)ctx->csz.p + 2 * (size_t)nchains; ca.rhb = ca.csz + nsub;
-            HIPC(hipEventRecord(ctx->ev[18], mst[1]));
-            if (nbytes / nrec <= 4000) HIPC(hipStreamWaitEvent(st, ctx->ev[18], 0));   // (the quality chains behind the header prior's passes, as when the host waited for those; not where records are long: few headers, long ones, and the chains have better things to do than wait for their sample)
-            launch_rec_encode_c(ca, (u32*)ctx->rflags.p, (u32*)ctx->rflags.p + nsub, (u32*)ctx->rtok.p, (u32*)ctx->rflags.p + 2 * (size_t)nsub, ctx->r_hot_dec, max_hdr, mst[1], min_hdr, min_hdr > 127 ? nullptr : ctx->ev[25]);
-            HIPC(hipEventRecord(ctx->ev[min_hdr > 127 ? 25 : 19], mst[1]));
-            HIPC(hipEventRecord(ctx->ev[3 + 2 * 1], mst[1]));          // (the header chains are through here; the copy below is not part of the model's phase)
+            HIPC(hipEventRecord(ctx->ev[EE_REC_CODE_BEGIN], mst[1]));
+            if (nbytes / nrec <= 4000) HIPC(hipStreamWaitEvent(st, ctx->ev[EE_REC_CODE_BEGIN], 0));   // (the quality chains behind the header prior's passes, as when the host waited for those; not where records are long: few headers, long ones, and the chains have better things to do than wait for their sample)
+            launch_rec_encode_c(ca, (u32*)ctx->rflags.p, (u32*)ctx->rflags.p + nsub, (u32*)ctx->rtok.p, (u32*)ctx->rflags.p + 2 * (size_t)nsub, ctx->r_hot_dec, max_hdr, mst[1], min_hdr, min_hdr > 127 ? nullptr : ctx->ev[EE_REC_CODE_END]);
+            HIPC(hipEventRecord(min_hdr > 127 ? ctx->ev[EE_REC_CODE_END] : ctx->ev[EE_NEVER_READ], mst[1]));
+            HIPC(hipEventRecord(ev_model_end(ctx, 1), mst[1]));          // (the header chains are through here; the copy below is not part of the model's phase)
             if ((rc = rec_prior_copy_back(ctx, mst[1]))) return rc;
-        } else HIPC(hipEventRecord(ctx->ev[3 + 2 * 1], mst[1]));
+        } else HIPC(hipEventRecord(ev_model_end(ctx, 1), mst[1]));
         if (models & SFQ_M_GEN) {
             ca.m = a; ca.csz = (u32*)ctx->csz.p + nchains;
             if (gm) {
@@ -1469,12 +1512,12 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
             // (Round 4 measured a generation's chains started as soon as its rows were there, on a stream of their own beside the counting
             //  passes of the generations behind it: 57.4 ms per 10 M genome-sampled reads against 58.8 -- the passes' atomics and the chains'
             //  row gathers wait for the same thing, random 64-byte sectors of tables larger than the caches, and their times add up.)
-            HIPC(hipEventRecord(ctx->ev[16], mst[3]));
+            HIPC(hipEventRecord(ctx->ev[EE_GEN_CODE_BEGIN], mst[3]));
             if (gm && gen_on) launch_gm_code(gmplan.cg, (const u8*)ctx->gm_tok.p, mst[3]);
             else { ca.flat_quads = (gm && !gen_on && flat_quads_req) ? 1u : 0u; ca.flat_raw = (gm && !gen_on && !flat_quads_req) ? 1u : 0u; launch_gen_encode_c(ca, mst[3], 0, 0, !gen_on); }
-            HIPC(hipEventRecord(ctx->ev[17], mst[3]));
+            HIPC(hipEventRecord(ctx->ev[EE_GEN_CODE_END], mst[3]));
         }
-        HIPC(hipEventRecord(ctx->ev[3 + 2 * 3], mst[3]));
+        HIPC(hipEventRecord(ev_model_end(ctx, 3), mst[3]));
         if (models & SFQ_M_QLT) {
             ca.m = a; ca.csz = (u32*)ctx->csz.p;
             // (round 5, measured and dropped: with the match model on, the quality chains held back until the bases' plan is through -- beside
@@ -1482,9 +1525,9 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
             //  quality chains end at 21.9 instead of 11.8, the call 24.3 -> 25.9 ms: the chip's work is conserved, whoever goes first.
             //  The other way round -- the quality chains queued FIRST, ahead of the two host decisions, in the default call: they take 6.4-8 ms
             //  instead of 9.1, the base and header chains 8 instead of 4.8, the call 12.4-13.8 ms against 12.6-12.8.)
-            HIPC(hipEventRecord(ctx->ev[14], st)); launch_qlt_encode_c(ca, st); HIPC(hipEventRecord(ctx->ev[15], st));
+            HIPC(hipEventRecord(ctx->ev[EE_QLT_CODE_BEGIN], st)); launch_qlt_encode_c(ca, st); HIPC(hipEventRecord(ctx->ev[EE_QLT_CODE_END], st));
         }
-        HIPC(hipEventRecord(ctx->ev[3], st));
+        HIPC(hipEventRecord(ev_model_end(ctx, 0), st));
         // the base exceptions: Rice-coded gap lists (dev_rice.h; the pass itself is models_w.hip k_gen_exc_w); sfq_params.kernel = 2 keeps the reference's own
         // coding of them (adaptive PowerRanger rows, a wave per block: what rounds 2 and 3 wrote)
         if (models & SFQ_M_GEN) {
@@ -1493,19 +1536,18 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
         }
         if (models & SFQ_M_USR)
             for (u32 b0 = 0; b0 < nblocks; b0 += slots) { ModelArgs ua = a; ua.batch0 = b0; ua.nbatch = std::min(slots, nblocks - b0); launch_usr_encode_w(ua, mst[2]); }
-        HIPC(hipEventRecord(ctx->ev[3 + 2 * 2], mst[2]));
-        side_late = false;
-        HIPC(hipStreamWaitEvent(st, ctx->ev[3 + 2 * 1], 0));        // header chains
-        HIPC(hipStreamWaitEvent(st, ctx->ev[3 + 2 * 3], 0));        // base chains
-        if (!side_late) HIPC(hipStreamWaitEvent(st, ctx->ev[3 + 2 * 2], 0));
+        HIPC(hipEventRecord(ev_model_end(ctx, 2), mst[2]));
+        HIPC(hipStreamWaitEvent(st, ev_model_end(ctx, 1), 0));        // header chains
+        HIPC(hipStreamWaitEvent(st, ev_model_end(ctx, 3), 0));        // base chains
+        HIPC(hipStreamWaitEvent(st, ev_model_end(ctx, 2), 0));        // the exception pass, the usr streams
     } else {
     // The lane-per-block reference kernels (kernel = 1, and usr) run in batches of `slots` blocks.
     if ((models & SFQ_M_GEN) && p.kernel == 1)   // first batch's Base2 tables (base2_ranger.hpp:68-71), while the chip is idle
         launch_fill_u32((u32*)ctx->tab.g_tab.p, (u64)std::min(slots, nblocks) << g_bits, 0x03030303u, st);
-    HIPC(hipEventRecord(ctx->ev[1], st));
+    HIPC(hipEventRecord(ctx->ev[EE_HEAD_END], st));
     for (int m = 0; m < 4; m++) {
-        if (m) HIPC(hipStreamWaitEvent(mst[m], ctx->ev[1], 0));
-        HIPC(hipEventRecord(ctx->ev[2 + 2 * m], mst[m]));
+        if (m) HIPC(hipStreamWaitEvent(mst[m], ctx->ev[EE_HEAD_END], 0));
+        HIPC(hipEventRecord(ev_model_begin(ctx, m), mst[m]));
         if (models & order[m]) {
             const bool batched = p.kernel == 1 || order[m] == SFQ_M_USR;
             if (!batched) {
@@ -1517,10 +1559,6 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
                 if ((models & (SFQ_M_QLT | SFQ_M_GEN | SFQ_M_REC)) == (SFQ_M_QLT | SFQ_M_GEN | SFQ_M_REC) &&
                     (order[m] == SFQ_M_QLT || order[m] == SFQ_M_GEN))
                 {
-#ifndef ADAPT_GEN_PCT
-#define ADAPT_GEN_PCT 33
-#define ADAPT_QLT_PCT 33
-#endif
                     const u32 pct = order[m] == SFQ_M_GEN ? ADAPT_GEN_PCT : ADAPT_QLT_PCT;
                     a.nbatch = std::min<u32>(a.nbatch, std::max<u32>(KR, ((u32)((u64)ctx->wave_slots * pct / 100) * KR) & ~(KR - 1)));
                 }
@@ -1549,12 +1587,12 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
             const u32 ocap[3] = { (u32)over_cap, (u32)over_cap, (u32)over_cap };
             launch_over_encode_w(a, d_file, (const u64*)ctx->line_off_o.p, (const u32*)ctx->olist.p, n_over, ooff, ocap, mst[m]);
         }
-        HIPC(hipEventRecord(ctx->ev[3 + 2 * m], mst[m]));
-        if (m) HIPC(hipStreamWaitEvent(st, ctx->ev[3 + 2 * m], 0));
+        HIPC(hipEventRecord(ev_model_end(ctx, m), mst[m]));
+        if (m) HIPC(hipStreamWaitEvent(st, ev_model_end(ctx, m), 0));
     }
     }
     ht.mark("chains queued");
-    HIPC(hipEventRecord(ctx->ev[10], st));
+    HIPC(hipEventRecord(ctx->ev[EE_PACK_BEGIN], st));
 
     // ---- pack ----------------------------------------------------------------------------------
     if ((rc = reserve(ctx, ctx->blk_stream_off, (size_t)nblocks * SFQ_NSTREAMS * 8))) return rc;
@@ -1569,11 +1607,7 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
             launch_chain_block_sizes(ca, ca.rgeo, SFQ_S_REC, rs, rs + nsub, st); chain_streams |= 1u << SFQ_S_REC;
         }
     }
-    // The three chain-coded streams come first in the output (rec, gen, qlt: enum sfq_stream), so their offsets need
-    // nothing of the side streams: with the exception pass still running (side_late) they are packed beside it, and
-    // the side streams -- a few MB -- when it is through.
-    const bool two_halves = side_late && chain_streams == 7u;
-    launch_block_stream_offsets((BlockDesc*)ctx->blocks.p, nblocks, (u64*)ctx->blk_stream_off.p, (u64*)ctx->stream_total.p, 0, two_halves ? 3 : SFQ_NSTREAMS, st);
+    launch_block_stream_offsets((BlockDesc*)ctx->blocks.p, nblocks, (u64*)ctx->blk_stream_off.p, (u64*)ctx->stream_total.p, st);
     // first headers -> blob
     if ((rc = reserve(ctx, ctx->lens, (size_t)nblocks * 4))) return rc;
     if ((rc = reserve(ctx, ctx->blob_off, ((size_t)nblocks + 1) * 8))) return rc;
@@ -1614,65 +1648,45 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     BlockDesc* hb = (BlockDesc*)((u8*)ctx->pin2 + p2_hb);
     u64* hboff = (u64*)((u8*)ctx->pin2 + p2_off);
     u32* h_csz = (u32*)((u8*)ctx->pin2 + p2_csz);
-    bool chn_on_device = false; u32 chn_n = 0; size_t chn_eager = 0;       // "chn.idx": the size lists arrive as bytes ([info 16 B][bytes] where h_csz points)
-    u64 bases[SFQ_NSTREAMS], run = 0;
-    if (two_halves) {
-        if ((rc = pack_prior_now())) return rc;
-        HIPC(hipStreamSynchronize(st));                                 // the chains are through; totals[0..2] are here
-        for (int s = 0; s < 3; s++) { bases[s] = run; run += totals[s]; }
-        if (run > out_cap) return fail(ctx, SFQ_E_OVERFLOW, "output needs more than %llu bytes, caller gave %llu", (unsigned long long)run, (unsigned long long)out_cap);
-        HIPC(hipMemcpyAsync((u64*)ctx->stream_total.p + SFQ_NSTREAMS, bases, 3 * 8, hipMemcpyHostToDevice, st));
-        launch_compact_chains(ca, ca.geo, SFQ_S_QLT, 2, 1, (const u32*)ctx->csz.p, (const u64*)ctx->blk_stream_off.p, (const u64*)ctx->stream_total.p + SFQ_NSTREAMS, d_out, st);
-        launch_compact_chains(ca, ggeo, SFQ_S_GEN, 3, 4, gen_csz, (const u64*)ctx->blk_stream_off.p, (const u64*)ctx->stream_total.p + SFQ_NSTREAMS, d_out, st);
-        launch_compact_chains(ca, ca.rgeo, SFQ_S_REC, 3, 2, (const u32*)ctx->csz.p + 2 * (size_t)nchains, (const u64*)ctx->blk_stream_off.p, (const u64*)ctx->stream_total.p + SFQ_NSTREAMS, d_out, st);
-        HIPC(hipMemcpyAsync(h_csz, d_sizes, n_sizes * 4, hipMemcpyDeviceToHost, st));
-        // the side streams: behind the exception pass and the framing exceptions
-        HIPC(hipStreamWaitEvent(st, ctx->ev[12], 0));
-        HIPC(hipStreamWaitEvent(st, ctx->ev[3 + 2 * 2], 0));
-        launch_block_stream_offsets((BlockDesc*)ctx->blocks.p, nblocks, (u64*)ctx->blk_stream_off.p, (u64*)ctx->stream_total.p, 3, SFQ_NSTREAMS, st);
-        HIPC(hipMemcpyAsync(totals + 3, (u64*)ctx->stream_total.p + 3, (SFQ_NSTREAMS - 3) * 8, hipMemcpyDeviceToHost, st));
-    }
+    // "chn.idx": the size lists arrive as bytes ([info 16 B][bytes] where h_csz points), the first chn_eager of them at once
+    const bool rec_chains = (chain_streams >> SFQ_S_REC) & 1;
+    const u32 chn_n = frozen ? nchains + ngc + (rec_chains ? nsub * 2 : 0u) : 0u;
+    const size_t chn_eager = std::min<size_t>((size_t)chn_n * 5, n_sizes * 4 + 64 - 16);
     // The packing follows the sizes on the device: k_stream_gate places the streams and holds the packing back where a block has
     // failed or the caller's buffer is too small (the host reports that below, from the same numbers) -- no host round trip between
     // the chains and the packing.  Everything the host wants comes back behind it in one go; the first headers too, as far as a
     // guess at their size reaches.
     u32* d_gate = (u32*)((u64*)ctx->stream_total.p + 2 * SFQ_NSTREAMS);
     const u64 blob_guess = std::min<u64>(blob_cap, (u64)nblocks * 256);
-    if (!two_halves) {
-        launch_stream_gate((const BlockDesc*)ctx->blocks.p, nblocks, (const u64*)ctx->stream_total.p, out_cap, (u64*)ctx->stream_total.p + SFQ_NSTREAMS, d_gate, st);
-        launch_compact((const BlockDesc*)ctx->blocks.p, nblocks, (const u8*)ctx->arena.p, (const u64*)ctx->blk_stream_off.p,
-                       (const u64*)ctx->stream_total.p + SFQ_NSTREAMS, d_out, chain_streams, st, d_gate);
-        if (frozen) {
-            if (chain_streams & (1u << SFQ_S_QLT))
-                launch_compact_chains(ca, ca.geo, SFQ_S_QLT, 2, 1, (const u32*)ctx->csz.p, (const u64*)ctx->blk_stream_off.p, (const u64*)ctx->stream_total.p + SFQ_NSTREAMS, d_out, st, d_gate);
-            if (chain_streams & (1u << SFQ_S_GEN))
-                launch_compact_chains(ca, ggeo, SFQ_S_GEN, 3, 4, gen_csz, (const u64*)ctx->blk_stream_off.p, (const u64*)ctx->stream_total.p + SFQ_NSTREAMS, d_out, st, d_gate);
-            if (chain_streams & (1u << SFQ_S_REC))
-                launch_compact_chains(ca, ca.rgeo, SFQ_S_REC, 3, 2, (const u32*)ctx->csz.p + 2 * (size_t)nchains, (const u64*)ctx->blk_stream_off.p, (const u64*)ctx->stream_total.p + SFQ_NSTREAMS, d_out, st, d_gate);
-            // "chn.idx": the size lists come back as the bytes the blob holds (chains.hip launch_chain_index_bytes: made from half a
-            // million sizes on the host they were 1.0 ms of every call's tail), as far as a guess at their number reaches
-            {
-                const bool recl = (chain_streams >> SFQ_S_REC) & 1;
-                chn_n = nchains + ngc + (recl ? nsub * 2 : 0u);
-                const u32 b1 = nchains, b2 = nchains + ngc, b3 = recl ? nchains + ngc + nsub : chn_n;
-                if ((rc = reserve(ctx, ctx->chn_len, (size_t)chn_n * 4 + 16))) return rc;
-                if ((rc = reserve(ctx, ctx->chn_off, ((size_t)chn_n + 4) * 8))) return rc;
-                if ((rc = reserve(ctx, ctx->chn_out, (size_t)chn_n * 5 + 64))) return rc;
-                if ((rc = reserve(ctx, ctx->scan_tmp, ((size_t)chn_n / 1024 + 4) * 8 + 65536))) return rc;
-                u64* d_info = (u64*)ctx->chn_off.p + chn_n + 1;
-                launch_chain_index_bytes(d_sizes, chn_n, b1, b2 > chn_n ? chn_n : b2, b3, (u32*)ctx->chn_len.p, (u64*)ctx->chn_off.p, (u64*)ctx->scan_tmp.p,
-                                         (u8*)ctx->chn_out.p, d_info, st);
-                chn_eager = std::min<size_t>((size_t)chn_n * 5, n_sizes * 4 + 64 - 16);
-                HIPC(hipMemcpyAsync(h_csz, d_info, 16, hipMemcpyDeviceToHost, st));
-                if (chn_eager) HIPC(hipMemcpyAsync((u8*)h_csz + 16, ctx->chn_out.p, chn_eager, hipMemcpyDeviceToHost, st));
-                chn_on_device = true;
-            }
+    launch_stream_gate((const BlockDesc*)ctx->blocks.p, nblocks, (const u64*)ctx->stream_total.p, out_cap, (u64*)ctx->stream_total.p + SFQ_NSTREAMS, d_gate, st);
+    launch_compact((const BlockDesc*)ctx->blocks.p, nblocks, (const u8*)ctx->arena.p, (const u64*)ctx->blk_stream_off.p,
+                   (const u64*)ctx->stream_total.p + SFQ_NSTREAMS, d_out, chain_streams, st, d_gate);
+    if (frozen) {
+        if (chain_streams & (1u << SFQ_S_QLT))
+            launch_compact_chains(ca, ca.geo, SFQ_S_QLT, 2, 1, (const u32*)ctx->csz.p, (const u64*)ctx->blk_stream_off.p, (const u64*)ctx->stream_total.p + SFQ_NSTREAMS, d_out, st, d_gate);
+        if (chain_streams & (1u << SFQ_S_GEN))
+            launch_compact_chains(ca, ggeo, SFQ_S_GEN, 3, 4, gen_csz, (const u64*)ctx->blk_stream_off.p, (const u64*)ctx->stream_total.p + SFQ_NSTREAMS, d_out, st, d_gate);
+        if (chain_streams & (1u << SFQ_S_REC))
+            launch_compact_chains(ca, ca.rgeo, SFQ_S_REC, 3, 2, (const u32*)ctx->csz.p + 2 * (size_t)nchains, (const u64*)ctx->blk_stream_off.p, (const u64*)ctx->stream_total.p + SFQ_NSTREAMS, d_out, st, d_gate);
+        // "chn.idx": the size lists come back as the bytes the blob holds (chains.hip launch_chain_index_bytes: made from half a
+        // million sizes on the host they were 1.0 ms of every call's tail), as far as a guess at their number reaches
+        {
+            const u32 b1 = nchains, b2 = nchains + ngc, b3 = rec_chains ? nchains + ngc + nsub : chn_n;
+            if ((rc = reserve(ctx, ctx->chn_len, (size_t)chn_n * 4 + 16))) return rc;
+            if ((rc = reserve(ctx, ctx->chn_off, ((size_t)chn_n + 4) * 8))) return rc;
+            if ((rc = reserve(ctx, ctx->chn_out, (size_t)chn_n * 5 + 64))) return rc;
+            if ((rc = reserve(ctx, ctx->scan_tmp, ((size_t)chn_n / 1024 + 4) * 8 + 65536))) return rc;
+            u64* d_info = (u64*)ctx->chn_off.p + chn_n + 1;
+            launch_chain_index_bytes(d_sizes, chn_n, b1, b2 > chn_n ? chn_n : b2, b3, (u32*)ctx->chn_len.p, (u64*)ctx->chn_off.p, (u64*)ctx->scan_tmp.p,
+                                     (u8*)ctx->chn_out.p, d_info, st);
+            HIPC(hipMemcpyAsync(h_csz, d_info, 16, hipMemcpyDeviceToHost, st));
+            if (chn_eager) HIPC(hipMemcpyAsync((u8*)h_csz + 16, ctx->chn_out.p, chn_eager, hipMemcpyDeviceToHost, st));
         }
-        HIPC(hipEventRecord(ctx->ev[11], st));
-        if ((rc = pack_prior_now())) return rc;               // (before the copy into pageable memory below: that one returns when the stream has reached it)
-        ctx->first_hdrs.resize((size_t)blob_guess);
-        if (blob_guess) HIPC(hipMemcpyAsync(ctx->first_hdrs.data(), ctx->blob.p, (size_t)blob_guess, hipMemcpyDeviceToHost, st));
     }
+    HIPC(hipEventRecord(ctx->ev[EE_PACK_END], st));
+    if ((rc = pack_prior_now())) return rc;               // (before the copy into pageable memory below: that one returns when the stream has reached it)
+    ctx->first_hdrs.resize((size_t)blob_guess);
+    if (blob_guess) HIPC(hipMemcpyAsync(ctx->first_hdrs.data(), ctx->blob.p, (size_t)blob_guess, hipMemcpyDeviceToHost, st));
     HIPC(hipMemcpyAsync(hb, ctx->blocks.p, (size_t)nblocks * sizeof(BlockDesc), hipMemcpyDeviceToHost, st));
     HIPC(hipMemcpyAsync(hboff, ctx->blob_off.p, ((size_t)nblocks + 1) * 8, hipMemcpyDeviceToHost, st));
     ht.mark("packing queued");
@@ -1680,7 +1694,7 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     ht.mark("priors packed");
     HIPC(hipStreamSynchronize(st));
     ht.mark("device through");
-    run = 0;
+    u64 bases[SFQ_NSTREAMS], run = 0;
     for (int s = 0; s < SFQ_NSTREAMS; s++) { bases[s] = run; run += totals[s]; res->stream_bytes[s] = totals[s]; res->stream_offset[s] = bases[s]; }
     res->total_bytes = run;
     // per-block status first: an overflowed block has a meaningless size
@@ -1692,26 +1706,16 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     ht.mark("  statuses looked at");
     if (run > out_cap) return fail(ctx, SFQ_E_OVERFLOW, "output needs %llu bytes, caller gave %llu", (unsigned long long)run, (unsigned long long)out_cap);
     if (hboff[nblocks] > blob_cap) return fail(ctx, SFQ_E_OVERFLOW, "first-header blob overflow");
-    if (two_halves) {
-        HIPC(hipMemcpyAsync((u64*)ctx->stream_total.p + SFQ_NSTREAMS, bases, sizeof bases, hipMemcpyHostToDevice, st));
-        launch_compact((const BlockDesc*)ctx->blocks.p, nblocks, (const u8*)ctx->arena.p, (const u64*)ctx->blk_stream_off.p,
-                       (const u64*)ctx->stream_total.p + SFQ_NSTREAMS, d_out, chain_streams, st);
-        HIPC(hipEventRecord(ctx->ev[11], st));
+    if (hboff[nblocks] > blob_guess) {                               // (long first headers: the rest of them)
         ctx->first_hdrs.resize((size_t)hboff[nblocks]);
-        if (hboff[nblocks]) HIPC(hipMemcpyAsync(ctx->first_hdrs.data(), ctx->blob.p, (size_t)hboff[nblocks], hipMemcpyDeviceToHost, st));
+        HIPC(hipMemcpyAsync(ctx->first_hdrs.data() + blob_guess, (const u8*)ctx->blob.p + blob_guess, (size_t)(hboff[nblocks] - blob_guess), hipMemcpyDeviceToHost, st));
         HIPC(hipStreamSynchronize(st));
-    } else {
-        if (hboff[nblocks] > blob_guess) {                               // (long first headers: the rest of them)
-            ctx->first_hdrs.resize((size_t)hboff[nblocks]);
-            HIPC(hipMemcpyAsync(ctx->first_hdrs.data() + blob_guess, (const u8*)ctx->blob.p + blob_guess, (size_t)(hboff[nblocks] - blob_guess), hipMemcpyDeviceToHost, st));
-            HIPC(hipStreamSynchronize(st));
-        } else ctx->first_hdrs.resize((size_t)hboff[nblocks]);
-    }
+    } else ctx->first_hdrs.resize((size_t)hboff[nblocks]);
 
     ht.mark("  first headers home");
     ctx->prior_on = false;
     ctx->chain_blob.clear();
-    if (frozen) {            // "chn.idx": chain_reads, flags (bit 0: generation tables of the bases in use), nchains, sizes
+    if (frozen) {            // "chn.idx": chain_reads, flags (kernels.h ChnFlag), nchains, sizes
         // (half a million varints, written through a pointer into room for the longest: pushed byte by byte into the vector they
         //  were 1.0 ms of every call, after the GPU had finished)
         // (written into a scratch vector that keeps its size from call to call -- growing the blob itself zero-fills 2.5 MB every call --
@@ -1721,48 +1725,29 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
         if (o.size() < o_need) o.resize(o_need);
         u8* w = o.data();
         auto put = [&w](u32 v) { while (v >= 0x80) { *w++ = (u8)(v | 0x80); v >>= 7; } *w++ = (u8)v; };
-        // a list of sizes: each as the zigzag difference to the one before it (neighbouring chains hold as many symbols of the same
-        // statistics: a byte a chain instead of two -- at 12 records a chain the index was 0.5 % of the archive)
-        // (half a million sizes: eight at a time where all eight differences take one byte -- nearly always; 0.86 -> 0.3 ms of the call's tail)
-        auto put_list = [&put, &w](const u32* v, size_t n) {
-            u32 prev = 0; size_t i = 0;
-            for (; i + 8 <= n; i += 8) {
-                u32 z[8], any = 0;
-                for (int j = 0; j < 8; j++) { const i32 d = (i32)(v[i + j] - (j ? v[i + j - 1] : prev)); z[j] = ((u32)d << 1) ^ (u32)(d >> 31); any |= z[j]; }
-                if (any < 0x80u) { u64 b8 = 0; for (int j = 0; j < 8; j++) b8 |= (u64)z[j] << (8 * j); memcpy(w, &b8, 8); w += 8; }
-                else for (int j = 0; j < 8; j++) put(z[j]);
-                prev = v[i + 7];
-            }
-            for (; i < n; i++) { const i32 d = (i32)(v[i] - prev); put(((u32)d << 1) ^ (u32)(d >> 31)); prev = v[i]; }
-        };
-        const bool rec_chains = (chain_streams >> SFQ_S_REC) & 1;
-        put(ca.geo.chain_reads); put(gen_on | (rec_chains ? 2u : 0u) | 4u /* sizes as differences */ | (seg_len ? 8u : 0u) | (exc_rice ? 16u : 0u) | ((gm && gen_on) ? 32u : 0u) /* bases: the match model */
-            | ((gm && !gen_on) ? (flat_quads_req ? 64u : 128u) : 0u) /* bases without a model: two bits each, no coder (block format 10; 64 = four a symbol through the coder: format 9's, still read) */);
+        // (the lists of sizes: each size as the zigzag difference to the one before it -- neighbouring chains hold as many symbols of the
+        //  same statistics: a byte a chain instead of two -- written on the device, chains.hip launch_chain_index_bytes: the one writer)
+        put(ca.geo.chain_reads);
+        put((gen_on ? CHN_GEN_ON : 0u) | (rec_chains ? CHN_REC_CHAINS : 0u) | CHN_DELTAS | (seg_len ? CHN_SEGMENTS : 0u) | (exc_rice ? CHN_EXC_RICE : 0u) | ((gm && gen_on) ? CHN_GEN_MATCH : 0u)
+            | ((gm && !gen_on) ? (flat_quads_req ? CHN_FLAT_QUADS : CHN_FLAT_RAW) : 0u));
         if (gm && gen_on) { put(gmplan.tb); put(ggeo.chain_reads); put(ngc); }      // (the index's bits; the base chains' records, their number)
         put(nchains);
         if (seg_len) { put(seg_len); for (u32 b = 0; b < nblocks; b++) put(seg_blk[b]); }      // segments: their length, every block's share of the chains
-        if (chn_on_device) {           // the lists as the device wrote them
-            const u64* info = (const u64*)h_csz;
-            const u8* lb = (const u8*)h_csz + 16;
-            const u64 la = info[0], lall = info[1];
-            if (la > lall || lall > (u64)chn_n * 5) return fail(ctx, SFQ_E_HIP, "chain index: %llu / %llu bytes of lists for %u sizes", (unsigned long long)la, (unsigned long long)lall, chn_n);
-            std::vector<u8> rest;
-            if (lall > chn_eager) {                                      // (sizes that take more bytes than the guess: the rest of them)
-                rest.resize((size_t)lall);
-                HIPC(hipMemcpyAsync(rest.data(), ctx->chn_out.p, (size_t)lall, hipMemcpyDeviceToHost, st));
-                HIPC(hipStreamSynchronize(st));
-                lb = rest.data();
-            }
-            if (o.size() < o_need + (size_t)lall) { const size_t used = (size_t)(w - o.data()); o.resize(o_need + (size_t)lall); w = o.data() + used; }
-            memcpy(w, lb, (size_t)la); w += la;
-            if (rec_chains) { put(ca.rgeo.chain_reads); put(nsub); memcpy(w, lb + la, (size_t)(lall - la)); w += lall - la; }
-        } else {
-        put_list(h_csz, nchains); put_list(h_csz + nchains, ngc);
-        if (rec_chains) {              // header chains: records per chain, their number, stream sizes, header bytes
-            put(ca.rgeo.chain_reads); put(nsub);
-            put_list(h_csz + (size_t)nchains + ngc, nsub); put_list(h_csz + (size_t)nchains + ngc + nsub, nsub);
+        // the lists as the device wrote them
+        const u64* info = (const u64*)h_csz;
+        const u8* lb = (const u8*)h_csz + 16;
+        const u64 la = info[0], lall = info[1];
+        if (la > lall || lall > (u64)chn_n * 5) return fail(ctx, SFQ_E_HIP, "chain index: %llu / %llu bytes of lists for %u sizes", (unsigned long long)la, (unsigned long long)lall, chn_n);
+        std::vector<u8> rest;
+        if (lall > chn_eager) {                                      // (sizes that take more bytes than the guess: the rest of them)
+            rest.resize((size_t)lall);
+            HIPC(hipMemcpyAsync(rest.data(), ctx->chn_out.p, (size_t)lall, hipMemcpyDeviceToHost, st));
+            HIPC(hipStreamSynchronize(st));
+            lb = rest.data();
         }
-        }
+        if (o.size() < o_need + (size_t)lall) { const size_t used = (size_t)(w - o.data()); o.resize(o_need + (size_t)lall); w = o.data() + used; }
+        memcpy(w, lb, (size_t)la); w += la;
+        if (rec_chains) { put(ca.rgeo.chain_reads); put(nsub); memcpy(w, lb + la, (size_t)(lall - la)); w += lall - la; }
         ctx->chain_blob.assign(o.data(), w);
     }
     ht.mark("chain index written");
@@ -1779,21 +1764,21 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
         bi.status = 0; bi.hdr_bytes = d.hdr_bytes;
     }
     res->n_records = nrec_file; res->n_blocks = nblocks; res->first_hdr_bytes = hboff[nblocks];
-    res->kernel_ms[SFQ_T_FRAME] = ev_ms(ctx->ev[0], ctx->ev[1]);
-    for (int m = 0; m < 4; m++) res->kernel_ms[tslot[m]] = ev_ms(ctx->ev[2 + 2 * m], ctx->ev[3 + 2 * m]);     // the models overlap: these do not add up
-    res->kernel_ms[SFQ_T_PACK] = ev_ms(ctx->ev[10], ctx->ev[11]);
-    res->kernel_ms[SFQ_T_TOTAL] = ev_ms(ctx->ev[0], ctx->ev[11]);
-    if (reframe) res->coder_ms[3] = ev_ms(ctx->ev[12], ctx->ev[23]);          // the framing kernel (frame.hip k_frame)
+    res->kernel_ms[SFQ_T_FRAME] = ev_ms(ctx->ev[EE_BEGIN], ctx->ev[EE_HEAD_END]);
+    for (int m = 0; m < 4; m++) res->kernel_ms[tslot[m]] = ev_ms(ev_model_begin(ctx, m), ev_model_end(ctx, m));     // the models overlap: these do not add up
+    res->kernel_ms[SFQ_T_PACK] = ev_ms(ctx->ev[EE_PACK_BEGIN], ctx->ev[EE_PACK_END]);
+    res->kernel_ms[SFQ_T_TOTAL] = ev_ms(ctx->ev[EE_BEGIN], ctx->ev[EE_PACK_END]);
+    if (reframe) res->coder_ms[3] = ev_ms(ctx->ev[EE_FRAME_K_BEGIN], ctx->ev[EE_FRAME_K_END]);          // the framing kernel (frame.hip k_frame)
     ht.mark("block index built");
     if (frozen) {
-        if (models & SFQ_M_QLT) res->coder_ms[0] = ev_ms(ctx->ev[14], ctx->ev[15]);
-        if (models & SFQ_M_GEN) res->coder_ms[1] = ev_ms(ctx->ev[16], ctx->ev[17]);
-        if (models & SFQ_M_REC) res->coder_ms[2] = ev_ms(ctx->ev[18], ctx->ev[25]);      // (the token step; where every header is long, the general kernel)
+        if (models & SFQ_M_QLT) res->coder_ms[0] = ev_ms(ctx->ev[EE_QLT_CODE_BEGIN], ctx->ev[EE_QLT_CODE_END]);
+        if (models & SFQ_M_GEN) res->coder_ms[1] = ev_ms(ctx->ev[EE_GEN_CODE_BEGIN], ctx->ev[EE_GEN_CODE_END]);
+        if (models & SFQ_M_REC) res->coder_ms[2] = ev_ms(ctx->ev[EE_REC_CODE_BEGIN], ctx->ev[EE_REC_CODE_END]);      // (the token step; where every header is long, the general kernel)
     } else {                                       // one persistent kernel per model: the phase is the kernel
         res->coder_ms[0] = res->kernel_ms[SFQ_T_QLT]; res->coder_ms[1] = res->kernel_ms[SFQ_T_GEN]; res->coder_ms[2] = res->kernel_ms[SFQ_T_REC];
     }
     if (crc_pass) {
-        HIPC(hipEventSynchronize(ctx->crc_ev[1]));
+        HIPC(hipEventSynchronize(ctx->crc_ev[CRC_EV_DONE]));
         crc_take(ctx, nblocks);
     }
     return SFQ_OK;
@@ -1977,7 +1962,7 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
     sfq_result local; if (!res) res = &local;
     memset(res, 0, sizeof *res);
     res->abi_version = SFQ_ABI_VERSION;
-    HIPC(hipEventRecord(ctx->ev[0], st));
+    HIPC(hipEventRecord(ctx->ev[ED_BEGIN], st));
 
     // What the host builds for the device -- block descriptors, stream offsets, the chains' sizes and offsets, the header
     // staging slices -- is built in page-locked memory (the encoder's end-of-call scratch): a copy out of pageable memory goes
@@ -2043,14 +2028,15 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
         if (!get_v(cb, cn, cp, v) || v == 0 || v > 0xFFFFFFFFull) return fail(ctx, SFQ_E_CORRUPT, "bad chain index (chn.idx)");
         chain_reads = (u32)v;
         if (!get_v(cb, cn, cp, v)) return fail(ctx, SFQ_E_CORRUPT, "bad chain index (chn.idx)");
-        gen_on = (u32)v & 1u; rec_chains = ((u32)v >> 1) & 1u;
-        const bool deltas = ((u32)v >> 2) & 1u;              // sizes as zigzag differences to the entry before (round 4; version-8 archives of round 3: plain)
-        const bool segs = ((u32)v >> 3) & 1u;                // chains are segments of one record (long reads): their length and the blocks' shares follow
-        exc_rice = ((u32)v >> 4) & 1u;                       // the base exceptions are Rice-coded gap lists (exc.hip; round 4)
-        gm_on = ((u32)v >> 5) & 1u;                          // the bases are coded under the match model (gm.hip; round 5): the index's bits follow
-        flat_quads = ((u32)v >> 6) & 1u;                     // bases without a model are coded four a symbol (round 5)
-        flat_raw = ((u32)v >> 7) & 1u;                       // ... or not coded at all: two bits each, four a byte (round 5b, block format 10)
-        if (v >> 8 || ((flat_quads | flat_raw) && gen_on) || (flat_quads && flat_raw)) return fail(ctx, SFQ_E_CORRUPT, "bad chain index (chn.idx: unknown flags)");
+        const u32 fl = (u32)v;                               // the flags (kernels.h ChnFlag)
+        gen_on = (fl & CHN_GEN_ON) != 0; rec_chains = (fl & CHN_REC_CHAINS) != 0;
+        const bool deltas = (fl & CHN_DELTAS) != 0;          // (round 4; version-8 archives of round 3: plain)
+        const bool segs = (fl & CHN_SEGMENTS) != 0;          // their length and the blocks' shares follow
+        exc_rice = (fl & CHN_EXC_RICE) != 0;
+        gm_on = (fl & CHN_GEN_MATCH) != 0;                   // the index's bits follow
+        flat_quads = (fl & CHN_FLAT_QUADS) != 0;
+        flat_raw = (fl & CHN_FLAT_RAW) != 0;
+        if ((v & ~(u64)CHN_KNOWN) || ((flat_quads | flat_raw) && gen_on) || (flat_quads && flat_raw)) return fail(ctx, SFQ_E_CORRUPT, "bad chain index (chn.idx: unknown flags)");
         if (gm_on) {
             u64 t = 0;
             if (!gen_on || !exc_rice || !get_v(cb, cn, cp, t) || t < 8 || t > 26) return fail(ctx, SFQ_E_CORRUPT, "bad chain index (chn.idx: match model)");
@@ -2222,13 +2208,13 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
         if ((rc = reserve(ctx, ctx->otxt[1], (size_t)out_cap + 16))) return rc;
         if ((rc = reserve(ctx, ctx->otxt[2], (size_t)out_cap + 16))) return rc;
         HIPC(hipMemsetAsync(ctx->opiece.p, 0, (size_t)n_over * 64, st));
-        HIPC(hipEventRecord(ctx->ev[8], st));
+        HIPC(hipEventRecord(ctx->ev[ED_OVER_FORK], st));
         launch_over_decode_w(da.m, s_l[0], (u32)bi.size[SFQ_S_USR_LREC], 0, 1, n_over, nullptr, (u64*)ctx->ono.p, (u64*)ctx->opiece.p, (u8*)ctx->otxt[0].p, h_cnt[1], st);
         // the base and quality lines: a wave each, beside everything else (joined before the records are laid out)
-        HIPC(hipStreamWaitEvent(ctx->st_aux[2], ctx->ev[8], 0));
+        HIPC(hipStreamWaitEvent(ctx->st_aux[2], ctx->ev[ED_OVER_FORK], 0));
         launch_over_decode_w(da.m, s_l[1], (u32)bi.size[SFQ_S_USR_LGEN], 1, 1, n_over, nullptr, nullptr, (u64*)ctx->opiece.p, (u8*)ctx->otxt[1].p, out_cap, ctx->st_aux[2]);
         launch_over_decode_w(da.m, s_l[2], (u32)bi.size[SFQ_S_USR_LQLT], 2, 1, n_over, nullptr, nullptr, (u64*)ctx->opiece.p, (u8*)ctx->otxt[2].p, out_cap, ctx->st_aux[2]);
-        HIPC(hipEventRecord(ctx->ev[9], ctx->st_aux[2]));
+        HIPC(hipEventRecord(ctx->ev[ED_OVER_LINES_END], ctx->st_aux[2]));
         // kept record -> file number
         if ((rc = reserve(ctx, ctx->oflags, (size_t)nrec_file * 4))) return rc;
         if ((rc = reserve(ctx, ctx->ofpos, ((size_t)nrec_file + 1) * 8))) return rc;
@@ -2287,7 +2273,7 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
     }
     HIPC(hipMemcpyAsync(&tot_s, (u64*)ctx->soff.p + nrec, 8, hipMemcpyDeviceToHost, st));
     HIPC(hipMemcpyAsync(&tot_q, (u64*)ctx->qoff.p + nrec, 8, hipMemcpyDeviceToHost, st));
-    HIPC(hipEventRecord(ctx->ev[1], st));
+    HIPC(hipEventRecord(ctx->ev[ED_HEAD_END], st));
     HIPC(hipStreamSynchronize(st));
     // (a damaged usr stream can claim any lengths: what cannot fit the caller's buffer is refused before anything is decoded)
     if (tot_s > out_cap + (u64)spad * nrec || tot_q > out_cap + (u64)qpad * nrec) return fail(ctx, SFQ_E_CORRUPT, "line lengths add up to %llu bases / %llu qualities, the output buffer holds %llu bytes",
@@ -2326,8 +2312,8 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
             HIPC(hipMemcpyAsync((u32*)ctx->csz.p + nchains, h_csz + nchains, (ncs - nchains) * 4, hipMemcpyHostToDevice, sg));
             HIPC(hipMemcpyAsync((u64*)ctx->coff.p + nchains, h_coff + nchains, (ncs - nchains) * 8, hipMemcpyHostToDevice, sg));
         }
-        HIPC(hipEventRecord(ctx->ev[27], sg));
-        HIPC(hipStreamWaitEvent(sr, ctx->ev[27], 0));
+        HIPC(hipEventRecord(ctx->ev[ED_LISTS_COPIED], sg));
+        HIPC(hipStreamWaitEvent(sr, ctx->ev[ED_LISTS_COPIED], 0));
         ht.mark("chain lists read, copied");
         return SFQ_OK;
     };
@@ -2338,9 +2324,9 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
     //    with sixteen free wave slots, the quality decoder (the call's critical path) behind it.
     hipStream_t st_rec = ctx->st_aux[0], st_gen = ctx->st_aux[1];
     auto fork_streams = [&]() -> int {
-        HIPC(hipEventRecord(ctx->ev[2], st));
-        HIPC(hipStreamWaitEvent(ctx->st_aux[0], ctx->ev[2], 0));
-        HIPC(hipStreamWaitEvent(ctx->st_aux[1], ctx->ev[2], 0));
+        HIPC(hipEventRecord(ctx->ev[ED_FORK], st));
+        HIPC(hipStreamWaitEvent(ctx->st_aux[0], ctx->ev[ED_FORK], 0));
+        HIPC(hipStreamWaitEvent(ctx->st_aux[1], ctx->ev[ED_FORK], 0));
         return SFQ_OK;
     };
     if (frozen) {
@@ -2385,14 +2371,9 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
         ca.csz = (u32*)ctx->csz.p; ca.coff = (const u64*)ctx->coff.p;
         if ((rc = fork_streams())) return rc;
         launch_qlt_decode_c(ca, da, st);
-        HIPC(hipEventRecord(ctx->ev[3], st));
-#ifdef SFQ_EXP_QDEC_ALONE          /* scratch experiments only: the quality decoder by itself, timed; the call then fails */
-        HIPC(hipStreamSynchronize(st));
-        fprintf(stderr, "EXP qdec alone: %.3f ms\n", ev_ms(ctx->ev[2], ctx->ev[3]));
-        return fail(ctx, SFQ_E_ARG, "experiment build");
-#endif
+        HIPC(hipEventRecord(ctx->ev[ED_QLT_END], st));
         if ((rc = rest_of_lists(st_gen, st_rec))) return rc;
-        HIPC(hipEventRecord(ctx->ev[7], st_gen));
+        HIPC(hipEventRecord(ctx->ev[ED_GEN_BEGIN], st_gen));
         // bases: generation by generation -- a generation's rows come from the counts of everything decoded before it
         ca.csz = (u32*)ctx->csz.p + nchains; ca.coff = (const u64*)ctx->coff.p + nchains;
         ca.st_buf = da.seq_stage; ca.st_bytes = tot_s; ca.st_off = da.soff; ca.st_len = da.slen;
@@ -2444,8 +2425,8 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
         da.m.batch0 = b0; da.m.nbatch = std::min(slots, nblocks - b0);
         if (wave_dec) launch_qlt_decode_w(da, st); else launch_qlt_decode_l(da, st);
     }
-    HIPC(hipEventRecord(ctx->ev[3], st));
-    HIPC(hipEventRecord(ctx->ev[7], st_gen));
+    HIPC(hipEventRecord(ctx->ev[ED_QLT_END], st));
+    HIPC(hipEventRecord(ctx->ev[ED_GEN_BEGIN], st_gen));
     for (u32 b0 = 0; b0 < nblocks; b0 += slots) {
         da.m.batch0 = b0; da.m.nbatch = std::min(slots, nblocks - b0);
         launch_fill_u32((u32*)ctx->tab.g_tab.p, (u64)da.m.nbatch << g_bits, 0x03030303u, st_gen);
@@ -2454,8 +2435,8 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
         if (wave_dec && g_bits_min >= 6 && g_bits_min == g_bits) launch_gen_decode_w(da, st_gen); else launch_gen_decode_l(da, st_gen);
     }
     }
-    HIPC(hipEventRecord(ctx->ev[4], st_gen));
-    HIPC(hipStreamWaitEvent(st, ctx->ev[4], 0));
+    HIPC(hipEventRecord(ctx->ev[ED_GEN_END], st_gen));
+    HIPC(hipStreamWaitEvent(st, ctx->ev[ED_GEN_END], 0));
 
     // 3. headers; the staging size comes from the index when known, else grows on overflow
     ht.mark("quality + base decoders queued");
@@ -2554,7 +2535,7 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
         HIPC(hipMemcpyAsync(ctx->blocks.p, hb, (size_t)nblocks * sizeof(BlockDesc), hipMemcpyHostToDevice, st));
     }
     ht.mark("decoders through (host waited)");
-    HIPC(hipEventRecord(ctx->ev[5], st));
+    HIPC(hipEventRecord(ctx->ev[ED_REC_END], st));
 
     // 4. lay the records out
     launch_record_sizes(da, nrec, (u32*)ctx->rsize.p, st);
@@ -2564,7 +2545,7 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
         launch_scan_u32((const u32*)ctx->rsize.p, (u64*)ctx->roff.p, nrec, (u64*)ctx->scan_tmp.p, st);
         HIPC(hipMemcpyAsync(&total, (u64*)ctx->roff.p + nrec, 8, hipMemcpyDeviceToHost, st));
     } else {                                               // every record of the file in file order: the kept ones' sizes, the oversize ones' raw lines
-        HIPC(hipStreamWaitEvent(st, ctx->ev[9], 0));
+        HIPC(hipStreamWaitEvent(st, ctx->ev[ED_OVER_LINES_END], 0));
         if ((rc = reserve(ctx, ctx->osize_all, (size_t)nrec_file * 4))) return rc;
         if ((rc = reserve(ctx, ctx->oroff_all, ((size_t)nrec_file + 1) * 8))) return rc;
         if ((rc = reserve(ctx, ctx->oroff_k, (size_t)nrec * 8 + 16))) return rc;
@@ -2586,7 +2567,7 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
     launch_assemble(da, nrec, d_roff, d_out, st);
     if (n_over) launch_over_place(n_over, (const u64*)ctx->ono.p, (const u64*)ctx->opiece.p, (const u8*)ctx->otxt[0].p, (const u8*)ctx->otxt[1].p, (const u8*)ctx->otxt[2].p,
                                   (const u64*)ctx->oroff_all.p, d_out, st);
-    HIPC(hipEventRecord(ctx->ev[6], st));
+    HIPC(hipEventRecord(ctx->ev[ED_END], st));
     if (crc_pass) {                                        // checksums: the output blocks end where the next block's first record starts
         launch_crc_block_bounds(d_roff, block_reads, nblocks, total, (u64*)ctx->crc_bounds.p, st);
         if ((rc = crc_queue(ctx, d_out, total, nblocks, st))) return rc;
@@ -2603,12 +2584,12 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
                                 ctx->crcs[b], expect[b]);
     }
     res->n_records = nrec_file; res->n_blocks = nblocks; res->total_bytes = total;
-    res->kernel_ms[SFQ_T_USR] = ev_ms(ctx->ev[0], ctx->ev[1]);
-    res->kernel_ms[SFQ_T_QLT] = ev_ms(ctx->ev[2], ctx->ev[3]);
-    res->kernel_ms[SFQ_T_GEN] = ev_ms(ctx->ev[7], ctx->ev[4]);
-    res->kernel_ms[SFQ_T_REC] = ev_ms(ctx->ev[2], ctx->ev[5]);          // the chains overlap: these do not add up
-    res->kernel_ms[SFQ_T_PACK] = ev_ms(ctx->ev[5], ctx->ev[6]);
-    res->kernel_ms[SFQ_T_TOTAL] = ev_ms(ctx->ev[0], ctx->ev[6]);
+    res->kernel_ms[SFQ_T_USR] = ev_ms(ctx->ev[ED_BEGIN], ctx->ev[ED_HEAD_END]);
+    res->kernel_ms[SFQ_T_QLT] = ev_ms(ctx->ev[ED_FORK], ctx->ev[ED_QLT_END]);
+    res->kernel_ms[SFQ_T_GEN] = ev_ms(ctx->ev[ED_GEN_BEGIN], ctx->ev[ED_GEN_END]);
+    res->kernel_ms[SFQ_T_REC] = ev_ms(ctx->ev[ED_FORK], ctx->ev[ED_REC_END]);          // the chains overlap: these do not add up
+    res->kernel_ms[SFQ_T_PACK] = ev_ms(ctx->ev[ED_REC_END], ctx->ev[ED_END]);
+    res->kernel_ms[SFQ_T_TOTAL] = ev_ms(ctx->ev[ED_BEGIN], ctx->ev[ED_END]);
     return SFQ_OK;
 }
 

@@ -405,9 +405,9 @@ static void launch_qlt_lds(const ChainArgs& a, u32 dyn, hipStream_t st) {
 void launch_qlt_encode_c(const ChainArgs& a, hipStream_t st) {
     if (a.exc_flag) { hipLaunchKernelGGL((k_qlt_encode_c<256, false, true>), dim3((a.geo.nchains + 255) / 256), dim3(256), 0, st, a); return; }   // (chains that mark: no caller does)
     if (a.q_hot) {
-        // One workgroup of 1024 lanes per CU shares the image (a table per 256 lanes would hold a quarter of the rows).  205 k chains
-        // are 200 such workgroups: 56 CUs carry no quality chains -- and that is where the other kernels get their work done.  With
-        // workgroups of 832 lanes on 247 CUs the quality chains took as long and the header coder 6.1 ms instead of 2.5.
+        // One workgroup of 1024 lanes per CU shares the image (a table per 256 lanes would hold a quarter of the rows).  The default
+        // geometry aims at as many chains as 256 such workgroups hold, one per CU (api.cpp SFQ_CHAINS_WANT; DESIGN.md 4.5 on why
+        // not the 200 of rounds 4 and 5a).  With workgroups of 832 lanes the quality chains took as long and the header coder 6.1 ms instead of 2.5.
         const u32 dyn = QH_MAP_BYTES(a.q_rows) + a.q_hot * QH_ROW_U16 * 2u;
         launch_qlt_lds<1024>(a, dyn, st);
     } else hipLaunchKernelGGL((k_qlt_encode_c<256, false, false>), dim3((a.geo.nchains + 255) / 256), dim3(256), 0, st, a);
@@ -428,9 +428,6 @@ void launch_qlt_encode_c(const ChainArgs& a, hipStream_t st) {
 //   * stream bytes come through a 64-bit shift register topped up four bytes at a time, the next four always in flight.
 template <int THREADS, bool LDS>
 __global__ __launch_bounds__(THREADS) void k_qlt_decode_c(ChainArgs a, DecodeArgs da) {
-#ifdef PRIO_QDEC
-    __builtin_amdgcn_s_setprio(PRIO_QDEC);
-#endif
     extern __shared__ u32 lds[];                              // the decoder's image: map, then the staged contexts' coarse lists
     const uint2* const lmap = reinterpret_cast<const uint2*>(lds);
     const u16* const lrows = reinterpret_cast<const u16*>(lds + QH_MAP_BYTES(a.q_rows) / 4u);
@@ -456,11 +453,7 @@ __global__ __launch_bounds__(THREADS) void k_qlt_decode_c(ChainArgs a, DecodeArg
     for (u32 k = 0; k < cp.nrec; k++) {
         const u32 n = n_next; const u64 off = off_next;
         if (k + 1 < cp.nrec) { n_next = da.qlen[cp.r0 + k + 1]; off_next = da.qoff[cp.r0 + k + 1]; }
-#ifdef SFQ_EXP_OUT_LOCAL               /* scratch experiment: every lane's output into a small region that stays in L2 (the text comes out wrong) */
-        LaneOut32 out; out.begin(da.qual_stage + (size_t)(c & 8191u) * 64u + 0 * off);
-#else
         LaneOut32 out; out.begin(da.qual_stage + off);
-#endif
         u32 last = 0, p1 = 0, p2 = 0, delta = 5;
         for (u32 i = 0; i < n; i++) {
             // largest s with cum[s] <= prob (cum is increasing: every g >= 1): the eighth of the row from the coarse list, then the
@@ -469,16 +462,11 @@ __global__ __launch_bounds__(THREADS) void k_qlt_decode_c(ChainArgs a, DecodeArg
             u32 hot = ~0u;                                                  // the row's place in the LDS image, if it is staged
             if constexpr (LDS) {
                 const uint2 mr = lmap[last >> 5];
-#ifndef SFQ_EXP_QDEC_FLAT
                 asm volatile("" :: "v"(mr.x), "v"(mr.y));                   // (both words in one read, not the rank behind a branch on the bits)
-#endif
                 const u32 bit = 1u << (last & 31u);
                 if (mr.x & bit) hot = (mr.y + (u32)__popc(mr.x & (bit - 1u))) * QHD_ROW_U16;
             }
             uint4 cv;
-#ifdef SFQ_EXP_QDEC_FLAT
-            if (hot != ~0u) cv = *reinterpret_cast<const uint4*>(lrows + hot); else cv = *reinterpret_cast<const uint4*>(qd);
-#else
             // two loads, not one through a generic pointer (what `staged ? LDS : table` compiles to: a flat load, which takes the
             // vector memory path for all 64 lanes): every lane reads LDS -- a lane whose row is not staged reads list 0 and drops
             // it --, the few lanes without a staged row gather theirs
@@ -490,7 +478,6 @@ __global__ __launch_bounds__(THREADS) void k_qlt_decode_c(ChainArgs a, DecodeArg
                 const bool st = hot != ~0u;
                 cv.x = st ? cl.x : cg.x; cv.y = st ? cl.y : cg.y; cv.z = st ? cl.z : cg.z; cv.w = st ? cl.w : cg.w;
             } else cv = *reinterpret_cast<const uint4*>(qd);
-#endif
             rc.top_up();                                                    // (behind the row's fetch: the two loads travel together)
             u32 r;
             const u32 prob = rc.get_freq16(r);
@@ -1048,7 +1035,7 @@ __global__ __launch_bounds__(THREADS) void k_gen_encode_c(ChainArgs a, u32 c0, u
         if (illegal) atomicMax(&a.m.blocks[cp.b].status, (u32)(-SFQ_E_GENCHAR));
     }
 }
-// ---- bases without a model, packed by a wavefront per chain (block format 10, "chn.idx" flag bit 7) ----------------------------
+// ---- bases without a model, packed by a wavefront per chain (block format 10, "chn.idx" flag CHN_FLAT_RAW) ----------------------------
 // The chain's bases two bits each, four a byte (the first in the low bits), across its records' ends; the last byte padded with
 // zeros; N-like, illegal and lowercase characters code as gen_code_of(c) & 3.  Lane i of the wave owns output dword t = i + 64 j:
 // bases 16 t .. 16 t + 15 of the concatenation.  It finds the record of its first base in the prefix of the line lengths, takes its
@@ -1250,7 +1237,7 @@ __global__ __launch_bounds__(THREADS) void k_gen_decode_c(ChainArgs a, DecodeArg
         const u64 lo = cp.sub_lo < n_next ? cp.sub_lo : n_next;
         n_next = (u32)(n_next - lo < cp.sub_len ? n_next - lo : cp.sub_len); off_next += lo;
     }
-    // (block format 10, "chn.idx" flag bit 7: the chain is its bases, two bits each, four a byte -- no coder)
+    // (block format 10, "chn.idx" flag CHN_FLAT_RAW: the chain is its bases, two bits each, four a byte -- no coder)
     const u8* const raw = da.streams + a.coff[c]; const u32 raw_n = a.csz[c];
     u32 racc = 0, rnb = 0, rat = 0, rbad = 0;
     for (u32 k = 0; k < cp.nrec; k++) {
@@ -1279,7 +1266,7 @@ __global__ __launch_bounds__(THREADS) void k_gen_decode_c(ChainArgs a, DecodeArg
                 last = (last << 2) | b;
                 v = b == 0 ? cand.x : b == 1 ? cand.y : b == 2 ? cand.z : cand.w;
             }
-        } else if (a.flat_quads) {                                                          // no model, four bases a symbol ("chn.idx" flag bit 6)
+        } else if (a.flat_quads) {                                                          // no model, four bases a symbol ("chn.idx" flag CHN_FLAT_QUADS)
             for (u32 i = 0; i < llen; i += 4u) {
                 const u32 k = llen - i < 4u ? llen - i : 4u;
                 rc.top_up();
@@ -1906,9 +1893,6 @@ __device__ __forceinline__ bool rec_tokens(const LT& L, u32 col, u32 n, u32 nf, 
 }
 template <u32 ML>
 __global__ __launch_bounds__(64) void k_rec_tokens(ChainArgs a, u32* __restrict__ tok, u32* __restrict__ ntok, u32* __restrict__ flags) {
-#ifdef PRIO_REC
-    __builtin_amdgcn_s_setprio(PRIO_REC);
-#endif
     __shared__ RecTokLds<ML> L;
     const u32 lane = threadIdx.x, col = lane + 1;
     const u32 c = blockIdx.x;
@@ -2018,9 +2002,6 @@ __device__ __forceinline__ u32 rec_code_entry(const RecCodeLds& L, const u32* __
     return slot != 0xFFu ? L.rows[slot * 256 + sym] : grows[(size_t)row * 256 + sym];
 }
 __global__ __launch_bounds__(256) void k_rec_code(ChainArgs a, const u32* __restrict__ tok, const u32* __restrict__ ntok, const u32* __restrict__ flags, u32 n_hot) {
-#ifdef PRIO_REC
-    __builtin_amdgcn_s_setprio(PRIO_REC);
-#endif
     __shared__ RecCodeLds L;
     for (u32 i = threadIdx.x; i < PR_REC_ROWS; i += 256) { const u32 sl = a.rmap[i]; L.map[i] = (u8)(sl < n_hot ? sl : 0xFFu); }
     for (u32 i = threadIdx.x; i < n_hot * 256; i += 256) L.rows[i] = a.rrows[(size_t)a.rhot[i >> 8] * 256 + (i & 255)];

@@ -67,8 +67,8 @@ std::vector<uint8_t> pack_block_index(const std::vector<sfq_block_info>& blocks)
 bool unpack_block_index(const std::vector<uint8_t>& bytes, std::vector<sfq_block_info>& blocks, int nstreams = SFQ_NSTREAMS);
 
 // The block format's "version" info key.  7: block format, the reference's quirks kept; 8: lossless ("gen.lc", 14 stream sizes per
-// index entry); 9: "chn.idx" may carry flag bits 2-5 (difference-coded lists, segments, Rice-coded base exceptions, the bases' match
-// model): a reader of version 8 did not look at flags it did not know, so what sets them says 9 and is refused there; 10: flag bit 7
+// index entry); 9: "chn.idx" may carry the flags CHN_DELTAS .. CHN_GEN_MATCH (kernels.h ChnFlag: difference-coded lists, segments, Rice-coded base
+// exceptions, the bases' match model): a reader of version 8 did not look at flags it did not know, so what sets them says 9 and is refused there; 10: CHN_FLAT_RAW
 // (bases without a model as two bits each, no coder): a reader of version 9 refuses the flag, so what sets it says 10
 const int kBlockVersion = 10;
 const int kBlockVersionMin = 7;

@@ -209,11 +209,7 @@ struct LaneOut {
         n++;
         if ((n & 3u) == 0) {                                       // a dword is full: the first three of a row of sixteen bytes wait
             const u32 q = (n >> 2) & 3u;
-#ifdef SFQ_EXP_OUT_LOCAL
-            if (q == 0) *reinterpret_cast<uint4*>(p + ((n - 16) & 48u)) = make_uint4(w0, w1, w2, acc);
-#else
             if (q == 0) *reinterpret_cast<uint4*>(p + n - 16) = make_uint4(w0, w1, w2, acc);
-#endif
             w0 = q == 1 ? acc : w0; w1 = q == 2 ? acc : w1; w2 = q == 3 ? acc : w2;
         }
     }

@@ -16,7 +16,7 @@
 //   q < 32: q one bits, a zero bit, the low k bits of v;   else: 32 one bits, then v in 40 bits
 //   A += v, N += 1; when N reaches 32 both are halved.   Start: A = 256, N = 1.
 // Bits fill bytes from the low end; a list ends with v = 0 (no gap is 0) and zero bits up to a byte; an empty list is an empty
-// stream.  oracle/sfq_oracle.c sfqo_exc_rice_block restates it; "chn.idx" flag bit 4 says a call's lists are coded this way
+// stream.  oracle/sfq_oracle.c sfqo_exc_rice_block restates it; "chn.idx" flag CHN_EXC_RICE (kernels.h) says a call's lists are coded this way
 // (archives without it -- rounds 2 and 3 -- are read through k_gen_exc_decode_w).
 #include "kernels.h"
 #include "dev_rice.h"

@@ -576,8 +576,8 @@ __global__ __launch_bounds__(256) void k_block_stream_offsets(BlockDesc* blocks,
     }
     if (threadIdx.x == 0) stream_total[s] = carry_s;
 }
-void launch_block_stream_offsets(BlockDesc* blocks, u32 nblocks, u64* blk_stream_off, u64* stream_total, u32 s0, u32 s1, hipStream_t st) {
-    hipLaunchKernelGGL(k_block_stream_offsets, dim3(s1 - s0), dim3(256), 0, st, blocks, nblocks, blk_stream_off, stream_total, s0);
+void launch_block_stream_offsets(BlockDesc* blocks, u32 nblocks, u64* blk_stream_off, u64* stream_total, hipStream_t st) {
+    hipLaunchKernelGGL(k_block_stream_offsets, dim3(SFQ_NSTREAMS), dim3(256), 0, st, blocks, nblocks, blk_stream_off, stream_total, 0u);
 }
 // Where each stream starts in the caller's buffer, and whether the packing may run at all: the blocks' worst status and the
 // output's size against the caller's room are looked at HERE, so that the host need not come back between the sizes and the

@@ -86,8 +86,8 @@ struct ChainArgs {
     u32 g_bound[GEN_MAX_GENERATIONS + 1];      // generation g = blocks [g_bound[g], g_bound[g + 1])
     const u32* g_rows[GEN_MAX_GENERATIONS];    // its rows (null = the initial row)
     const u32* g_init;          // encode: one dword holding the initial row (3, 3, 3, 3), read where a generation has no rows
-    u32 flat_quads;             // bases without a model (round 5, "chn.idx" flag bit 6): a line's bases four at a time, one symbol of 4^k equally likely ones
-    u32 flat_raw;               // bases without a model (round 5b, "chn.idx" flag bit 7, block format 10): a chain's bases two bits each, four a byte, no coder
+    u32 flat_quads;             // bases without a model (round 5, "chn.idx" flag CHN_FLAT_QUADS): a line's bases four at a time, one symbol of 4^k equally likely ones
+    u32 flat_raw;               // bases without a model (round 5b, "chn.idx" flag CHN_FLAT_RAW, block format 10): a chain's bases two bits each, four a byte, no coder
                                 // (k = 4, fewer at a line's end) instead of 3 of 12 a base
 };
 void launch_hot_rows(const u32* hist, const u32* rows66, const u32* qrows, u32 q_rows, u32 want, u32* ctot /* [q_rows] */,
@@ -123,11 +123,24 @@ void launch_gen_count_binned(const ChainArgs& a, u32 b0, u32 b1, u64 nrec_range,
                              hipStream_t st, u32 sub = 0);
 void launch_gen_encode_c(const ChainArgs& a, hipStream_t st, u32 c0 = 0, u32 c1 = 0 /* chains [c0, c1); 0, 0 = all */, bool flat = false /* every chain: the initial row */);
 // gen.Ns / gen.Nn side streams, a wave per block (models_w.hip); flags: the records that may hold an exception (null = look at all)
+// "chn.idx": the flag byte behind the records per chain.  The ONE definition of its bits: api.cpp writes and reads by these names
+// (tests/util.py parse_chain_index mirrors the numbers on purpose)
+enum ChnFlag : u32 {
+    CHN_GEN_ON     = 1u << 0,   // the bases' generation tables (or, with CHN_GEN_MATCH, their match model) are in use
+    CHN_REC_CHAINS = 1u << 1,   // the headers are coded chain by chain: their geometry and two more lists follow
+    CHN_DELTAS     = 1u << 2,   // every list of sizes as zigzag differences to the entry before (version-8 archives: plain)
+    CHN_SEGMENTS   = 1u << 3,   // chains are segments of one record (long reads): their length and the blocks' shares follow
+    CHN_EXC_RICE   = 1u << 4,   // the base exceptions are Rice-coded gap lists (exc.hip)
+    CHN_GEN_MATCH  = 1u << 5,   // the bases are coded under the match model (gm.hip): the index's bits and the base chains' geometry follow
+    CHN_FLAT_QUADS = 1u << 6,   // bases without a model, four a symbol through the coder (block format 9; still read)
+    CHN_FLAT_RAW   = 1u << 7,   // bases without a model, two bits each, no coder (block format 10)
+    CHN_KNOWN      = (1u << 8) - 1
+};
 // "chn.idx": the size lists csz[0 .. n) (lists [0, b1), [b1, b2), [b2, b3), [b3, n)) as zigzag-difference varints, back to back in
 // out; len[n], off[n + 1], scan_tmp: scratch; info[0] = bytes before list b2, info[1] = all
 void launch_chain_index_bytes(const u32* csz, u32 n, u32 b1, u32 b2, u32 b3, u32* len, u64* off, u64* scan_tmp, u8* out, u64* info, hipStream_t st);
 void launch_gen_exc_w(const ModelArgs& a, const u8* flags, u32* ticket, hipStream_t st);
-// the same lists as adaptive Rice codes (models_w.hip k_gen_exc_w<true>, dev_rice.h; frozen tables, "chn.idx" flag bit 4) and the way back, a lane per block (exc.hip)
+// the same lists as adaptive Rice codes (models_w.hip k_gen_exc_w<true>, dev_rice.h; frozen tables, "chn.idx" flag CHN_EXC_RICE) and the way back, a lane per block (exc.hip)
 void launch_gen_exc_r(const ModelArgs& a, const u8* flags, u32* ticket, hipStream_t st);
 void launch_gen_exc_decode_r(const struct DecodeArgs& a, u32 nblocks, hipStream_t st);
 #define REC_COUNT_COPIES 32u        // the header prior's counting pass counts into this many copies of the table (chains.hip k_rec_count_sum)
@@ -148,7 +161,7 @@ void launch_seg_count_dec(const u32* slen, const u32* qlen, u64 nrec, u32 seg_le
 void launch_seg_fill(const u64* seg_off, u64 nrec, u32* seg_rec, hipStream_t st);
 void launch_chain_block_sizes(const ChainArgs& a, const ChainGeoArgs& geo, int stream, const u32* csz, const u32* rhb /* or null */, hipStream_t st);
 void launch_compact_chains(const ChainArgs& a, const ChainGeoArgs& geo, int stream, u32 num, u32 den, const u32* csz, const u64* blk_stream_off,
-                           const u64* stream_base, u8* out, hipStream_t st, const u32* gate = nullptr /* frame.hip k_stream_gate */);
+                           const u64* stream_base, u8* out, hipStream_t st, const u32* gate /* frame.hip k_stream_gate */);
 #define GEN_STEP 4u             // a counted base adds GEN_STEP to its row entry (chains.hip)
 // A generation of n records (its blocks x block_reads: the last block of a call may be short) is counted through every
 // s-th record, s = ceil(n / GEN_COUNT_CAP): half a million records tell a row's shape, and the counting -- a
@@ -221,9 +234,9 @@ void launch_gen_decode_w(const DecodeArgs& a, hipStream_t st);          // (gen_
 void launch_rec_decode_w(const DecodeArgs& a, hipStream_t st);
 
 // packing
-void launch_block_stream_offsets(BlockDesc* blocks, u32 nblocks, u64* blk_stream_off, u64* stream_total, u32 s0, u32 s1 /* streams [s0, s1) */, hipStream_t st);
+void launch_block_stream_offsets(BlockDesc* blocks, u32 nblocks, u64* blk_stream_off, u64* stream_total, hipStream_t st);      // every stream of the call
 void launch_compact(const BlockDesc* blocks, u32 nblocks, const u8* arena, const u64* blk_stream_off,
-                    const u64* stream_base, u8* out, u32 skip_streams /* bit s: stream s is packed by launch_compact_chains */, hipStream_t st, const u32* gate = nullptr);
+                    const u64* stream_base, u8* out, u32 skip_streams /* bit s: stream s is packed by launch_compact_chains */, hipStream_t st, const u32* gate);
 void launch_stream_gate(const BlockDesc* blocks, u32 nblocks, const u64* stream_total, u64 out_cap, u64* stream_base /* [SFQ_NSTREAMS] */, u32* gate /* [2]: go, worst status */, hipStream_t st);
 void launch_record_sizes(const DecodeArgs& a, u64 nrec, u32* rsize, hipStream_t st);
 void launch_assemble(const DecodeArgs& a, u64 nrec, const u64* roff, u8* out, hipStream_t st);

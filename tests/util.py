@@ -129,7 +129,8 @@ def write_archive(path: str, info_text: str, streams):
 
 def unpack_chains(blob: bytes, nblocks=None):
     """"chn.idx" -> dict(chain_reads, flags, qlt, gen [, seg_len, seg_blocks] [, rec_chain_reads, rec, rec_hdr_bytes]); mirrors api.cpp.
-    flags bit 2: every list of sizes is stored as zigzag differences to the entry before it; bit 3: the chains are SEGMENTS of one
+    The flag bits are csrc/kernels.h enum ChnFlag (CHN_GEN_ON = bit 0 .. CHN_FLAT_RAW = bit 7); this parser keeps its own numbers, as the
+    independent mirror.  flags bit 2: every list of sizes is stored as zigzag differences to the entry before it; bit 3: the chains are SEGMENTS of one
     record -- their length and every block's number of chains follow the chain count (nblocks must be given); bit 4: the base
     exceptions are Rice-coded gap lists (exc.hip); bit 5: the bases are coded under the generation match model (gm.hip), the bits of its index
     follow the flags."""
