@@ -152,7 +152,7 @@ typedef struct sfq_result {
     uint64_t stream_offset[SFQ_NSTREAMS];  /* per stream: where its block-concatenation starts in d_out */
     uint64_t total_bytes;                  /* bytes used in d_out                                  */
     uint64_t first_hdr_bytes;              /* size of the first-header blob (see sfq_get_first_headers) */
-    uint32_t n_chains;                     /* frozen tables: chains per chain-coded stream (else 0)   */
+    uint32_t n_chains;                     /* frozen tables: chains per chain-coded stream (else 0); sfq_decode_block_range: quality chains decoded */
     uint32_t reserved;
     double   kernel_ms[8];                 /* device time of the last call, by phase (see SFQ_T_*): a model's phase is
                                               everything on its stream -- counting passes, row building, the coding kernel */
@@ -255,6 +255,27 @@ int sfq_decode_blocks_host(sfq_ctx* ctx, const sfq_params* params, const sfq_blo
                            const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
                            const uint8_t* h_streams, uint64_t streams_bytes, const uint64_t stream_offset[SFQ_NSTREAMS],
                            uint8_t* h_fastq_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* result);
+/* A WINDOW of the call's blocks -- blocks [first_block, first_block + n_window) -- without decoding the rest (the reference has no
+ * counterpart: UsrLoad::decode reads a file from its first record on).  h_blocks, n_blocks, the first-header blob, stream_offset and the
+ * installed blobs (sfq_set_qlt_prior / sfq_set_rec_prior / sfq_set_chain_index) describe the WHOLE call, exactly as for
+ * sfq_decode_blocks; the output is the text of the window's records and nothing else, from byte 0 of the output buffer, *out_bytes its
+ * length (SFQ_E_OVERFLOW: the size needed).  result->n_records / n_blocks are the window's; result->n_chains = the quality chains
+ * the call decoded (0 with adaptive tables).  What is decoded outside the window is what the format forces: with
+ * frozen tables and a base model ("chn.idx" flag bit 0) the line lengths of the blocks in front and the bases of the generations
+ * before the window's last block's; otherwise nothing.  n_window = 0 or a window past n_blocks: SFQ_E_ARG; a one-block archive with
+ * oversize records (usr.lrec): SFQ_E_UNSUPPORTED.  Checksums installed with sfq_set_block_checksums are the WINDOW's blocks' (n must
+ * equal n_window), and sfq_get_checksums returns n_window values.  The _host entry copies to the device only the byte ranges of
+ * every stream that the call reads. */
+int sfq_decode_block_range(sfq_ctx* ctx, const sfq_params* params, const sfq_block_info* h_blocks, uint32_t n_blocks,
+                           const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
+                           const uint8_t* d_streams, const uint64_t stream_offset[SFQ_NSTREAMS],
+                           uint32_t first_block, uint32_t n_window,
+                           uint8_t* d_fastq_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* result);
+int sfq_decode_block_range_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_info* h_blocks, uint32_t n_blocks,
+                                const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
+                                const uint8_t* h_streams, uint64_t streams_bytes, const uint64_t stream_offset[SFQ_NSTREAMS],
+                                uint32_t first_block, uint32_t n_window,
+                                uint8_t* h_fastq_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* result);
 
 /* ---- checksums ------------------------------------------------------------------------------------------------------
  * CRC-32 (IEEE 802.3, reflected, polynomial 0xEDB88320, init and final XOR 0xFFFFFFFF: the value of zlib's crc32) computed

@@ -27,7 +27,7 @@ EXPORTS = [
     "sfq_archive_write", "sfq_pack_block_index", "sfq_ctx_device_memory", "sfq_get_chain_index", "sfq_set_chain_index", "sfq_get_rec_prior", "sfq_set_rec_prior", "sfq_build_priors",
     "sfq_host_alloc", "sfq_host_free", "sfq_count_priors", "sfq_prior_counts_words", "sfq_get_prior_counts", "sfq_set_prior_counts",
     "sfq_archive_write_segments", "sfq_crc32", "sfq_crc32_combine", "sfq_ctx_set_checksums", "sfq_get_checksums",
-    "sfq_set_block_checksums",
+    "sfq_set_block_checksums", "sfq_decode_block_range", "sfq_decode_block_range_host",
 ]
 
 
@@ -119,6 +119,10 @@ def lib():
                                         C.POINTER(u64), u8p, u64, C.POINTER(u64), C.POINTER(Result)]
         L.sfq_decode_blocks_host.argtypes = [vp, C.POINTER(Params), C.POINTER(BlockInfo), C.c_uint32, u8p, u64, u8p, u64,
                                              C.POINTER(u64), u8p, u64, C.POINTER(u64), C.POINTER(Result)]
+        L.sfq_decode_block_range.argtypes = [vp, C.POINTER(Params), C.POINTER(BlockInfo), C.c_uint32, u8p, u64, u8p,
+                                             C.POINTER(u64), C.c_uint32, C.c_uint32, u8p, u64, C.POINTER(u64), C.POINTER(Result)]
+        L.sfq_decode_block_range_host.argtypes = [vp, C.POINTER(Params), C.POINTER(BlockInfo), C.c_uint32, u8p, u64, u8p, u64,
+                                                  C.POINTER(u64), C.c_uint32, C.c_uint32, u8p, u64, C.POINTER(u64), C.POINTER(Result)]
         L.sfq_get_qlt_prior.argtypes = [vp, u8p, u64]
         L.sfq_get_qlt_prior.restype = C.c_int64
         L.sfq_set_qlt_prior.argtypes = [vp, u8p, u64]
@@ -436,3 +440,48 @@ class Context:
                                              data.ctypes.data_as(C.c_void_p), len(data), soff,
                                              out.ctypes.data_as(C.c_void_p), out_cap, C.byref(n), C.byref(res)))
         return out[:n.value].tobytes()
+
+    def decode_range_device(self, blocks, first_hdrs: bytes, d_streams, stream_offset, first_block, n_window, d_out, out_cap, prior=b"",
+                            level=3, version=0, chains=b"", lds_rows=0, rec_prior=b"", kernel=0, crcs=None):
+        """Device-pointer decode of blocks [first_block, first_block + n_window) of a call (sfq_decode_block_range): blocks, the first
+        headers, stream_offset and the blobs are the whole call's; crcs: the window's expected CRCs.  Returns (bytes written, Result)."""
+        L = lib()
+        self._check(L.sfq_set_qlt_prior(self._h, prior if prior else None, len(prior)))
+        self._check(L.sfq_set_chain_index(self._h, chains if chains else None, len(chains)))
+        self._check(L.sfq_set_rec_prior(self._h, rec_prior if rec_prior else None, len(rec_prior)))
+        if crcs is not None:
+            self.set_block_checksums(crcs)
+        p = Params(level, 0, 0, 0, kernel, version, 0, 0, 0, lds_rows)
+        res = Result()
+        n = C.c_uint64()
+        fb = np.frombuffer(first_hdrs if len(first_hdrs) else b"\0", np.uint8)
+        soff = (C.c_uint64 * NSTREAMS)(*list(stream_offset))
+        self._check(L.sfq_decode_block_range(self._h, C.byref(p), blocks, len(blocks), fb.ctypes.data_as(C.c_void_p), len(first_hdrs),
+                                             C.c_void_p(d_streams), soff, first_block, n_window, C.c_void_p(d_out), out_cap,
+                                             C.byref(n), C.byref(res)))
+        return n.value, res
+
+    def decode_range_host(self, enc: Encoded, first_block, n_window, level=3, version=0, out_cap=None, kernel=0, lds_rows=0, crcs=None):
+        """Blocks [first_block, first_block + n_window) of an Encoded back to FASTQ text (sfq_decode_block_range_host); crcs: the
+        window's expected CRCs (default: the window's share of enc.crcs, where the encode computed them).  Returns (text, Result)."""
+        L = lib()
+        self._check(L.sfq_set_qlt_prior(self._h, enc.prior if enc.prior else None, len(enc.prior)))
+        self._check(L.sfq_set_chain_index(self._h, enc.chains if enc.chains else None, len(enc.chains)))
+        self._check(L.sfq_set_rec_prior(self._h, enc.rec_prior if enc.rec_prior else None, len(enc.rec_prior)))
+        data = enc.data if isinstance(enc.data, np.ndarray) else np.ascontiguousarray(np.frombuffer(bytes(enc.data), np.uint8))
+        if crcs is None and enc.crcs is not None:
+            crcs = enc.crcs[first_block:first_block + n_window]
+        if crcs is not None:
+            self.set_block_checksums(crcs)
+        p = Params(level, 0, 0, 0, kernel, version, 0, 0, 0, lds_rows)
+        res = Result()
+        if out_cap is None:
+            out_cap = 64 * len(data) + (1 << 20)
+        out = np.empty(out_cap, np.uint8)
+        n = C.c_uint64()
+        fb = np.frombuffer(enc.first_hdrs if len(enc.first_hdrs) else b"\0", np.uint8)
+        soff = (C.c_uint64 * NSTREAMS)(*list(enc.res.stream_offset))
+        self._check(L.sfq_decode_block_range_host(self._h, C.byref(p), enc.blocks, len(enc.blocks), fb.ctypes.data_as(C.c_void_p), len(enc.first_hdrs),
+                                                  data.ctypes.data_as(C.c_void_p), len(data), soff, first_block, n_window,
+                                                  out.ctypes.data_as(C.c_void_p), out_cap, C.byref(n), C.byref(res)))
+        return out[:n.value].tobytes(), res

@@ -1912,7 +1912,10 @@ int sfq_set_chain_index(sfq_ctx* ctx, const uint8_t* h_blob, uint64_t n) {
 static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info* h_blocks, uint32_t nblocks,
                        const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
                        const uint8_t* d_streams, const uint64_t stream_offset[SFQ_NSTREAMS],
-                       uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* res, const u32* expect);
+                       uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* res, const u32* expect, const struct Window& w);
+// The blocks [b0, b0 + n) of the call that one decode produces: all of them (sfq_decode_blocks), or a window (sfq_decode_block_range:
+// ranged -- what is outside the window is decoded only where the format forces it, decode_body)
+struct Window { u32 b0, n; bool ranged; };
 // The checksums installed with sfq_set_block_checksums belong to the decode call that follows, whatever it returns: both entry
 // points take them before anything else, so that no early return leaves them for the call after.
 struct Expected {
@@ -1922,18 +1925,19 @@ struct Expected {
 static int decode_device(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info* h_blocks, uint32_t nblocks,
                          const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
                          const uint8_t* d_streams, const uint64_t stream_offset[SFQ_NSTREAMS],
-                         uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* res, const Expected& ex) {
+                         uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* res, const Expected& ex, const Window& w) {
     if (!pp || !h_blocks || !nblocks || !d_streams || !stream_offset || !d_out || !out_bytes)
         return fail(ctx, SFQ_E_ARG, "null argument");
+    if (w.n == 0 || w.b0 >= nblocks || w.n > nblocks - w.b0) return fail(ctx, SFQ_E_ARG, "blocks %u..+%u: not a window of the call's %u blocks", w.b0, w.n, nblocks);
     HIPC(hipSetDevice(ctx->dev));
     Settle settle(ctx);
     drop_encode_blobs(ctx);                             // whatever an encode left behind is not this archive's
     ctx->crcs.clear(); ctx->text_crc = 0;
     const bool check = ex.set;
     const std::vector<u32>& expect = ex.crc;
-    if (check && expect.size() != nblocks) return fail(ctx, SFQ_E_ARG, "%zu block checksums installed for a call of %u blocks", expect.size(), nblocks);
+    if (check && expect.size() != w.n) return fail(ctx, SFQ_E_ARG, "%zu block checksums installed for a call of %u blocks", expect.size(), w.n);
     const int rc = decode_body(ctx, pp, h_blocks, nblocks, h_first_hdrs, first_hdr_bytes, d_streams, stream_offset, d_out, out_cap, out_bytes, res,
-                               check ? expect.data() : nullptr);
+                               check ? expect.data() : nullptr, w);
     settle.ok = rc == SFQ_OK;
     return rc;
 }
@@ -1943,12 +1947,20 @@ int sfq_decode_blocks(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info* 
                       uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* res) {
     if (!ctx) return SFQ_E_ARG;
     const Expected ex(ctx);
-    return decode_device(ctx, pp, h_blocks, nblocks, h_first_hdrs, first_hdr_bytes, d_streams, stream_offset, d_out, out_cap, out_bytes, res, ex);
+    return decode_device(ctx, pp, h_blocks, nblocks, h_first_hdrs, first_hdr_bytes, d_streams, stream_offset, d_out, out_cap, out_bytes, res, ex, Window{ 0, nblocks, false });
+}
+int sfq_decode_block_range(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info* h_blocks, uint32_t nblocks,
+                           const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
+                           const uint8_t* d_streams, const uint64_t stream_offset[SFQ_NSTREAMS], uint32_t first_block, uint32_t n_window,
+                           uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* res) {
+    if (!ctx) return SFQ_E_ARG;
+    const Expected ex(ctx);
+    return decode_device(ctx, pp, h_blocks, nblocks, h_first_hdrs, first_hdr_bytes, d_streams, stream_offset, d_out, out_cap, out_bytes, res, ex, Window{ first_block, n_window, true });
 }
 static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info* h_blocks, uint32_t nblocks,
                        const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
                        const uint8_t* d_streams, const uint64_t stream_offset[SFQ_NSTREAMS],
-                       uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* res, const u32* expect) {
+                       uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* res, const u32* expect, const Window& win) {
     sfq_params p = *pp;
     HostTimes ht;
     p.level = clamp_level(p.level);
@@ -2007,6 +2019,11 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
         if (h_blocks[b].size[SFQ_S_USR_LREC] | h_blocks[b].size[SFQ_S_USR_LGEN] | h_blocks[b].size[SFQ_S_USR_LQLT])
             return fail(ctx, SFQ_E_UNSUPPORTED, "block %u holds oversize records (usr.lrec): only a one-block (format 6) archive does", b);
     if (has_over && nblocks != 1) return fail(ctx, SFQ_E_UNSUPPORTED, "oversize records (usr.lrec) in an archive of %u blocks: only a one-block (format 6) archive has them", nblocks);
+    if (has_over && win.ranged) return fail(ctx, SFQ_E_UNSUPPORTED, "a window of an archive with oversize records (usr.lrec): its one block is not cut");
+    // The window: blocks [wb0, wb1), records [wr0, wr1).  Every per-record and per-chain array below keeps the CALL's numbering -- a kernel
+    // indexes it with the record or chain it works on, whatever the window -- while grids, scans and the staged text are the window's.
+    const u32 wb0 = win.b0, wb1 = win.b0 + win.n;
+    const u64 wr0 = h_blocks[wb0].first_record; u64 wr1 = h_blocks[wb1 - 1].first_record + h_blocks[wb1 - 1].n_records, nrec_w = wr1 - wr0;
     ht.mark("blocks checked");
     // frozen tables: the chain index ("chn.idx")
     const bool frozen = !ctx->chain_blob.empty();
@@ -2141,6 +2158,19 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
         });
     }
     ht.mark("  header prior, chain sizes up");
+    // What a window needs from outside itself.  A base model (generation tables, the match model) reads the decoded bases of every
+    // EARLIER generation at absolute stage positions: the line lengths (usr.*) of blocks [0, wb1) and the bases of the generations
+    // before the window's last block's, G.  Segments: a record's chains follow from its line lengths, and the chains are numbered over
+    // the call -- the usr.* streams of [0, wb1) again (long reads: few records).  Everything else is the window's alone.
+    u32 bound[GEN_MAX_GENERATIONS + 1];
+    const u32 ngen = gen_bounds(nblocks, bound);
+    u32 G = 0; while (bound[G + 1] < wb1) G++;
+    const bool base_prefix = frozen && gen_on && ngen >= 3;
+    const u32 ub0 = (base_prefix || seg_len) ? 0u : wb0, sb0 = base_prefix ? 0u : wb0;        // first block of the usr.* decode / of the base stage
+    const u64 ur0 = h_blocks[ub0].first_record, sr0 = h_blocks[sb0].first_record;
+    // generation g's blocks that are decoded: all of an earlier generation, the window's share of G
+    auto gen_lo = [&](u32 g) -> u32 { return g < G ? bound[g] : std::max(wb0, bound[G]); };
+    auto gen_hi = [&](u32 g) -> u32 { return g < G ? bound[g + 1] : wb1; };
     if ((rc = reserve(ctx, ctx->blocks, (size_t)nblocks * sizeof(BlockDesc)))) return rc;
     if ((rc = reserve(ctx, ctx->blk_stream_off, nbso * 8))) return rc;
     if ((rc = reserve(ctx, ctx->d_first, (size_t)first_hdr_bytes + 16))) return rc;
@@ -2150,20 +2180,20 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
 
     const u32 q_rows = p.level == 1 ? (1u << 12) : (1u << 16);
     u32 slots = 0;
-    if ((rc = ensure_tables(ctx, nblocks, q_rows, (u32)g_bits, frozen ? (SFQ_M_REC | SFQ_M_USR) : SFQ_M_ALL, &slots))) return rc;
+    if ((rc = ensure_tables(ctx, wb1 - ub0, q_rows, (u32)g_bits, frozen ? (SFQ_M_REC | SFQ_M_USR) : SFQ_M_ALL, &slots))) return rc;
     if ((rc = advance_epoch(ctx, nblocks))) return rc;
 
-    if ((rc = reserve(ctx, ctx->slen, (size_t)nrec * 4))) return rc;
-    if ((rc = reserve(ctx, ctx->qlen, (size_t)nrec * 4))) return rc;
-    if ((rc = reserve(ctx, ctx->pfg, (size_t)nrec))) return rc;
-    if ((rc = reserve(ctx, ctx->pfq, (size_t)nrec))) return rc;
-    if ((rc = reserve(ctx, ctx->soff, ((size_t)nrec + 1) * 8))) return rc;
-    if ((rc = reserve(ctx, ctx->qoff, ((size_t)nrec + 1) * 8))) return rc;
-    if ((rc = reserve(ctx, ctx->hlen, (size_t)nrec * 4))) return rc;
-    if ((rc = reserve(ctx, ctx->hoff, (size_t)nrec * 8))) return rc;
-    if ((rc = reserve(ctx, ctx->rsize, (size_t)nrec * 4))) return rc;
-    if ((rc = reserve(ctx, ctx->roff, ((size_t)nrec + 1) * 8))) return rc;
-    if ((rc = reserve(ctx, ctx->scan_tmp, ((size_t)nrec / 1024 + 4) * 8 + 65536))) return rc;
+    if ((rc = reserve(ctx, ctx->slen, (size_t)wr1 * 4))) return rc;
+    if ((rc = reserve(ctx, ctx->qlen, (size_t)wr1 * 4))) return rc;
+    if ((rc = reserve(ctx, ctx->pfg, (size_t)wr1))) return rc;
+    if ((rc = reserve(ctx, ctx->pfq, (size_t)wr1))) return rc;
+    if ((rc = reserve(ctx, ctx->soff, ((size_t)wr1 + 1) * 8))) return rc;
+    if ((rc = reserve(ctx, ctx->qoff, ((size_t)wr1 + 1) * 8))) return rc;
+    if ((rc = reserve(ctx, ctx->hlen, (size_t)wr1 * 4))) return rc;
+    if ((rc = reserve(ctx, ctx->hoff, (size_t)wr1 * 8))) return rc;
+    if ((rc = reserve(ctx, ctx->rsize, (size_t)wr1 * 4))) return rc;
+    if ((rc = reserve(ctx, ctx->roff, ((size_t)wr1 + 1) * 8))) return rc;
+    if ((rc = reserve(ctx, ctx->scan_tmp, ((size_t)wr1 / 1024 + 4) * 8 + 65536))) return rc;
 
     ctx->prior_on = false;
     if (!ctx->prior_blob.empty()) {
@@ -2182,7 +2212,11 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
     da.slen = (u32*)ctx->slen.p; da.qlen = (u32*)ctx->qlen.p; da.pfg = (u8*)ctx->pfg.p; da.pfq = (u8*)ctx->pfq.p;
     da.soff = (const u64*)ctx->soff.p; da.qoff = (const u64*)ctx->qoff.p;
     da.hlen = (u32*)ctx->hlen.p; da.hoff = (u64*)ctx->hoff.p;
-    da.block_reads = block_reads; da.version = version; da.max_line = (u32)std::min<u64>(out_cap, 0x3ffffffeull);
+    da.block_reads = block_reads; da.version = version;
+    // (the caller's capacity bounds a line of the text it gets.  The usr.* streams of blocks in FRONT of a window are decoded by the same kernels,
+    //  and a record there may be longer than the whole window: those runs keep the format's own bound, and what the window's lines add up to is
+    //  checked against the capacity behind the scans, below)
+    da.max_line = ub0 < wb0 ? 0x3ffffffeu : (u32)std::min<u64>(out_cap, 0x3ffffffeull);
 
     // 0. format 6's oversize records (UsrLoad::update, usrs.cpp:473-485): their numbers and raw lines first -- the other
     //    streams count records in file numbers, the models never saw them
@@ -2224,6 +2258,7 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
         launch_scan_u32((const u32*)ctx->oflags.p, (u64*)ctx->ofpos.p, nrec_file, (u64*)ctx->scan_tmp.p, st);
         launch_over_map((const u32*)ctx->oflags.p, (const u64*)ctx->ofpos.p, nrec_file, (u32*)ctx->orecmap.p, st);
         nrec = nrec_file - n_over;
+        wr1 = nrec; nrec_w = nrec;                         // (one block, decoded whole: the window is the records the models saw)
         hb[0].nrec = (u32)nrec;
         HIPC(hipMemcpyAsync(&((BlockDesc*)ctx->blocks.p)[0].nrec, &hb[0].nrec, 4, hipMemcpyHostToDevice, st));
         da.m.rec_map = (const u32*)ctx->orecmap.p;
@@ -2235,53 +2270,59 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
     if (frozen && rec_chains != 0) { if ((rc = upload_rec_rows(ctx, rec_prior_f, st))) return rc; }
     // "no header yet" for every record, while the chip is still idle: behind the decoders' launches these two fills -- 120 MB, a fill
     // kernel that must find room beside them -- took 2.4 ms on the header decoder's stream (hdr_marks_cleared)
-    HIPC(hipMemsetAsync(ctx->hoff.p, 0xFF, (size_t)nrec * 8, st));
-    HIPC(hipMemsetAsync(ctx->hlen.p, 0, (size_t)nrec * 4, st));
+    HIPC(hipMemsetAsync((u64*)ctx->hoff.p + wr0, 0xFF, (size_t)nrec_w * 8, st));
+    HIPC(hipMemsetAsync((u32*)ctx->hlen.p + wr0, 0, (size_t)nrec_w * 4, st));
     const u32 usr_prefilled = (block_reads != 0 && !has_over && nblocks > 1) ? 1u : 0u;
-    if (usr_prefilled) launch_usr_fill(da, nrec, st);
+    if (usr_prefilled) launch_usr_fill(da, ur0, wr1, st);
     // (a wave per block -- decode_w.hip -- unless the cross-check kernels are asked for or format 6's oversize records break the count of the records)
-    for (u32 b0 = 0; b0 < nblocks; b0 += slots) {
-        da.m.batch0 = b0; da.m.nbatch = std::min(slots, nblocks - b0);
+    for (u32 b0 = ub0; b0 < wb1; b0 += slots) {
+        da.m.batch0 = b0; da.m.nbatch = std::min(slots, wb1 - b0);
         if (p.kernel == 0 && !has_over) launch_usr_decode_w(da, st, usr_prefilled); else launch_usr_decode_l(da, st, usr_prefilled);
     }
-    const u32 spad = (frozen && !gm_on && !gen_on && exc_rice && !seg_len && nrec && out_cap / nrec >= 128) ? 31u : 0u;
+    // The places of the lines in their stages: scans over the records that are staged -- [sr0, wr1) for the bases, the window for the
+    // qualities --, written at the records' own indices, so a stage starts at its first staged record and is as large as what is staged
+    const u64 nrec_s = wr1 - sr0;
+    u32* const slen_s = da.slen + sr0; u64* const soff_s = (u64*)ctx->soff.p + sr0;
+    const u32 spad = (frozen && !gm_on && !gen_on && exc_rice && !seg_len && nrec_w && out_cap / nrec_w >= 128) ? 31u : 0u;
     if (gm_on) {
-        // the match model's stage: a '\n' behind every base line (gm.hip) -- soff[r] = (bases before r) + r
-        if ((rc = reserve(ctx, ctx->gm_boff, ((size_t)nrec + 1) * 8))) return rc;
-        launch_scan_u32(da.slen, (u64*)ctx->gm_boff.p, nrec, (u64*)ctx->scan_tmp.p, st);
-        launch_gm_soff((const u64*)ctx->gm_boff.p, nrec, (u64*)ctx->soff.p, st);
+        // the match model's stage: a '\n' behind every base line (gm.hip) -- soff[r] = (bases before r) + r  (a base model: sr0 = 0)
+        if ((rc = reserve(ctx, ctx->gm_boff, ((size_t)wr1 + 1) * 8))) return rc;
+        launch_scan_u32(da.slen, (u64*)ctx->gm_boff.p, wr1, (u64*)ctx->scan_tmp.p, st);
+        launch_gm_soff((const u64*)ctx->gm_boff.p, wr1, (u64*)ctx->soff.p, st);
         da.boff = (const u64*)ctx->gm_boff.p;
     } else if (spad) {
         // flat bases (no model of either kind), Rice-coded exception lists: the lines start on 32-byte sectors, as the quality lines do; the
         // exception lists' positions count bases, so the bases before every record go along (exc.hip)
-        if ((rc = reserve(ctx, ctx->gm_boff, ((size_t)nrec + 1) * 8))) return rc;
-        launch_scan_u32(da.slen, (u64*)ctx->gm_boff.p, nrec, (u64*)ctx->scan_tmp.p, st);
-        launch_scan_u32(da.slen, (u64*)ctx->soff.p, nrec, (u64*)ctx->scan_tmp.p, st, spad);
+        if ((rc = reserve(ctx, ctx->gm_boff, ((size_t)wr1 + 1) * 8))) return rc;
+        launch_scan_u32(slen_s, (u64*)ctx->gm_boff.p + sr0, nrec_s, (u64*)ctx->scan_tmp.p, st);
+        launch_scan_u32(slen_s, soff_s, nrec_s, (u64*)ctx->scan_tmp.p, st, spad);
         da.boff = (const u64*)ctx->gm_boff.p;
     } else
-    launch_scan_u32(da.slen, (u64*)ctx->soff.p, nrec, (u64*)ctx->scan_tmp.p, st);
+    launch_scan_u32(slen_s, soff_s, nrec_s, (u64*)ctx->scan_tmp.p, st);
     // the quality lines' places in their stage: on 32-byte sectors where the lines are long enough for that to cost little (dev_chain.h LaneOut32)
-    const u32 qpad = (frozen && nrec && out_cap / nrec >= 128) ? 31u : 0u;
-    launch_scan_u32(da.qlen, (u64*)ctx->qoff.p, nrec, (u64*)ctx->scan_tmp.p, st, qpad);
-    u64 tot_s = 0, tot_q = 0;
+    const u32 qpad = (frozen && nrec_w && out_cap / nrec_w >= 128) ? 31u : 0u;
+    launch_scan_u32(da.qlen + wr0, (u64*)ctx->qoff.p + wr0, nrec_w, (u64*)ctx->scan_tmp.p, st, qpad);
+    u64 tot_s = 0, tot_q = 0, s_w0 = 0;                // the stages' sizes; where the window's bases start in theirs
     u32 dec_max_line = 0;                              // the longest base line (how the base tables' counting passes split their work)
     if (frozen && gen_on) {                            // (only the generation tables' counting passes ask: 0.12 ms of the head otherwise)
         if ((rc = reserve(ctx, ctx->status, 256))) return rc;
         HIPC(hipMemsetAsync(ctx->status.p, 0, 256, st));
-        launch_max_u32(da.slen, nrec, (u32*)ctx->status.p, st);
+        launch_max_u32(slen_s, nrec_s, (u32*)ctx->status.p, st);
         HIPC(hipMemcpyAsync(&dec_max_line, ctx->status.p, 4, hipMemcpyDeviceToHost, st));
     }
-    HIPC(hipMemcpyAsync(&tot_s, (u64*)ctx->soff.p + nrec, 8, hipMemcpyDeviceToHost, st));
-    HIPC(hipMemcpyAsync(&tot_q, (u64*)ctx->qoff.p + nrec, 8, hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(&tot_s, (u64*)ctx->soff.p + wr1, 8, hipMemcpyDeviceToHost, st));
+    if (sr0 != wr0) HIPC(hipMemcpyAsync(&s_w0, (u64*)ctx->soff.p + wr0, 8, hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(&tot_q, (u64*)ctx->qoff.p + wr1, 8, hipMemcpyDeviceToHost, st));
     HIPC(hipEventRecord(ctx->ev[ED_HEAD_END], st));
     HIPC(hipStreamSynchronize(st));
     // (a damaged usr stream can claim any lengths: what cannot fit the caller's buffer is refused before anything is decoded)
-    if (tot_s > out_cap + (u64)spad * nrec || tot_q > out_cap + (u64)qpad * nrec) return fail(ctx, SFQ_E_CORRUPT, "line lengths add up to %llu bases / %llu qualities, the output buffer holds %llu bytes",
+    // (the bases staged in FRONT of a window are not the caller's text: what they add up to is bounded by the device's memory, below)
+    if (tot_s - s_w0 > out_cap + (u64)spad * nrec_w || tot_q > out_cap + (u64)qpad * nrec_w) return fail(ctx, SFQ_E_CORRUPT, "line lengths add up to %llu bases / %llu qualities, the output buffer holds %llu bytes",
                                                            (unsigned long long)tot_s, (unsigned long long)tot_q, (unsigned long long)out_cap);
     if ((rc = reserve(ctx, ctx->seq_stage, (size_t)tot_s + 64))) return rc;          // (gm.hip's windows read sixteen bytes at any place up to tot_s)
     if ((rc = reserve(ctx, ctx->qual_stage, (size_t)tot_q + 16))) return rc;
     da.seq_stage = (u8*)ctx->seq_stage.p; da.qual_stage = (u8*)ctx->qual_stage.p;
-    if (gm_on && seg_len) launch_gm_sentinels(da.seq_stage, da.soff, da.slen, nrec, st);        // (whole-record chains write their lines' sentinels themselves)
+    if (gm_on && seg_len) launch_gm_sentinels(da.seq_stage, da.soff, da.slen, wr1, st);        // (whole-record chains write their lines' sentinels themselves)
 
     ht.mark("head queued");
     const size_t lists_cap = lists_pending ? ctx->chain_blob.size() + 16 : 0;       // (every listed size is a byte of the index or more: what h_csz / h_coff were sized by)
@@ -2337,17 +2378,18 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
         if (seg_len) {
             // segments: a record's share of the chains follows from its line lengths (the usr streams have given them); what the
             // index says of the blocks must agree
-            if ((rc = reserve(ctx, ctx->segn, (size_t)nrec * 4))) return rc;
-            if ((rc = reserve(ctx, ctx->segoff, ((size_t)nrec + 1) * 8))) return rc;
-            launch_seg_count_dec(da.slen, da.qlen, nrec, seg_len, (u32*)ctx->segn.p, st);
-            launch_scan_u32((const u32*)ctx->segn.p, (u64*)ctx->segoff.p, nrec, (u64*)ctx->scan_tmp.p, st);
-            std::vector<u64> h_off((size_t)nrec + 1);
-            HIPC(hipMemcpyAsync(h_off.data(), ctx->segoff.p, ((size_t)nrec + 1) * 8, hipMemcpyDeviceToHost, st));
+            // (of the records [0, wr1): the chains are numbered over the call)
+            if ((rc = reserve(ctx, ctx->segn, (size_t)wr1 * 4))) return rc;
+            if ((rc = reserve(ctx, ctx->segoff, ((size_t)wr1 + 1) * 8))) return rc;
+            launch_seg_count_dec(da.slen, da.qlen, wr1, seg_len, (u32*)ctx->segn.p, st);
+            launch_scan_u32((const u32*)ctx->segn.p, (u64*)ctx->segoff.p, wr1, (u64*)ctx->scan_tmp.p, st);
+            std::vector<u64> h_off((size_t)wr1 + 1);
+            HIPC(hipMemcpyAsync(h_off.data(), ctx->segoff.p, ((size_t)wr1 + 1) * 8, hipMemcpyDeviceToHost, st));
             HIPC(hipStreamSynchronize(st));
-            for (u32 b = 0; b <= nblocks; b++)
-                if (h_off[std::min<u64>((u64)b * block_reads, nrec)] != seg_c0[b]) return fail(ctx, SFQ_E_CORRUPT, "chain index: block %u's segments disagree with its records' line lengths", b);
+            for (u32 b = 0; b <= wb1; b++)
+                if (h_off[std::min<u64>((u64)b * block_reads, wr1)] != seg_c0[b]) return fail(ctx, SFQ_E_CORRUPT, "chain index: block %u's segments disagree with its records' line lengths", b);
             if ((rc = reserve(ctx, ctx->segrec, (size_t)nchains * 4 + 16))) return rc;
-            launch_seg_fill((const u64*)ctx->segoff.p, nrec, (u32*)ctx->segrec.p, st);
+            launch_seg_fill((const u64*)ctx->segoff.p, wr1, (u32*)ctx->segrec.p, st);
             ca.seg_len = seg_len; ca.seg_off = (const u64*)ctx->segoff.p; ca.seg_rec = (const u32*)ctx->segrec.p;
         }
         auto chain0_of = [&](u32 b) -> u32 { return seg_len ? seg_c0[b] : (u32)std::min<u64>((u64)b * cpb, nchains); };
@@ -2359,8 +2401,9 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
         ca.q_hot = 0; ca.q_rows = q_rows;
         // the coarse lists of the contexts that carry the most weight live in LDS (chains.hip launch_hot_rows_dec); automatic where the
         // call has chains for a 1024-lane workgroup on most CUs (as the encoder's image); sfq_params.lds_rows: a number, or none
+        const u32 qc0 = chain0_of(wb0), qc1 = chain0_of(wb1);          // the quality chains of the window: the only ones decoded
         const u32 want_hot = p.lds_rows == SFQ_LDS_ROWS_NONE ? 0u : p.lds_rows ? std::min<u32>(p.lds_rows, hot_rows_dec_max())
-                             : nchains >= 150000u ? hot_rows_dec_max() : 0u;
+                             : qc1 - qc0 >= 150000u ? hot_rows_dec_max() : 0u;
         if (want_hot) {
             const size_t img_bytes = (size_t)q_rows / 4 + (size_t)want_hot * 16 + 64;       // chains.hip QHD_ROW_U16
             if ((rc = reserve(ctx, ctx->qw, img_bytes + (size_t)q_rows * 4 + 256))) return rc;
@@ -2370,15 +2413,14 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
         }
         ca.csz = (u32*)ctx->csz.p; ca.coff = (const u64*)ctx->coff.p;
         if ((rc = fork_streams())) return rc;
-        launch_qlt_decode_c(ca, da, st);
+        launch_qlt_decode_c(ca, da, qc0, qc1, st);
+        if (win.ranged) res->n_chains = qc1 - qc0;
         HIPC(hipEventRecord(ctx->ev[ED_QLT_END], st));
         if ((rc = rest_of_lists(st_gen, st_rec))) return rc;
         HIPC(hipEventRecord(ctx->ev[ED_GEN_BEGIN], st_gen));
         // bases: generation by generation -- a generation's rows come from the counts of everything decoded before it
         ca.csz = (u32*)ctx->csz.p + nchains; ca.coff = (const u64*)ctx->coff.p + nchains;
         ca.st_buf = da.seq_stage; ca.st_bytes = tot_s; ca.st_off = da.soff; ca.st_len = da.slen;
-        u32 bound[GEN_MAX_GENERATIONS + 1];
-        const u32 ngen = gen_bounds(nblocks, bound);
         if (gm_on) {
             // the match model: generation by generation, each indexed behind its chains (gm.hip)
             if (ngen < 3) return fail(ctx, SFQ_E_CORRUPT, "chain index: the match model on a call of %u generations", ngen);
@@ -2386,12 +2428,12 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
             HIPC(hipMemsetAsync(ctx->gm_T.p, 0xFF, (size_t)8 << gm_tb, st_gen));
             ca.geo.chain_reads = gchain_reads; ca.geo.cpb = gcpb; ca.geo.nchains = ngc;        // (the base chains' own geometry; nothing behind this reads the quality chains')
             auto gchain0_of = [&](u32 b) -> u32 { return seg_len ? seg_c0[b] : (u32)std::min<u64>((u64)b * gcpb, ngc); };
-            for (u32 g = 0; g < ngen; g++) {
-                launch_gm_decode_c(ca, da, gchain0_of(bound[g]), gchain0_of(bound[g + 1]), (u64)bound[g] * block_reads, (const u64*)ctx->gm_T.p, gm_tb, tot_s, st_gen);
-                if (g + 1 < ngen) launch_gm_insert(ca, bound[g], bound[g + 1], (u64)(bound[g + 1] - bound[g]) * block_reads, dec_max_line, (u64*)ctx->gm_T.p, gm_tb, st_gen);
+            for (u32 g = 0; g <= G; g++) {                  // (the whole call: G = ngen - 1, every generation in full)
+                launch_gm_decode_c(ca, da, gchain0_of(gen_lo(g)), gchain0_of(gen_hi(g)), (u64)bound[g] * block_reads, (const u64*)ctx->gm_T.p, gm_tb, tot_s, st_gen);
+                if (g < G) launch_gm_insert(ca, bound[g], bound[g + 1], (u64)(bound[g + 1] - bound[g]) * block_reads, dec_max_line, (u64*)ctx->gm_T.p, gm_tb, st_gen);
             }
         } else
-        if (!gen_on || ngen < 3) { ca.flat_quads = flat_quads; ca.flat_raw = flat_raw; launch_gen_decode_c(ca, da, 0, nchains, st_gen); }
+        if (!gen_on || ngen < 3) { ca.flat_quads = flat_quads; ca.flat_raw = flat_raw; launch_gen_decode_c(ca, da, chain0_of(wb0), chain0_of(wb1), st_gen); }
         else {
             const u64 nctx = 1ull << g_bits;
             if ((rc = reserve(ctx, ctx->gcnt, (size_t)nctx * 16))) return rc;
@@ -2403,32 +2445,40 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
             for (u32 g = 0; g <= ngen; g++) ca.g_bound[g] = bound[g];
             u32* rows = (u32*)ctx->grows.p;
             const u64 br = block_reads;
-            for (u32 g = 0; g < ngen; g++) {
+            for (u32 g = 0; g <= G; g++) {                  // (the whole call: G = ngen - 1, every generation in full)
                 // rows of generation g (two buffers in turn: a generation's rows are dead once it is decoded)
                 // (the pass that sums generation g - 1's bins has written them, below)
                 ca.g_rows[g] = g >= 2 ? rows + nctx * (g & 1) : nullptr;
                 // (generations 0 and 1 both code with the initial row: one launch -- each is a sixty-fourth of the call, a launch of
                 //  its own runs as long as ONE lane takes for its chain, 3 ms at 10 M reads)
-                if (g == 0) { ca.g_rows[1] = nullptr; launch_gen_decode_c(ca, da, chain0_of(bound[0]), chain0_of(bound[2]), st_gen); }
-                else if (g >= 2) launch_gen_decode_c(ca, da, chain0_of(bound[g]), chain0_of(bound[g + 1]), st_gen);
-                if (g + 1 < ngen) launch_gen_count_binned(ca, bound[g], bound[g + 1], (u64)(bound[g + 1] - bound[g]) * br, dec_max_line, gbins, (u32*)ctx->gcnt.p,
+                if (g == 0) {
+                    ca.g_rows[1] = nullptr;
+                    if (G >= 1 && gen_lo(1) == bound[1]) launch_gen_decode_c(ca, da, chain0_of(bound[0]), chain0_of(gen_hi(1)), st_gen);
+                    else {                                 // (a window inside generation 0 or 1)
+                        launch_gen_decode_c(ca, da, chain0_of(gen_lo(0)), chain0_of(gen_hi(0)), st_gen);
+                        if (G >= 1) launch_gen_decode_c(ca, da, chain0_of(gen_lo(1)), chain0_of(gen_hi(1)), st_gen);
+                    }
+                }
+                else if (g >= 2) launch_gen_decode_c(ca, da, chain0_of(gen_lo(g)), chain0_of(gen_hi(g)), st_gen);
+                if (g < G) launch_gen_count_binned(ca, bound[g], bound[g + 1], (u64)(bound[g + 1] - bound[g]) * br, dec_max_line, gbins, (u32*)ctx->gcnt.p,
                                                           g >= 1 ? rows + nctx * ((g + 1) & 1) : nullptr, GEN_STEP, st_gen);
             }
         }
-        if (exc_rice) launch_gen_exc_decode_r(da, nblocks, st_gen);
-        else for (u32 b0 = 0; b0 < nblocks; b0 += slots) { da.m.batch0 = b0; da.m.nbatch = std::min(slots, nblocks - b0); launch_gen_exc_decode_w(da, st_gen); }
+        // (the exceptions of the window alone: what the models read of the earlier generations is the stage without them)
+        if (exc_rice) launch_gen_exc_decode_r(da, wb0, wb1, st_gen);
+        else for (u32 b0 = wb0; b0 < wb1; b0 += slots) { da.m.batch0 = b0; da.m.nbatch = std::min(slots, wb1 - b0); launch_gen_exc_decode_w(da, st_gen); }
     } else {
     // adaptive tables: a wavefront per block (decode_w.hip); sfq_params.kernel = 1: the lane-per-block cross-check kernels
     const bool wave_dec = p.kernel == 0;
     if ((rc = fork_streams())) return rc;
-    for (u32 b0 = 0; b0 < nblocks; b0 += slots) {
-        da.m.batch0 = b0; da.m.nbatch = std::min(slots, nblocks - b0);
+    for (u32 b0 = wb0; b0 < wb1; b0 += slots) {
+        da.m.batch0 = b0; da.m.nbatch = std::min(slots, wb1 - b0);
         if (wave_dec) launch_qlt_decode_w(da, st); else launch_qlt_decode_l(da, st);
     }
     HIPC(hipEventRecord(ctx->ev[ED_QLT_END], st));
     HIPC(hipEventRecord(ctx->ev[ED_GEN_BEGIN], st_gen));
-    for (u32 b0 = 0; b0 < nblocks; b0 += slots) {
-        da.m.batch0 = b0; da.m.nbatch = std::min(slots, nblocks - b0);
+    for (u32 b0 = wb0; b0 < wb1; b0 += slots) {
+        da.m.batch0 = b0; da.m.nbatch = std::min(slots, wb1 - b0);
         launch_fill_u32((u32*)ctx->tab.g_tab.p, (u64)da.m.nbatch << g_bits, 0x03030303u, st_gen);
         // (the wave kernel's 64-entry window assumes every block of the call has the context bits it was picked for: an index
         //  that mixes them -- no encoder writes one -- goes to the lane kernel, which follows each block's own)
@@ -2447,10 +2497,13 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
     if (!hso || !hsc) return fail(ctx, SFQ_E_NOMEM, "decode: host scratch");
     if ((rc = reserve(ctx, ctx->hso, ((size_t)nstage + 1) * 8))) return rc;
     if ((rc = reserve(ctx, ctx->hsc, (size_t)nstage * 4))) return rc;
+    // the window's header chains / blocks: slices [hs0, hs1) of the staging, the only ones laid out
+    const u32 rc0 = frozen_rec ? (u32)std::min<u64>((u64)wb0 * rcpb, nsub) : 0u, rc1 = frozen_rec ? (u32)std::min<u64>((u64)wb1 * rcpb, nsub) : 0u;
+    const u32 hs0 = frozen_rec ? rc0 : wb0, hs1 = frozen_rec ? rc1 : wb1;
     for (int attempt = 0; ; attempt++) {
         u64 o = 0;
         if (frozen_rec) {
-            for (u32 c = 0; c < nsub; c++) {
+            for (u32 c = rc0; c < rc1; c++) {
                 const u32 b = c / rcpb, j = c - b * rcpb;
                 const u32 nr = std::min<u32>(rchain_reads, h_blocks[b].n_records - std::min(h_blocks[b].n_records, j * rchain_reads));
                 u64 cap = (u64)h_rhb[c] + nr + SFQ_MAX_ID_LLEN + 64;
@@ -2458,7 +2511,7 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
                 hso[c] = o; hsc[c] = (u32)cap; o += (cap + 15) & ~15ull;
             }
         } else
-        for (u32 b = 0; b < nblocks; b++) {
+        for (u32 b = wb0; b < wb1; b++) {
             const sfq_block_info& bi = h_blocks[b];
             // (hdr_bytes is what the ENCODER saw: where the reference's restoration differs from the text -- an emptied field
             //  comes back "0", SURVEY H7 -- the headers of a format-6 block come back longer, so an overflow is retried with more)
@@ -2467,15 +2520,15 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
             if (cap > 0xFFFFFFF0ull) cap = 0xFFFFFFF0ull;
             hso[b] = o; hsc[b] = (u32)cap; o += (cap + 15) & ~15ull;
         }
-        hso[nstage] = o;
+        hso[hs1] = o;
         // (all the headers together cannot outgrow the caller's buffer for the text: a damaged stream that keeps asking for more ends here)
-        if (attempt && o > 2 * out_cap + (u64)nstage * (SFQ_MAX_ID_LLEN + 96)) return fail(ctx, SFQ_E_CORRUPT, "decode: the headers do not fit the output buffer (corrupt stream)");
+        if (attempt && o > 2 * out_cap + (u64)(hs1 - hs0) * (SFQ_MAX_ID_LLEN + 96)) return fail(ctx, SFQ_E_CORRUPT, "decode: the headers do not fit the output buffer (corrupt stream)");
         if ((rc = reserve(ctx, ctx->hdr_stage, (size_t)o + 16))) return rc;
-        HIPC(hipMemcpyAsync(ctx->hso.p, hso, ((size_t)nstage + 1) * 8, hipMemcpyHostToDevice, st_rec));
-        HIPC(hipMemcpyAsync(ctx->hsc.p, hsc, (size_t)nstage * 4, hipMemcpyHostToDevice, st_rec));
+        HIPC(hipMemcpyAsync((u64*)ctx->hso.p + hs0, hso + hs0, ((size_t)(hs1 - hs0) + 1) * 8, hipMemcpyHostToDevice, st_rec));
+        HIPC(hipMemcpyAsync((u32*)ctx->hsc.p + hs0, hsc + hs0, (size_t)(hs1 - hs0) * 4, hipMemcpyHostToDevice, st_rec));
         if (attempt) {                                     // (the first time round they were cleared at the head of the call: hdr_marks_cleared)
-            HIPC(hipMemsetAsync(ctx->hoff.p, 0xFF, (size_t)nrec * 8, st_rec));
-            HIPC(hipMemsetAsync(ctx->hlen.p, 0, (size_t)nrec * 4, st_rec));
+            HIPC(hipMemsetAsync((u64*)ctx->hoff.p + wr0, 0xFF, (size_t)nrec_w * 8, st_rec));
+            HIPC(hipMemsetAsync((u32*)ctx->hlen.p + wr0, 0, (size_t)nrec_w * 4, st_rec));
         }
         da.hdr_stage = (u8*)ctx->hdr_stage.p; da.hdr_stage_off = (const u64*)ctx->hso.p; da.hdr_stage_cap = (const u32*)ctx->hsc.p;
         if (attempt) { if ((rc = advance_epoch(ctx, nblocks))) return rc; da.m.epoch_base = ctx->epoch_base; ctx->epoch_base += nblocks; }
@@ -2493,42 +2546,45 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
                 // 3.6 + 7.8 ms in kernels that found that out record by record, the longest path of their decode
                 std::vector<u32> pre_v; u32* pre = nullptr; bool any_pre = false;
                 if (!attempt) {
-                    for (u32 c = 0; c < nsub && !any_pre; c++) any_pre = (u64)h_rhb[c] > 127ull * rchain_reads;      // (a first look: usually none)
+                    for (u32 c = rc0; c < rc1 && !any_pre; c++) any_pre = (u64)h_rhb[c] > 127ull * rchain_reads;      // (a first look: usually none)
                     if (any_pre) { pre_v.assign((size_t)nsub * 2, 0u); pre = pre_v.data(); any_pre = false; }
                 }
                 u32 n_pre = 0;
                 if (pre) {
-                    for (u32 c = 0; c < nsub; c++) {
+                    for (u32 c = rc0; c < rc1; c++) {
                         const u32 b = c / rcpb, k0 = (c - b * rcpb) * rchain_reads, bn = h_blocks[b].n_records;
                         const u64 n = k0 < bn ? std::min<u64>(rchain_reads, bn - k0) : 0;
                         if (n && (u64)h_rhb[c] > 127ull * n) { pre[c] = 1; pre[nsub + c] = 2; any_pre = true; n_pre++; }
                     }
                 }
-                all_pre = n_pre == nsub;                   // every chain: the general kernel alone is launched (below)
+                all_pre = n_pre == rc1 - rc0;              // every chain: the general kernel alone is launched (below)
                 if (any_pre) { HIPC(hipMemcpyAsync(ctx->rflags.p, pre, (size_t)nsub * 8, hipMemcpyHostToDevice, st_rec)); HIPC(hipStreamSynchronize(st_rec)); }      // (pre_v is a local)
                 else HIPC(hipMemsetAsync(ctx->rflags.p, 0, (size_t)nsub * 4 * 2, st_rec));
                 rflags = (u32*)ctx->rflags.p; dflags = rflags + nsub;
-                const u64 tb = (rec_dtok_bytes(nrec) + 15) & ~15ull;
-                if ((rc = reserve(ctx, ctx->rtok, (size_t)(tb + nrec * 4 + 16)))) return rc;          // tokens, then the records' places among them
-                dtok = (u32*)ctx->rtok.p; dtoff = (u32*)((u8*)ctx->rtok.p + tb);
+                // (of the window's records; the kernels index both by the call's record numbers: the pointers they get stand wr0 records in front)
+                const u64 tb = (rec_dtok_bytes(nrec_w) + 15) & ~15ull;
+                if ((rc = reserve(ctx, ctx->rtok, (size_t)(tb + nrec_w * 4 + 16)))) return rc;          // tokens, then the records' places among them
+                dtok = (u32*)ctx->rtok.p - rec_dtok_bytes(wr0) / 4; dtoff = (u32*)((u8*)ctx->rtok.p + tb) - wr0;
             }
-            if (all_pre) launch_rec_decode_c(cr, da, nullptr, st_rec, nullptr, nullptr, nullptr);
-            else launch_rec_decode_c(cr, da, rflags, st_rec, dtok, dtoff, dflags);
+            if (rc1 > rc0) {
+                if (all_pre) launch_rec_decode_c(cr, da, nullptr, st_rec, nullptr, nullptr, nullptr, rc0, rc1);
+                else launch_rec_decode_c(cr, da, rflags, st_rec, dtok, dtoff, dflags, rc0, rc1);
+            }
         } else
-        for (u32 b0 = 0; b0 < nblocks; b0 += slots) {
-            da.m.batch0 = b0; da.m.nbatch = std::min(slots, nblocks - b0);
+        for (u32 b0 = wb0; b0 < wb1; b0 += slots) {
+            da.m.batch0 = b0; da.m.nbatch = std::min(slots, wb1 - b0);
             if (p.kernel == 0) launch_rec_decode_w(da, st_rec); else launch_rec_decode_l(da, st_rec);
         }
         HIPC(hipStreamSynchronize(st_rec));
         HIPC(hipStreamSynchronize(st));
         HIPC(hipMemcpyAsync(hb, ctx->blocks.p, (size_t)nblocks * sizeof(BlockDesc), hipMemcpyDeviceToHost, st));
         HIPC(hipStreamSynchronize(st));
-        bool overflow = false; int worst = 0;
+        bool overflow = false; int worst = 0; u32 worst_b = 0;
         for (u32 b = 0; b < nblocks; b++) {
             if (hb[b].status == (u32)(-SFQ_E_OVERFLOW) && !frozen_rec) overflow = true;
-            else if (hb[b].status) worst = std::max<int>(worst, (int)hb[b].status);
+            else if ((int)hb[b].status > worst) { worst = (int)hb[b].status; worst_b = b; }
         }
-        if (worst) return fail(ctx, -worst, "decode: block kernel reported error %d (corrupt or truncated stream)", -worst);
+        if (worst) return fail(ctx, -worst, "decode: block %u: kernel reported error %d (corrupt or truncated stream)", worst_b, -worst);
         if (!overflow) break;
         if (attempt >= 8) return fail(ctx, SFQ_E_OVERFLOW, "decode: header staging overflow");
         for (u32 b = 0; b < nblocks; b++) hb[b].status = 0;
@@ -2538,12 +2594,13 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
     HIPC(hipEventRecord(ctx->ev[ED_REC_END], st));
 
     // 4. lay the records out
-    launch_record_sizes(da, nrec, (u32*)ctx->rsize.p, st);
+    // (the window's records; the scan starts at its first one, so record r lies at roff[r] - roff[wr0] = roff[r] of the output)
+    launch_record_sizes(da, wr0, wr1, (u32*)ctx->rsize.p, st);
     u64 total = 0;
     const u64* d_roff = (const u64*)ctx->roff.p;
     if (!n_over) {
-        launch_scan_u32((const u32*)ctx->rsize.p, (u64*)ctx->roff.p, nrec, (u64*)ctx->scan_tmp.p, st);
-        HIPC(hipMemcpyAsync(&total, (u64*)ctx->roff.p + nrec, 8, hipMemcpyDeviceToHost, st));
+        launch_scan_u32((const u32*)ctx->rsize.p + wr0, (u64*)ctx->roff.p + wr0, nrec_w, (u64*)ctx->scan_tmp.p, st);
+        HIPC(hipMemcpyAsync(&total, (u64*)ctx->roff.p + wr1, 8, hipMemcpyDeviceToHost, st));
     } else {                                               // every record of the file in file order: the kept ones' sizes, the oversize ones' raw lines
         HIPC(hipStreamWaitEvent(st, ctx->ev[ED_OVER_LINES_END], 0));
         if ((rc = reserve(ctx, ctx->osize_all, (size_t)nrec_file * 4))) return rc;
@@ -2563,27 +2620,27 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
     if (total > out_cap) return fail(ctx, SFQ_E_OVERFLOW, "decoded text needs %llu bytes, caller gave %llu", (unsigned long long)total, (unsigned long long)out_cap);
     ht.mark("sizes known");
     const bool crc_pass = ctx->crc_on || expect;
-    if (crc_pass && (rc = crc_reserve(ctx, d_out, 0, total, nblocks))) return rc;
-    launch_assemble(da, nrec, d_roff, d_out, st);
+    if (crc_pass && (rc = crc_reserve(ctx, d_out, 0, total, win.n))) return rc;
+    launch_assemble(da, wr0, wr1, d_roff, d_out, st);
     if (n_over) launch_over_place(n_over, (const u64*)ctx->ono.p, (const u64*)ctx->opiece.p, (const u8*)ctx->otxt[0].p, (const u8*)ctx->otxt[1].p, (const u8*)ctx->otxt[2].p,
                                   (const u64*)ctx->oroff_all.p, d_out, st);
     HIPC(hipEventRecord(ctx->ev[ED_END], st));
     if (crc_pass) {                                        // checksums: the output blocks end where the next block's first record starts
-        launch_crc_block_bounds(d_roff, block_reads, nblocks, total, (u64*)ctx->crc_bounds.p, st);
-        if ((rc = crc_queue(ctx, d_out, total, nblocks, st))) return rc;
+        launch_crc_block_bounds(d_roff + wr0, block_reads, win.n, total, (u64*)ctx->crc_bounds.p, st);       // (the window's blocks, from its first record on)
+        if ((rc = crc_queue(ctx, d_out, total, win.n, st))) return rc;
     }
     HIPC(hipStreamSynchronize(st));
     ht.mark("assembled");
     if (crc_pass) {
-        crc_take(ctx, nblocks);
+        crc_take(ctx, win.n);
         if (expect)
-            for (u32 b = 0; b < nblocks; b++)
-                if (ctx->crcs[b] != expect[b])
+            for (u32 b = wb0; b < wb1; b++)
+                if (ctx->crcs[b - wb0] != expect[b - wb0])
                     return fail(ctx, SFQ_E_CORRUPT, "checksum: block %u (records %llu..%llu) decodes to text of CRC-32 %08x, the archive says %08x",
                                 b, (unsigned long long)((u64)b * block_reads), (unsigned long long)((u64)b * block_reads + h_blocks[b].n_records - 1),
-                                ctx->crcs[b], expect[b]);
+                                ctx->crcs[b - wb0], expect[b - wb0]);
     }
-    res->n_records = nrec_file; res->n_blocks = nblocks; res->total_bytes = total;
+    res->n_records = win.ranged ? nrec_w : nrec_file; res->n_blocks = win.n; res->total_bytes = total;
     res->kernel_ms[SFQ_T_USR] = ev_ms(ctx->ev[ED_BEGIN], ctx->ev[ED_HEAD_END]);
     res->kernel_ms[SFQ_T_QLT] = ev_ms(ctx->ev[ED_FORK], ctx->ev[ED_QLT_END]);
     res->kernel_ms[SFQ_T_GEN] = ev_ms(ctx->ev[ED_GEN_BEGIN], ctx->ev[ED_GEN_END]);
@@ -2593,13 +2650,13 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
     return SFQ_OK;
 }
 
-int sfq_decode_blocks_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_info* h_blocks, uint32_t n_blocks,
-                           const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
-                           const uint8_t* h_streams, uint64_t streams_bytes, const uint64_t stream_offset[SFQ_NSTREAMS],
-                           uint8_t* h_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* result) {
-    if (!ctx) return SFQ_E_ARG;
+static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_info* h_blocks, uint32_t n_blocks,
+                       const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
+                       const uint8_t* h_streams, uint64_t streams_bytes, const uint64_t stream_offset[SFQ_NSTREAMS],
+                       uint8_t* h_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* result, const Window& w) {
     const Expected ex(ctx);
     if (!h_streams || !h_out || !h_blocks || !stream_offset) return fail(ctx, SFQ_E_ARG, "null argument");
+    if (w.n == 0 || w.b0 >= n_blocks || w.n > n_blocks - w.b0) return fail(ctx, SFQ_E_ARG, "blocks %u..+%u: not a window of the call's %u blocks", w.b0, w.n, n_blocks);
     HIPC(hipSetDevice(ctx->dev));
     int rc;
     // the index is untrusted: every stream's blocks must lie inside the bytes handed over (the device entry point cannot
@@ -2613,13 +2670,58 @@ int sfq_decode_blocks_host(sfq_ctx* ctx, const sfq_params* params, const sfq_blo
     }
     if ((rc = reserve(ctx, ctx->in_stage, (size_t)streams_bytes + 16))) return rc;
     if ((rc = reserve(ctx, ctx->out_stage, (size_t)out_cap + 16))) return rc;
-    HIPC(hipMemcpyAsync(ctx->in_stage.p, h_streams, (size_t)streams_bytes, hipMemcpyHostToDevice, ctx->st));
+    if (!w.ranged) HIPC(hipMemcpyAsync(ctx->in_stage.p, h_streams, (size_t)streams_bytes, hipMemcpyHostToDevice, ctx->st));
+    else {
+        // A window: only the bytes the call reads go to the device, each range at its own offset (no offset is rebased).  What decode_body
+        // reads outside the window: under a base model the usr.* streams of every block in front and the base chains of the generations
+        // before the window's last block's; with segments the usr.* streams in front.
+        size_t cp = 0; u64 v = 0, fl = 0;
+        const std::vector<u8>& cb = ctx->chain_blob;
+        if (!cb.empty() && get_v(cb.data(), cb.size(), cp, v) && get_v(cb.data(), cb.size(), cp, fl)) {} else fl = 0;
+        u32 bound[GEN_MAX_GENERATIONS + 1];
+        const u32 ngen = gen_bounds(n_blocks, bound), wb1 = w.b0 + w.n;
+        u32 G = 0; while (bound[G + 1] < wb1) G++;
+        const bool base_prefix = (fl & CHN_GEN_ON) && ngen >= 3, segs = (fl & CHN_SEGMENTS) != 0;
+        for (int sx = 0; sx < SFQ_NSTREAMS; sx++) {
+            const bool usr = sx == SFQ_S_USR_X || sx == SFQ_S_USR_XQ || sx == SFQ_S_USR_PFG || sx == SFQ_S_USR_PFQ;
+            // blocks [0, pre) in front of the window's own [lo, wb1)
+            u32 pre = 0, lo = w.b0;
+            if (usr && (base_prefix || segs)) lo = 0;
+            else if (sx == SFQ_S_GEN && base_prefix) { pre = bound[G]; if (lo <= pre) { lo = 0; pre = 0; } }
+            u64 at = stream_offset[sx], from = at;
+            for (u32 b = 0; b <= wb1; b++) {
+                if (b == lo) from = at;
+                if ((b == pre && pre) || b == wb1) {
+                    if (at > from) HIPC(hipMemcpyAsync((u8*)ctx->in_stage.p + from, h_streams + from, (size_t)(at - from), hipMemcpyHostToDevice, ctx->st));
+                    from = at;
+                }
+                if (b < wb1) at += h_blocks[b].size[sx];
+            }
+        }
+    }
     rc = decode_device(ctx, params, h_blocks, n_blocks, h_first_hdrs, first_hdr_bytes, (const u8*)ctx->in_stage.p,
-                       stream_offset, (u8*)ctx->out_stage.p, out_cap, out_bytes, result, ex);
+                       stream_offset, (u8*)ctx->out_stage.p, out_cap, out_bytes, result, ex, w);
     if (rc) return rc;
     HIPC(hipMemcpyAsync(h_out, ctx->out_stage.p, (size_t)*out_bytes, hipMemcpyDeviceToHost, ctx->st));
     HIPC(hipStreamSynchronize(ctx->st));
     return SFQ_OK;
+}
+int sfq_decode_blocks_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_info* h_blocks, uint32_t n_blocks,
+                           const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
+                           const uint8_t* h_streams, uint64_t streams_bytes, const uint64_t stream_offset[SFQ_NSTREAMS],
+                           uint8_t* h_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* result) {
+    if (!ctx) return SFQ_E_ARG;
+    return decode_host(ctx, params, h_blocks, n_blocks, h_first_hdrs, first_hdr_bytes, h_streams, streams_bytes, stream_offset, h_out, out_cap, out_bytes, result,
+                       Window{ 0, n_blocks, false });
+}
+int sfq_decode_block_range_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_info* h_blocks, uint32_t n_blocks,
+                                const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
+                                const uint8_t* h_streams, uint64_t streams_bytes, const uint64_t stream_offset[SFQ_NSTREAMS],
+                                uint32_t first_block, uint32_t n_window,
+                                uint8_t* h_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* result) {
+    if (!ctx) return SFQ_E_ARG;
+    return decode_host(ctx, params, h_blocks, n_blocks, h_first_hdrs, first_hdr_bytes, h_streams, streams_bytes, stream_offset, h_out, out_cap, out_bytes, result,
+                       Window{ first_block, n_window, true });
 }
 
 int sfq_crc32(sfq_ctx* ctx, const uint8_t* d_data, const uint64_t* h_bounds, uint32_t n_ranges, uint32_t* h_crc) {

@@ -427,7 +427,7 @@ void launch_qlt_encode_c(const ChainArgs& a, hipStream_t st) {
 //     without branches: two masked steps, a loop only behind them (a symbol of probability below 2^-16);
 //   * stream bytes come through a 64-bit shift register topped up four bytes at a time, the next four always in flight.
 template <int THREADS, bool LDS>
-__global__ __launch_bounds__(THREADS) void k_qlt_decode_c(ChainArgs a, DecodeArgs da) {
+__global__ __launch_bounds__(THREADS) void k_qlt_decode_c(ChainArgs a, DecodeArgs da, u32 c0, u32 c1 /* the chains [c0, c1) */) {
     extern __shared__ u32 lds[];                              // the decoder's image: map, then the staged contexts' coarse lists
     const uint2* const lmap = reinterpret_cast<const uint2*>(lds);
     const u16* const lrows = reinterpret_cast<const u16*>(lds + QH_MAP_BYTES(a.q_rows) / 4u);
@@ -437,8 +437,8 @@ __global__ __launch_bounds__(THREADS) void k_qlt_decode_c(ChainArgs a, DecodeArg
         for (u32 i = threadIdx.x; i < nd; i += THREADS) lds[i] = src[i];
         __syncthreads();
     }
-    const u32 c = blockIdx.x * THREADS + threadIdx.x;
-    if (c >= a.geo.nchains) return;
+    const u32 c = c0 + blockIdx.x * THREADS + threadIdx.x;
+    if (c >= c1) return;
     LaneDecQ rc; rc.init(da.streams + a.coff[c], a.csz[c], reinterpret_cast<const u8*>(a.qesc));
     const int level = a.m.level;
     const u32 mask12 = level == 1 ? 0xFFFu : 0xFFFFu;
@@ -521,16 +521,19 @@ __global__ __launch_bounds__(THREADS) void k_qlt_decode_c(ChainArgs a, DecodeArg
     }
     if (rc.err) atomicMax(&a.m.blocks[cp.b].status, (u32)(-SFQ_E_CORRUPT));
 }
-void launch_qlt_decode_c(const ChainArgs& a, const DecodeArgs& da, hipStream_t st) {
+// the quality chains [c0, c1): a window of the call's blocks (api.cpp sfq_decode_block_range), or all of them
+void launch_qlt_decode_c(const ChainArgs& a, const DecodeArgs& da, u32 c0, u32 c1, hipStream_t st) {
+    if (c1 > a.geo.nchains) c1 = a.geo.nchains;
+    if (c1 <= c0) return;
     if (a.q_hot) {
         constexpr int T = 1024;                                // one workgroup per CU shares the image
         const u32 dyn = QH_MAP_BYTES(a.q_rows) + a.q_hot * QHD_ROW_U16 * 2u;
         static u32 allowed = 0;
         if (dyn > allowed) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_qlt_decode_c<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); allowed = dyn; }
-        hipLaunchKernelGGL((k_qlt_decode_c<T, true>), dim3((a.geo.nchains + T - 1) / T), dim3(T), dyn, st, a, da);
+        hipLaunchKernelGGL((k_qlt_decode_c<T, true>), dim3((c1 - c0 + T - 1) / T), dim3(T), dyn, st, a, da, c0, c1);
     } else {
         constexpr int T = 256;
-        hipLaunchKernelGGL((k_qlt_decode_c<T, false>), dim3((a.geo.nchains + T - 1) / T), dim3(T), 0, st, a, da);
+        hipLaunchKernelGGL((k_qlt_decode_c<T, false>), dim3((c1 - c0 + T - 1) / T), dim3(T), 0, st, a, da, c0, c1);
     }
 }
 
@@ -2154,9 +2157,9 @@ struct RecFrozenDec {
     __device__ __forceinline__ u32 err() const { return rc.err; }
 };
 // general path: one chain per lane; with `flags` only the chains the fast kernel below has handed over
-__global__ __launch_bounds__(64) void k_rec_decode_c(ChainArgs a, DecodeArgs da, const u32* flags) {
-    const u32 c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.rgeo.nchains) return;
+__global__ __launch_bounds__(64) void k_rec_decode_c(ChainArgs a, DecodeArgs da, const u32* flags, u32 c0, u32 c1 /* the header chains [c0, c1) */) {
+    const u32 c = c0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= c1) return;
     if (flags && !flags[c]) return;
     const RecChainPos cp = rec_chain_pos(a, c);
     BlockDesc* d = &da.m.blocks[cp.b];
@@ -2308,19 +2311,19 @@ __device__ __forceinline__ bool rec_fast_decode_lane(const DecodeArgs& a, const 
     out.end();
     return true;
 }
-__global__ __launch_bounds__(64) void k_rec_decode_f(ChainArgs a, DecodeArgs da, u32* flags, const u32* only /* the chains to take; null = all */) {
+__global__ __launch_bounds__(64) void k_rec_decode_f(ChainArgs a, DecodeArgs da, u32* flags, const u32* only /* the chains to take; null = all */, u32 cw0, u32 cw1 /* the header chains [cw0, cw1) */) {
     __builtin_amdgcn_s_setprio(3);         // (a wave per SIMD with a long serial walk beside the quality decoder's many: 19.2 -> 16.2 ms)
     __shared__ RecFastDecLds L;
     const u32 lane = threadIdx.x;
     {
-        const u32 c0 = blockIdx.x * 64 + lane;
-        if (only && !__any(c0 < a.rgeo.nchains && only[c0] == 1)) return;      // (2: marked by the host for the general kernel, its flag set there)
+        const u32 c0 = cw0 + blockIdx.x * 64 + lane;
+        if (only && !__any(c0 < cw1 && only[c0] == 1)) return;      // (2: marked by the host for the general kernel, its flag set there)
     }
     for (u32 i = lane; i < PR_REC_ROWS; i += 64) { const u32 sl = a.rmap[i]; L.map[i] = (u8)(sl < RDEC_LDS_ROWS ? sl : 0xFFu); }
     for (u32 i = lane; i < a.r_hot * RDEC_ROW; i += 64) L.drows[i / RDEC_ROW][i % RDEC_ROW] = a.rdec[(size_t)a.rhot[i / RDEC_ROW] * RDEC_ROW + i % RDEC_ROW];
     __syncthreads();
-    const u32 c = blockIdx.x * 64 + lane;
-    if (c >= a.rgeo.nchains) return;
+    const u32 c = cw0 + blockIdx.x * 64 + lane;
+    if (c >= cw1) return;
     if (only && only[c] != 1) return;
     const RecChainPos cp = rec_chain_pos(a, c);
     const BlockDesc* d = &da.m.blocks[cp.b];
@@ -2355,13 +2358,13 @@ struct RecSymSrc {
     }
     __device__ __forceinline__ u64 get_u(u32 row0) { return get_u_rows(*this, row0); }
 };
-__global__ __launch_bounds__(256) void k_rec_dsym(ChainArgs a, DecodeArgs da, u32* __restrict__ dtok, u32* __restrict__ dtoff, u32* __restrict__ dflags) {
+__global__ __launch_bounds__(256) void k_rec_dsym(ChainArgs a, DecodeArgs da, u32* __restrict__ dtok, u32* __restrict__ dtoff, u32* __restrict__ dflags, u32 c0, u32 c1 /* the header chains [c0, c1) */) {
     __shared__ RecDsymLds L;
     for (u32 i = threadIdx.x; i < PR_REC_ROWS; i += 256) { const u32 sl = a.rmap[i]; L.map[i] = (u8)(sl < RDEC_LDS_ROWS ? sl : 0xFFu); }
     for (u32 i = threadIdx.x; i < a.r_hot * RDEC_ROW; i += 256) L.drows[i / RDEC_ROW][i % RDEC_ROW] = a.rdec[(size_t)a.rhot[i / RDEC_ROW] * RDEC_ROW + i % RDEC_ROW];
     __syncthreads();
-    const u32 c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= a.rgeo.nchains) return;
+    const u32 c = c0 + blockIdx.x * 256 + threadIdx.x;
+    if (c >= c1) return;
     if (dflags[c]) return;                                  // (marked by the host: headers too long for the two steps, api.cpp)
     const RecChainPos cp = rec_chain_pos(a, c);
     const BlockDesc* d = &da.m.blocks[cp.b];
@@ -2425,10 +2428,10 @@ struct RecDtLds {
     u8 csep[RF_NF];                                                     // the separators: the same for every record of a chain without shape changes
     u64 cval[RF_NF];                                                    // the fields' running values behind that record (0: cold, or a string since)
 };
-__global__ __launch_bounds__(64) void k_rec_dtext(ChainArgs a, DecodeArgs da, const u32* __restrict__ dtok, const u32* __restrict__ dtoff, u32* __restrict__ dflags) {
+__global__ __launch_bounds__(64) void k_rec_dtext(ChainArgs a, DecodeArgs da, const u32* __restrict__ dtok, const u32* __restrict__ dtoff, u32* __restrict__ dflags, u32 c0 /* the grid's first chain */) {
     __shared__ RecDtLds L;
     const u32 lane = threadIdx.x;
-    const u32 c = blockIdx.x;
+    const u32 c = c0 + blockIdx.x;
     if (dflags[c]) return;
     const RecChainPos cp = rec_chain_pos(a, c);
     if (cp.nrec == 0) return;
@@ -2594,16 +2597,20 @@ __global__ __launch_bounds__(64) void k_rec_dtext(ChainArgs a, DecodeArgs da, co
     }
 }
 // flags: one dword per header chain, zeroed by the caller (null: every chain on the general path -- archives before version 5)
-void launch_rec_decode_c(const ChainArgs& a, const DecodeArgs& da, u32* flags, hipStream_t st, u32* dtok, u32* dtoff, u32* dflags) {
-    const dim3 grid((a.rgeo.nchains + 63) / 64);
+// the header chains [c0, c1) (c1 = 0: all of them); flags / dflags / dtoff are indexed by the call's chains and records, dtok by the record
+void launch_rec_decode_c(const ChainArgs& a, const DecodeArgs& da, u32* flags, hipStream_t st, u32* dtok, u32* dtoff, u32* dflags, u32 c0, u32 c1) {
+    if (!c1 || c1 > a.rgeo.nchains) c1 = a.rgeo.nchains;
+    if (c1 <= c0) return;
+    const u32 n = c1 - c0;
+    const dim3 grid((n + 63) / 64);
     if (flags && dtok) {                                                 // symbols, texts, then the lane kernels on the chains those left (dflags)
-        hipLaunchKernelGGL(k_rec_dsym, dim3((a.rgeo.nchains + 255) / 256), dim3(256), 0, st, a, da, dtok, dtoff, dflags);
-        hipLaunchKernelGGL(k_rec_dtext, dim3(a.rgeo.nchains), dim3(64), 0, st, a, da, (const u32*)dtok, (const u32*)dtoff, dflags);
-        hipLaunchKernelGGL(k_rec_decode_f, grid, dim3(64), 0, st, a, da, flags, (const u32*)dflags);
-        hipLaunchKernelGGL(k_rec_decode_c, grid, dim3(64), 0, st, a, da, (const u32*)flags);
+        hipLaunchKernelGGL(k_rec_dsym, dim3((n + 255) / 256), dim3(256), 0, st, a, da, dtok, dtoff, dflags, c0, c1);
+        hipLaunchKernelGGL(k_rec_dtext, dim3(n), dim3(64), 0, st, a, da, (const u32*)dtok, (const u32*)dtoff, dflags, c0);
+        hipLaunchKernelGGL(k_rec_decode_f, grid, dim3(64), 0, st, a, da, flags, (const u32*)dflags, c0, c1);
+        hipLaunchKernelGGL(k_rec_decode_c, grid, dim3(64), 0, st, a, da, (const u32*)flags, c0, c1);
         return;
     }
-    if (flags) hipLaunchKernelGGL(k_rec_decode_f, grid, dim3(64), 0, st, a, da, flags, (const u32*)nullptr);
-    hipLaunchKernelGGL(k_rec_decode_c, grid, dim3(64), 0, st, a, da, (const u32*)flags);
+    if (flags) hipLaunchKernelGGL(k_rec_decode_f, grid, dim3(64), 0, st, a, da, flags, (const u32*)nullptr, c0, c1);
+    hipLaunchKernelGGL(k_rec_decode_c, grid, dim3(64), 0, st, a, da, (const u32*)flags, c0, c1);
 }
 u64 rec_dtok_bytes(u64 nrec) { return nrec * RD_TOK_PER_REC * 4; }

@@ -7,11 +7,13 @@
 //               frozen tables (rows built by counting passes, one chain per GPU lane)
 //   -g dev    : HIP device
 //   -K        : store the CRC-32 of every block's text ("blk.crc") and of the file (info key "crc32"); a decode checks them
+//   -R F:N    : with -d: records F .. F + N - 1 only (numbered from 0 over the archive) -- the blocks that hold them are decoded, no others
 // All model / coder work happens in libslimfastq_amd.so on the GPU; this file parses arguments, reads and
 // writes files and fills the info page.
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <cerrno>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -83,6 +85,9 @@ static void usage() {
            "-C reads         : frozen tables: records per chain (default: automatic)\n"
            "-K               : checksums: store the CRC-32 of every block's text and of the whole file (computed on the GPU);\n"
            "                   decoding checks them and fails on a mismatch (needs the block format: not with -B 0)\n"
+           "-R first:count   : with -d: write records first .. first+count-1 only (numbered from 0 over the whole archive; count is\n"
+           "                   clipped at the end): only the blocks that hold them are decoded (and, under a base model, what the\n"
+           "                   format makes them depend on); with -b: of every job\n"
            "-S mbytes        : input is compressed in slabs of this many MiB, one archive segment each (default 512 for a\n"
            "                   regular file, read ahead while the GPU codes the slab before; 2048 for a pipe)\n"
            "-t threads       : threads reading a slab (default 6)\n"
@@ -112,7 +117,30 @@ struct Opts {
     bool force_frozen = false;                                         // -F
     long chain_reads = 0;                                              // -C
     bool checksum = false;                                             // -K
+    bool range = false; uint64_t r_first = 0, r_count = 0;             // -R first:count
 };
+// "FIRST:COUNT", both decimal, COUNT > 0
+static bool parse_range(const char* t, uint64_t& first, uint64_t& count) {
+    if (!t || *t < '0' || *t > '9') return false;
+    char* e = nullptr;
+    errno = 0;
+    const unsigned long long f = strtoull(t, &e, 10);
+    if (errno || !e || *e != ':' || e[1] < '0' || e[1] > '9') return false;
+    char* e2 = nullptr;
+    const unsigned long long c = strtoull(e + 1, &e2, 10);
+    if (errno || !e2 || *e2 || !c) return false;
+    first = f; count = c;
+    return true;
+}
+// where the first `skip` records (four lines each) of a text end, or n where it has fewer
+static size_t records_end(const uint8_t* t, size_t n, uint64_t skip) {
+    size_t at = 0;
+    for (uint64_t l = 0; l < 4 * skip && at < n; l++) {
+        const void* q = memchr(t + at, '\n', n - at);
+        at = q ? (size_t)((const uint8_t*)q - t) + 1 : n;
+    }
+    return at;
+}
 
 // Growable byte buffer that never zero-fills (a std::vector would touch gigabytes just to size them).
 struct Bytes {
@@ -468,6 +496,13 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         blocks.push_back(b);
         segs.push_back(sfqc::Segment{1, 0, (uint64_t)a.get_long("orig.size", 0), 0, 0});
     }
+    // -R: records [r_lo, r_hi) of the archive
+    uint64_t r_lo = 0, r_hi = 0;
+    if (o.range) {
+        const uint64_t total = blocks.back().first_record + blocks.back().n_records;
+        if (o.r_first >= total) croak("-R %llu:%llu: the archive holds %llu records", (unsigned long long)o.r_first, (unsigned long long)o.r_count, (unsigned long long)total);
+        r_lo = o.r_first; r_hi = o.r_count > total - r_lo ? total : r_lo + o.r_count;
+    }
     FILE* of = stdout;
     if (!usr.empty()) {
         if (!o.overwrite && access(usr.c_str(), F_OK) == 0) {
@@ -492,7 +527,7 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     // several segments of known size: the text of one is written (a thread) while the next is decoded, out of two
     // page-locked buffers (kept for the life of the process, like the encoder's)
     static uint8_t* opin[2] = { nullptr, nullptr }; static size_t opin_cap = 0;
-    size_t max_raw = 0; bool sized = segs.size() > 1;
+    size_t max_raw = 0; bool sized = segs.size() > 1 && !o.range;
     for (const sfqc::Segment& g : segs) { max_raw = std::max<size_t>(max_raw, (size_t)g.raw_bytes); if (!g.raw_bytes) sized = false; }
     if (sized && opin_cap < max_raw + 64) {
         for (auto& q : opin) { if (q) sfq_host_free(ctx, q); q = nullptr; }
@@ -513,9 +548,22 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         uint64_t need[SFQ_NSTREAMS] = {0}, hbytes = 0;
         for (auto& b : sb) { b.first_record -= rec0; b.first_hdr_off -= h0; hbytes += b.first_hdr_len; for (int s = 0; s < SFQ_NSTREAMS; s++) need[s] += b.size[s]; }
         if (h0 + hbytes > first.size()) croak("bad block index (first headers)");
+        // -R: the segment's blocks that hold records of the range; a segment without any is passed over (its priors still count for a
+        // later segment that shares them)
+        uint32_t w0 = 0, wn = (uint32_t)sb.size();
+        bool touched = true;
+        if (o.range) {
+            const uint64_t seg_end = rec0 + sb.back().first_record + sb.back().n_records, br = sb[0].n_records;
+            touched = r_lo < seg_end && r_hi > rec0 && br;
+            if (touched) {
+                const uint64_t lo = std::max(r_lo, rec0) - rec0, hi = std::min(r_hi, seg_end) - rec0;
+                w0 = (uint32_t)(lo / br); wn = (uint32_t)((hi - 1) / br) - w0 + 1;
+            }
+        }
+        if (!touched) for (int s = 0; s < SFQ_NSTREAMS; s++) spos[s] += need[s];
         data.clear();
         uint64_t soff[SFQ_NSTREAMS];
-        for (int s = 0; s < SFQ_NSTREAMS; s++) {
+        for (int s = 0; touched && s < SFQ_NSTREAMS; s++) {
             soff[s] = data.size();
             if (!need[s]) continue;
             const std::vector<uint8_t>* v = a.find(sfq_stream_name(s));
@@ -529,12 +577,17 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         if (sfq_set_chain_index(ctx, g.chain_bytes ? chn->data() + chn_off : nullptr, g.chain_bytes)) croak("%s", sfq_last_error(ctx));
         if (g.recpri_bytes) { if (sfq_set_rec_prior(ctx, rpr->data() + rpr_off, g.recpri_bytes)) croak("%s", sfq_last_error(ctx)); }
         else if (!shared_prior) sfq_set_rec_prior(ctx, nullptr, 0);
+        if (!touched) { b0 += g.nblocks; pri_off += g.prior_bytes; chn_off += g.chain_bytes; rpr_off += g.recpri_bytes; continue; }
         uint64_t cap = g.raw_bytes, got = 0;
         if (!cap) cap = data.size() * 8 + (1 << 20);
+        // (a window: its share of the segment's text and as much again; the call reports what it needs where that is too little --
+        //  or, where the window's lines alone outgrow it, a damaged stream: then the segment's size is tried)
+        const uint64_t cap_seg = cap;
+        if (o.range && wn < sb.size()) cap = std::min<uint64_t>(cap_seg, cap_seg / sb.size() * wn * 2 + (1 << 20));
         sfq_result res;
         int rc = 0;
         uint8_t* dst = nullptr;
-        for (int attempt = 0; attempt < 2; attempt++) {
+        for (int attempt = 0; attempt < (o.range ? 3 : 2); attempt++) {
             if (sized && cap + 16 <= opin_cap) dst = opin[ob];
             else {
                 if (!out.reserve((size_t)cap + 16)) croak("out of memory");
@@ -542,9 +595,13 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
                 dst = out.p;
             }
             // (the expected checksums are consumed by the call they are installed for)
-            if (!crcs.empty() && sfq_set_block_checksums(ctx, crcs.data() + b0, (uint32_t)sb.size())) croak("%s", sfq_last_error(ctx));
+            if (!crcs.empty() && sfq_set_block_checksums(ctx, crcs.data() + b0 + w0, wn)) croak("%s", sfq_last_error(ctx));
+            if (o.range) rc = sfq_decode_block_range_host(ctx, &p, sb.data(), (uint32_t)sb.size(), first.data() + h0, hbytes,
+                                                          data.data(), data.size(), soff, w0, wn, dst, cap, &got, &res);
+            else
             rc = sfq_decode_blocks_host(ctx, &p, sb.data(), (uint32_t)sb.size(), first.data() + h0, hbytes,
                                         data.data(), data.size(), soff, dst, cap, &got, &res);
+            if (o.range && rc == SFQ_E_CORRUPT && cap < cap_seg) { cap = cap_seg; continue; }
             if (rc != SFQ_E_OVERFLOW || got <= cap) break;
             cap = got;                                                 // the call reports the size it needs
         }
@@ -553,9 +610,17 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
                   sfq_last_error(ctx));
         if (rc) croak("%s", sfq_last_error(ctx));
         tick("sfq_decode_blocks_host");
+        const bool in_out = dst == out.p;                              // (not a page-locked buffer: written before the next segment reuses it)
+        if (o.range) {                                                 // the window's first and last block, cut to records: four lines each
+            const uint64_t wrec0 = rec0 + (uint64_t)w0 * sb[0].n_records;
+            const uint64_t lo = std::max(r_lo, wrec0), hi = std::min(r_hi, wrec0 + res.n_records);
+            const size_t from = records_end(dst, (size_t)got, lo - wrec0);
+            const size_t to = from + records_end(dst + from, (size_t)got - from, hi - lo);
+            dst += from; got = to - from;
+        }
         writer.join();
         if (wbad) croak("USR: Error writing output");
-        if (dst == out.p) { if (fwrite(dst, 1, (size_t)got, of) != got) croak("USR: Error writing output"); }
+        if (in_out) { if (fwrite(dst, 1, (size_t)got, of) != got) croak("USR: Error writing output"); }
         else {
             writer.start([dst, got, of, &wbad]() { if (fwrite(dst, 1, (size_t)got, of) != got) wbad = 1; });
             ob ^= 1;
@@ -573,7 +638,7 @@ int main(int argc, char** argv) {
     Opts o;
     bool statistics = false;
     if (argc == 1) usage();
-    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFK1234u:f:l:B:g:S:T:C:t:")) != -1;) {
+    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFK1234u:f:l:B:g:S:T:C:t:R:")) != -1;) {
         switch (opt) {
         case 'u': g_usr = optarg; break;
         case 'f': fil = optarg; break;
@@ -592,6 +657,7 @@ int main(int argc, char** argv) {
         case 'A': o.adaptive = true; break;
         case 'F': o.force_frozen = true; break;
         case 'K': o.checksum = true; break;
+        case 'R': if (!parse_range(optarg, o.r_first, o.r_count)) usage(); o.range = true; break;
         case 'C': o.chain_reads = strtol(optarg, 0, 0); break;
         case 't': o.io_threads = std::min(64, std::max(1, atoi(optarg))); break;
         case 'v': printf("Version %s\nInternal format version=%u (block format %u)\n", kUserVersion, kInternalVersion, kBlockVersion); exit(0);
@@ -603,6 +669,11 @@ int main(int argc, char** argv) {
     o.level = clamp_level(o.level);                                    // clamp at parse time (the reference records the clamped value only)
     if (o.checksum && o.block_reads == 0) {
         fprintf(stderr, "slimfastq: -K (checksums) needs the block format: -B 0 writes the reference's own format-6 file, which has no place for them\n");
+        return 1;
+    }
+
+    if (o.range && g_encode) {
+        fprintf(stderr, "slimfastq: -R (a range of records) goes with -d: it picks what a decode writes\n");
         return 1;
     }
 

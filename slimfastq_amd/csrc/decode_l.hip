@@ -55,17 +55,17 @@ __device__ __forceinline__ u32 calc_last_delta_d(u32& delta, u32 q, u32 q1, u32 
 __device__ __forceinline__ bool usr_streams_empty(const BlockDesc* d) {
     return (d->size[SFQ_S_USR_X] | d->size[SFQ_S_USR_XQ] | d->size[SFQ_S_USR_PFG] | d->size[SFQ_S_USR_PFQ]) == 0;
 }
-__global__ __launch_bounds__(256) void k_usr_fill(DecodeArgs a, u64 nrec) {
-    const u64 r = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (r >= nrec) return;
+__global__ __launch_bounds__(256) void k_usr_fill(DecodeArgs a, u64 rec0, u64 rec1 /* the records [rec0, rec1) */) {
+    const u64 r = rec0 + (u64)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rec1) return;
     BlockDesc* d = &a.m.blocks[r / a.block_reads];
     if (!usr_streams_empty(d)) return;
     u32 llen = d->llen;
     if (llen > a.max_line) { dset_status(d, SFQ_E_CORRUPT); llen = 0; }
     a.slen[r] = llen; a.qlen[r] = llen; a.pfg[r] = 0; a.pfq[r] = 0;
 }
-void launch_usr_fill(const DecodeArgs& a, u64 nrec, hipStream_t st) {
-    if (nrec) hipLaunchKernelGGL(k_usr_fill, dim3((u32)((nrec + 255) / 256)), dim3(256), 0, st, a, nrec);
+void launch_usr_fill(const DecodeArgs& a, u64 r0, u64 r1, hipStream_t st) {
+    if (r1 > r0) hipLaunchKernelGGL(k_usr_fill, dim3((u32)((r1 - r0 + 255) / 256)), dim3(256), 0, st, a, r0, r1);
 }
 __global__ __launch_bounds__(64) void k_usr_decode_l(DecodeArgs a, u32 prefilled) {
     DSlot sl;
@@ -309,15 +309,15 @@ void launch_gen_exc_decode_l(const DecodeArgs& a, hipStream_t st) {
 }
 
 // ---- UsrLoad::save (usrs.cpp:512-535): '@'hdr \n [pf]bases \n '+'[hdr] \n [pf]quals \n --------------------
-__global__ __launch_bounds__(256) void k_record_sizes(DecodeArgs a, u64 nrec, u32* rsize) {
-    u64 r = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (r >= nrec) return;
+__global__ __launch_bounds__(256) void k_record_sizes(DecodeArgs a, u64 rec0, u64 rec1 /* the records [rec0, rec1) */, u32* rsize) {
+    u64 r = rec0 + (u64)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rec1) return;
     const BlockDesc* d = &a.m.blocks[a.block_reads ? r / a.block_reads : 0];
     const u32 h = a.hlen[r], s = d->solid;
     rsize[r] = 1 + h + 1 + s + a.slen[r] + 1 + 1 + (d->two_id ? h : 0) + 1 + s + a.qlen[r] + 1;
 }
-void launch_record_sizes(const DecodeArgs& a, u64 nrec, u32* rsize, hipStream_t st) {
-    hipLaunchKernelGGL(k_record_sizes, dim3((u32)((nrec + 255) / 256)), dim3(256), 0, st, a, nrec, rsize);
+void launch_record_sizes(const DecodeArgs& a, u64 r0, u64 r1, u32* rsize, hipStream_t st) {
+    if (r1 > r0) hipLaunchKernelGGL(k_record_sizes, dim3((u32)((r1 - r0 + 255) / 256)), dim3(256), 0, st, a, r0, r1, rsize);
 }
 // a wave copies n bytes, a dword per lane and step (global loads and stores need no alignment on gfx9), the last 0..3 singly
 __device__ __forceinline__ void wave_copy(u8* dst, const u8* src, u32 n, u32 lane) {
@@ -349,9 +349,9 @@ __device__ __forceinline__ AsmFirst asm_first(const AsmRec& r, u32 lane) {
     if (lane < qd) f.vqq = lane < md ? f.vq : *reinterpret_cast<const u32*>(r.qp + 4 * lane);
     return f;
 }
-__global__ __launch_bounds__(64) void k_assemble(DecodeArgs a, u64 nrec, u32 rpw, const u64* __restrict__ roff, u8* __restrict__ out) {
+__global__ __launch_bounds__(64) void k_assemble(DecodeArgs a, u64 rec0, u64 nrec /* the records [rec0, nrec) */, u32 rpw, const u64* __restrict__ roff, u8* __restrict__ out) {
     const u32 lane = threadIdx.x;
-    const u64 r0 = (u64)blockIdx.x * rpw;
+    const u64 r0 = rec0 + (u64)blockIdx.x * rpw;
     if (r0 >= nrec) return;
     const u32 cnt = (u32)(nrec - r0 < rpw ? nrec - r0 : rpw);
     // the bounds of record r0 + lane
@@ -413,9 +413,9 @@ __global__ __launch_bounds__(64) void k_assemble(DecodeArgs a, u64 nrec, u32 rpw
 // 3.7 GB at the end of every decode, nothing beside it.
 __device__ __forceinline__ uint4 ld16u(const u8* p) { const u32* q = reinterpret_cast<const u32*>(p); return make_uint4(q[0], q[1], q[2], q[3]); }
 __device__ __forceinline__ void st16u(u8* p, const uint4& v) { u32* q = reinterpret_cast<u32*>(p); q[0] = v.x; q[1] = v.y; q[2] = v.z; q[3] = v.w; }
-__global__ __launch_bounds__(64) void k_assemble4(DecodeArgs a, u64 nrec, u32 rpw, const u64* __restrict__ roff, u8* __restrict__ out) {
+__global__ __launch_bounds__(64) void k_assemble4(DecodeArgs a, u64 rec0, u64 nrec /* the records [rec0, nrec) */, u32 rpw, const u64* __restrict__ roff, u8* __restrict__ out) {
     const u32 lane = threadIdx.x, grp = lane >> 4, sub = lane & 15u;
-    const u64 r0 = (u64)blockIdx.x * rpw;
+    const u64 r0 = rec0 + (u64)blockIdx.x * rpw;
     if (r0 >= nrec) return;
     const u32 cnt = (u32)(nrec - r0 < rpw ? nrec - r0 : rpw);
     const u64 rl = r0 + (lane < cnt ? lane : cnt - 1);                     // the bounds of record r0 + lane, handed to the record's sixteen lanes below
@@ -496,8 +496,10 @@ __global__ __launch_bounds__(256) void k_gather_u64(const u64* __restrict__ src,
 void launch_gather_u64(const u64* src, const u32* idx, u64 n, u64* dst, hipStream_t st) {
     if (n) hipLaunchKernelGGL(k_gather_u64, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, src, idx, n, dst);
 }
-void launch_assemble(const DecodeArgs& a, u64 nrec, const u64* roff, u8* out, hipStream_t st) {
+void launch_assemble(const DecodeArgs& a, u64 r0, u64 r1, const u64* roff, u8* out, hipStream_t st) {
+    if (r1 <= r0) return;
+    const u64 nrec = r1 - r0;
     const u32 rpw = (u32)std::max<u64>(1, std::min<u64>(64, nrec / 32768));
-    if (rpw >= 4) hipLaunchKernelGGL(k_assemble4, dim3((u32)((nrec + rpw - 1) / rpw)), dim3(64), 0, st, a, nrec, rpw, roff, out);      // many records: short ones
-    else hipLaunchKernelGGL(k_assemble, dim3((u32)((nrec + rpw - 1) / rpw)), dim3(64), 0, st, a, nrec, rpw, roff, out);
+    if (rpw >= 4) hipLaunchKernelGGL(k_assemble4, dim3((u32)((nrec + rpw - 1) / rpw)), dim3(64), 0, st, a, r0, r1, rpw, roff, out);      // many records: short ones
+    else hipLaunchKernelGGL(k_assemble, dim3((u32)((nrec + rpw - 1) / rpw)), dim3(64), 0, st, a, r0, r1, rpw, roff, out);
 }

@@ -23,9 +23,9 @@
 
 // A lane per block: "gen.Ns" -> the N byte, "gen.Nn" -> bit 7 ("keep this base": decode_l.hip merge_n), "gen.lc" -> bit 5, in
 // the block's staged bases (gens.cpp:187-188)
-__global__ __launch_bounds__(64) void k_gen_exc_decode_r(DecodeArgs a, u32 nblocks) {
-    const u32 b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= nblocks) return;
+__global__ __launch_bounds__(64) void k_gen_exc_decode_r(DecodeArgs a, u32 b0w, u32 b1w /* the blocks [b0w, b1w) */) {
+    const u32 b = b0w + blockIdx.x * 64 + threadIdx.x;
+    if (b >= b1w) return;
     BlockDesc* d = &a.m.blocks[b];
     RiceR r_ns, r_nn, r_lc;
     r_ns.init(a.streams + a.blk_stream_off[(u64)b * SFQ_NSTREAMS + SFQ_S_GEN_NS], (u32)d->size[SFQ_S_GEN_NS]);
@@ -66,6 +66,6 @@ __global__ __launch_bounds__(64) void k_gen_exc_decode_r(DecodeArgs a, u32 nbloc
     for (u64 gap = r_lc.get(); gap; gap = r_lc.get()) { at += gap; if (at > nb) { bad = 1; break; } *place(at) |= 0x20u; }
     if (bad | r_ns.err | r_nn.err | r_lc.err) atomicMax(&d->status, (u32)(-SFQ_E_CORRUPT));
 }
-void launch_gen_exc_decode_r(const DecodeArgs& a, u32 nblocks, hipStream_t st) {
-    if (nblocks) hipLaunchKernelGGL(k_gen_exc_decode_r, dim3((nblocks + 63) / 64), dim3(64), 0, st, a, nblocks);
+void launch_gen_exc_decode_r(const DecodeArgs& a, u32 b0, u32 b1, hipStream_t st) {
+    if (b1 > b0) hipLaunchKernelGGL(k_gen_exc_decode_r, dim3((b1 - b0 + 63) / 64), dim3(64), 0, st, a, b0, b1);
 }

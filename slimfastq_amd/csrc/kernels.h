@@ -142,7 +142,7 @@ void launch_chain_index_bytes(const u32* csz, u32 n, u32 b1, u32 b2, u32 b3, u32
 void launch_gen_exc_w(const ModelArgs& a, const u8* flags, u32* ticket, hipStream_t st);
 // the same lists as adaptive Rice codes (models_w.hip k_gen_exc_w<true>, dev_rice.h; frozen tables, "chn.idx" flag CHN_EXC_RICE) and the way back, a lane per block (exc.hip)
 void launch_gen_exc_r(const ModelArgs& a, const u8* flags, u32* ticket, hipStream_t st);
-void launch_gen_exc_decode_r(const struct DecodeArgs& a, u32 nblocks, hipStream_t st);
+void launch_gen_exc_decode_r(const struct DecodeArgs& a, u32 b0, u32 b1 /* blocks [b0, b1) */, hipStream_t st);
 #define REC_COUNT_COPIES 32u        // the header prior's counting pass counts into this many copies of the table (chains.hip k_rec_count_sum)
 void launch_rec_count(const ModelArgs& a, u64 nrec, u64 stride, u32 run, u32 nruns, u32* cnt /* [REC_COUNT_COPIES][PR_REC_ROWS][256], zeroed; the sums end up in copy 0 */,
                       u32* flags /* [nruns], zeroed */, hipStream_t st);
@@ -215,16 +215,17 @@ void launch_gen_encode_k(const ModelArgs& a, u32* ticket, hipStream_t st);
 void launch_rec_encode_w(const ModelArgs& a, u32* ticket_fast, u32* ticket_slow, hipStream_t st);
 void launch_usr_encode_w(const ModelArgs& a, hipStream_t st);      // framing exceptions, a wave per block; blocks [batch0, batch0 + nbatch), slot = workgroup
 
-void launch_qlt_decode_c(const ChainArgs& a, const DecodeArgs& da, hipStream_t st);
+void launch_qlt_decode_c(const ChainArgs& a, const DecodeArgs& da, u32 c0, u32 c1 /* chains [c0, c1) */, hipStream_t st);
 void launch_gen_decode_c(const ChainArgs& a, const DecodeArgs& da, u32 c0, u32 c1 /* chains [c0, c1) */, hipStream_t st);
 void launch_rec_decode_c(const ChainArgs& a, const DecodeArgs& da, u32* flags /* [rgeo.nchains], zeroed; null = general path only */, hipStream_t st,
-                         u32* dtok = nullptr /* rec_dtok_bytes(records); null = the lane kernels alone */, u32* dtoff = nullptr /* [records] */, u32* dflags = nullptr /* [rgeo.nchains], zeroed */);
+                         u32* dtok = nullptr /* rec_dtok_bytes(records); null = the lane kernels alone */, u32* dtoff = nullptr /* [records] */, u32* dflags = nullptr /* [rgeo.nchains], zeroed */,
+                         u32 c0 = 0, u32 c1 = 0 /* header chains [c0, c1); 0, 0 = all */);
 u64 rec_dtok_bytes(u64 nrec);
 void launch_gen_exc_decode_l(const DecodeArgs& a, hipStream_t st);          // applies gen.Ns / gen.Nn to the staged bases
 void launch_gen_exc_decode_w(const DecodeArgs& a, hipStream_t st);          // the same, a wave per block (models_w.hip); blocks [batch0, batch0 + nbatch), slot = workgroup
 void launch_usr_decode_l(const DecodeArgs& a, hipStream_t st, u32 prefilled = 0);          // prefilled: launch_usr_fill has written the blocks without framing exceptions
 void launch_usr_decode_w(const DecodeArgs& a, hipStream_t st, u32 prefilled);     // the same, a wave per block (decode_w.hip); blocks [batch0, batch0 + nbatch), slot = workgroup
-void launch_usr_fill(const DecodeArgs& a, u64 nrec, hipStream_t st);                                // block format: the records of blocks whose four usr.* streams are empty
+void launch_usr_fill(const DecodeArgs& a, u64 r0, u64 r1, hipStream_t st);                          // block format: the records [r0, r1) of blocks whose four usr.* streams are empty
 void launch_qlt_decode_l(const DecodeArgs& a, hipStream_t st);
 void launch_gen_decode_l(const DecodeArgs& a, hipStream_t st);
 void launch_rec_decode_l(const DecodeArgs& a, hipStream_t st);
@@ -238,8 +239,9 @@ void launch_block_stream_offsets(BlockDesc* blocks, u32 nblocks, u64* blk_stream
 void launch_compact(const BlockDesc* blocks, u32 nblocks, const u8* arena, const u64* blk_stream_off,
                     const u64* stream_base, u8* out, u32 skip_streams /* bit s: stream s is packed by launch_compact_chains */, hipStream_t st, const u32* gate);
 void launch_stream_gate(const BlockDesc* blocks, u32 nblocks, const u64* stream_total, u64 out_cap, u64* stream_base /* [SFQ_NSTREAMS] */, u32* gate /* [2]: go, worst status */, hipStream_t st);
-void launch_record_sizes(const DecodeArgs& a, u64 nrec, u32* rsize, hipStream_t st);
-void launch_assemble(const DecodeArgs& a, u64 nrec, const u64* roff, u8* out, hipStream_t st);
+// records [r0, r1) -- a window of the call's blocks, or all of them; every per-record array is indexed by the call's record number
+void launch_record_sizes(const DecodeArgs& a, u64 r0, u64 r1, u32* rsize, hipStream_t st);
+void launch_assemble(const DecodeArgs& a, u64 r0, u64 r1, const u64* roff /* record r goes to out + roff[r] */, u8* out, hipStream_t st);
 void launch_first_hdr_lens(const BlockDesc* blocks, u32 nblocks, u32* lens, hipStream_t st);
 void launch_gather_first_hdrs(const BlockDesc* blocks, u32 nblocks, const u8* fq, const u64* blob_off, u8* blob, u64 cap, hipStream_t st);
 
