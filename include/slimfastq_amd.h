@@ -299,6 +299,37 @@ int sfq_get_checksums(sfq_ctx* ctx, uint32_t* h_block_crc, uint32_t cap, uint32_
  * sfq_get_checksums lists what was computed); n must equal its n_blocks, or it returns SFQ_E_ARG. */
 int sfq_set_block_checksums(sfq_ctx* ctx, const uint32_t* h_crc, uint32_t n);
 
+/* ---- text statistics ---------------------------------------------------------------------------------------------------
+ * What the first questions about a FASTQ file need -- bases, GC and N share, Q20 / Q30 share, read-length range, mean quality per
+ * cycle -- counted on the device while the text is resident for an encode (stats.hip), on a stream of its own.  The reference has
+ * none.  A line is what the call's line index says it is: the bytes between two '\n', so the leading '@' / '+' and a SOLiD prefix
+ * character are counted, a '\n' never.  The statistics cover the whole input text, format 6's oversize records included.
+ * Only the encode calls compute them (sfq_encode_blocks, sfq_encode_blocks_host, sfq_encode_qlt_blocks); the priors-only calls
+ * (sfq_build_priors, sfq_count_priors) do not, and -- deliberately -- no decode does: a decoder's text is the encoder's, whose
+ * statistics the archive carries ("txt.stat"), and a decode call has no line index of its output to count from. */
+#define SFQ_STATS_CYCLES 512
+typedef struct sfq_text_stats {
+    uint64_t n_records;
+    uint64_t hdr_bytes, seq_bytes, plus_bytes, qlt_bytes; /* sum of the lengths of lines 1..4 of every record */
+    uint32_t seq_len_min, seq_len_max;                    /* over line 2 */
+    uint64_t seq_hist[256];                               /* byte histogram of all lines 2 */
+    uint64_t qlt_hist[256];                               /* byte histogram of all lines 4 */
+    uint64_t cyc_n[SFQ_STATS_CYCLES + 1];                 /* [c]: quality bytes at position c of their line; [512]: all at positions >= 512 */
+    uint64_t cyc_qsum[SFQ_STATS_CYCLES + 1];              /* the sum of those bytes' values (raw byte values: the Phred offset is the reader's) */
+} sfq_text_stats;
+/* on != 0: every encode call counts the statistics of its text.  Default off: no pass, no event, no buffer; the encoded bytes
+ * are the same either way. */
+int  sfq_ctx_set_stats(sfq_ctx* ctx, int on);
+/* 1: *out = the last encode call's statistics; 0: it computed none (the switch was off, the call failed, or it was not an encode). */
+int  sfq_get_text_stats(sfq_ctx* ctx, sfq_text_stats* out);
+/* The statistics of two texts into those of both (host only): sums add, the length range widens; merging into an all-zero
+ * struct copies. */
+void sfq_text_stats_merge(sfq_text_stats* into, const sfq_text_stats* add);
+/* The "txt.stat" stream; returns its size (out == NULL: size only), SFQ_E_OVERFLOW where cap is short. */
+int64_t sfq_pack_text_stats(const sfq_text_stats* stats, uint8_t* out, uint64_t cap);
+/* SFQ_E_CORRUPT: truncated, trailing bytes, an unknown version, an array longer than the struct's. */
+int  sfq_unpack_text_stats(const uint8_t* bytes, uint64_t n, sfq_text_stats* out);
+
 /* ---- the ".sfq" container (host only) ----------------------------------------------------------
  * Replaces FilerSave + the info page (filer.cpp:217-242, config.cpp:334-347) for hosts that assemble an archive
  * themselves: info_text is the info page ("key=value\n" lines), then n_streams named byte streams (names of at most

@@ -28,6 +28,7 @@ EXPORTS = [
     "sfq_host_alloc", "sfq_host_free", "sfq_count_priors", "sfq_prior_counts_words", "sfq_get_prior_counts", "sfq_set_prior_counts",
     "sfq_archive_write_segments", "sfq_crc32", "sfq_crc32_combine", "sfq_ctx_set_checksums", "sfq_get_checksums",
     "sfq_set_block_checksums", "sfq_decode_block_range", "sfq_decode_block_range_host",
+    "sfq_ctx_set_stats", "sfq_get_text_stats", "sfq_text_stats_merge", "sfq_pack_text_stats", "sfq_unpack_text_stats",
 ]
 
 
@@ -57,6 +58,30 @@ class Segment(C.Structure):
                 ("first_hdrs", C.c_void_p), ("first_hdr_bytes", C.c_uint64), ("qlt_prior", C.c_void_p), ("qlt_prior_bytes", C.c_uint64),
                 ("chain_index", C.c_void_p), ("chain_index_bytes", C.c_uint64), ("rec_prior", C.c_void_p), ("rec_prior_bytes", C.c_uint64),
                 ("raw_bytes", C.c_uint64)]
+
+
+STATS_CYCLES = 512
+
+
+class TextStats(C.Structure):
+    """sfq_text_stats: the statistics of a FASTQ text (stats.hip).  Compares by value."""
+    _fields_ = [("n_records", C.c_uint64), ("hdr_bytes", C.c_uint64), ("seq_bytes", C.c_uint64), ("plus_bytes", C.c_uint64),
+                ("qlt_bytes", C.c_uint64), ("seq_len_min", C.c_uint32), ("seq_len_max", C.c_uint32),
+                ("seq_hist", C.c_uint64 * 256), ("qlt_hist", C.c_uint64 * 256),
+                ("cyc_n", C.c_uint64 * (STATS_CYCLES + 1)), ("cyc_qsum", C.c_uint64 * (STATS_CYCLES + 1))]
+
+    def __eq__(self, other):
+        return isinstance(other, TextStats) and bytes(self) == bytes(other)
+
+    def __ne__(self, other):
+        return not self == other
+
+    __hash__ = None
+
+    def copy(self):
+        t = TextStats()
+        C.memmove(C.byref(t), C.byref(self), C.sizeof(TextStats))
+        return t
 
 
 class SfqError(RuntimeError):
@@ -151,6 +176,14 @@ def lib():
         L.sfq_ctx_set_checksums.argtypes = [vp, C.c_int]
         L.sfq_get_checksums.argtypes = [vp, u32p, C.c_uint32, u32p]
         L.sfq_set_block_checksums.argtypes = [vp, u32p, C.c_uint32]
+        tsp = C.POINTER(TextStats)
+        L.sfq_ctx_set_stats.argtypes = [vp, C.c_int]
+        L.sfq_get_text_stats.argtypes = [vp, tsp]
+        L.sfq_text_stats_merge.argtypes = [tsp, tsp]
+        L.sfq_text_stats_merge.restype = None
+        L.sfq_pack_text_stats.argtypes = [tsp, u8p, u64]
+        L.sfq_pack_text_stats.restype = C.c_int64
+        L.sfq_unpack_text_stats.argtypes = [u8p, u64, tsp]
         _lib = L
     return _lib
 
@@ -199,14 +232,43 @@ def crc32_combine(crc_a, crc_b, len_b):
     return int(lib().sfq_crc32_combine(crc_a & 0xFFFFFFFF, crc_b & 0xFFFFFFFF, int(len_b)))
 
 
+def stats_merge(into: TextStats, add: TextStats) -> TextStats:
+    """The statistics of two texts into those of both, in place (sfq_text_stats_merge); returns into."""
+    lib().sfq_text_stats_merge(C.byref(into), C.byref(add))
+    return into
+
+
+def pack_text_stats(stats: TextStats) -> bytes:
+    """The "txt.stat" stream of these statistics."""
+    L = lib()
+    n = L.sfq_pack_text_stats(C.byref(stats), None, 0)
+    if n < 0:
+        raise SfqError(n, "sfq_pack_text_stats")
+    buf = C.create_string_buffer(max(n, 1))
+    got = L.sfq_pack_text_stats(C.byref(stats), buf, n)
+    if got != n:
+        raise SfqError(got, "sfq_pack_text_stats")
+    return buf.raw[:n]
+
+
+def unpack_text_stats(blob: bytes) -> TextStats:
+    """"txt.stat" -> TextStats; SfqError (code -6) where the stream is damaged."""
+    t = TextStats()
+    rc = lib().sfq_unpack_text_stats(blob if len(blob) else None, len(blob), C.byref(t))
+    if rc:
+        raise SfqError(rc, "damaged txt.stat")
+    return t
+
+
 class Encoded:
     """Host copy of one sfq_encode_blocks result.  crcs / text_crc: the CRC-32 of every block's text and of the whole text,
-    where the context had checksums on (else None)."""
+    where the context had checksums on (else None); stats: the text's statistics (TextStats), where it had them on (else None)."""
 
-    def __init__(self, res, blocks, first_hdrs, data, prior=b"", chains=b"", rec_prior=b"", crcs=None, text_crc=None):
+    def __init__(self, res, blocks, first_hdrs, data, prior=b"", chains=b"", rec_prior=b"", crcs=None, text_crc=None, stats=None):
         self.res, self.blocks, self.first_hdrs, self.data, self.prior, self.chains = res, blocks, first_hdrs, data, prior, chains
         self.rec_prior = rec_prior
         self.crcs, self.text_crc = crcs, text_crc
+        self.stats = stats
 
     def clone(self):
         """A deep copy (the tests damage copies)."""
@@ -216,7 +278,7 @@ class Encoded:
         C.memmove(C.byref(res), C.byref(self.res), C.sizeof(Result))
         data = self.data.copy() if isinstance(self.data, np.ndarray) else bytes(self.data)
         return Encoded(res, blocks, bytes(self.first_hdrs), data, bytes(self.prior), bytes(self.chains), bytes(self.rec_prior),
-                       None if self.crcs is None else list(self.crcs), self.text_crc)
+                       None if self.crcs is None else list(self.crcs), self.text_crc, None if self.stats is None else self.stats.copy())
 
     def stream(self, s, block=None) -> bytes:
         """Bytes of stream s (an id or a name): the whole concatenation, or one block's part."""
@@ -281,6 +343,18 @@ class Context:
         buf = (C.c_uint32 * max(n, 1))()
         L.sfq_get_checksums(self._h, buf, n, None)
         return list(buf)[:n], text.value
+
+    def set_stats(self, on=True):
+        """Text statistics on: every encode call counts them of its text on the GPU (text_stats())."""
+        self._check(lib().sfq_ctx_set_stats(self._h, 1 if on else 0))
+
+    def text_stats(self):
+        """The last encode call's TextStats; None where it computed none."""
+        t = TextStats()
+        rc = lib().sfq_get_text_stats(self._h, C.byref(t))
+        if rc < 0:
+            self._check(rc)
+        return t if rc == 1 else None
 
     def set_block_checksums(self, crcs):
         """The expected CRCs of the next decode call's blocks (consumed by it)."""
@@ -376,7 +450,7 @@ class Context:
         crcs, text_crc = self.checksums()
         on = len(crcs) == res.n_blocks and res.n_blocks > 0
         return Encoded(res, blocks, self.first_headers(res.first_hdr_bytes), out[:res.total_bytes].copy(), self.prior(), self.chains(), self.rec_prior(),
-                       crcs if on else None, text_crc if on else None)
+                       crcs if on else None, text_crc if on else None, self.text_stats())
 
     def encode_device(self, d_ptr, nbytes, d_out, out_cap, level=3, block_reads=0, gen_bits=0, models=0, kernel=0, qlt_only=False,
                       prior_step=0, tables=0, chain_reads=0, lds_rows=0):

@@ -176,6 +176,13 @@ struct sfq_ctx {
     void* crc_pin = nullptr; size_t crc_pin_cap = 0;
     std::vector<u32> crcs; u32 text_crc = 0;          // the last call's: per block, whole text
     std::vector<u32> crc_expect; bool crc_expect_set = false;   // sfq_set_block_checksums, for the next decode
+    // text statistics (stats.hip): like the checksums, nothing of this exists until a caller turns them on
+    bool stats_on = false;
+    hipStream_t st_stats = nullptr;        // an encode's pass runs here, beside the models
+    hipEvent_t stats_ev[2] = {};           // fork from the context's stream, pass through
+    DevBuf stats_acc;
+    void* stats_pin = nullptr; size_t stats_pin_cap = 0;
+    sfq_text_stats stats; bool stats_valid = false;   // the last encode call's
 };
 
 namespace {
@@ -854,6 +861,14 @@ int crc_queue(sfq_ctx* ctx, const u8* d, u64 total, u32 n, hipStream_t st) {
     HIPC(hipMemcpyAsync(ctx->crc_pin, ctx->crc_out.p, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, st));
     return SFQ_OK;
 }
+// text statistics (stats.hip): the stream, events and buffers, made the first time they are wanted
+int stats_ready(sfq_ctx* ctx) {
+    if (!ctx->st_stats) HIPC(hipStreamCreateWithFlags(&ctx->st_stats, hipStreamNonBlocking));
+    for (auto& e : ctx->stats_ev) if (!e) HIPC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    int rc;
+    if ((rc = reserve(ctx, ctx->stats_acc, (size_t)text_stats_acc_bytes()))) return rc;
+    return reserve_pinned_buf(ctx, ctx->stats_pin, ctx->stats_pin_cap, sizeof(sfq_text_stats));
+}
 void crc_take(sfq_ctx* ctx, u32 n) {
     const u32* v = (const u32*)ctx->crc_pin;
     ctx->crcs.assign(v, v + n);
@@ -929,13 +944,16 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
         &ctx->hcnt, &ctx->hfreq, &ctx->rrows, &ctx->rdec, &ctx->rmap, &ctx->rflags, &ctx->rtok, &ctx->ptmp, &ctx->qrows, &ctx->qdec, &ctx->qesc, &ctx->qw, &ctx->csz, &ctx->coff, &ctx->gcnt, &ctx->grows, &ctx->glog, &ctx->gcost, &ctx->gbins, &ctx->gfill, &ctx->gm_T, &ctx->gm_slen, &ctx->gm_boff, &ctx->gm_soff, &ctx->gm_scan, &ctx->gm_stage, &ctx->gm_tok, &ctx->gm_csz, &ctx->gm_idx, &ctx->excf, &ctx->cflags, &ctx->segn, &ctx->segoff, &ctx->segrec, &ctx->pslot, &ctx->plist, &ctx->chn_len, &ctx->chn_off, &ctx->chn_out,
         &ctx->oflags, &ctx->okbytes, &ctx->ofpos, &ctx->okoff, &ctx->ofilt, &ctx->orecmap, &ctx->olist, &ctx->line_off_o, &ctx->ono, &ctx->opiece,
         &ctx->otxt[0], &ctx->otxt[1], &ctx->otxt[2], &ctx->osize_all, &ctx->oroff_all, &ctx->oroff_k, &ctx->ocnt,
-        &ctx->crc_tab, &ctx->crc_tiles, &ctx->crc_grps, &ctx->crc_bounds, &ctx->crc_out };
+        &ctx->crc_tab, &ctx->crc_tiles, &ctx->crc_grps, &ctx->crc_bounds, &ctx->crc_out, &ctx->stats_acc };
     for (DevBuf* b : all) release(*b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->pin2) (void)hipHostFree(ctx->pin2);
     if (ctx->crc_pin) (void)hipHostFree(ctx->crc_pin);
     for (auto& e : ctx->crc_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->st_crc) (void)hipStreamDestroy(ctx->st_crc);
+    if (ctx->stats_pin) (void)hipHostFree(ctx->stats_pin);
+    for (auto& e : ctx->stats_ev) if (e) (void)hipEventDestroy(e);
+    if (ctx->st_stats) (void)hipStreamDestroy(ctx->st_stats);
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
     for (auto& s : ctx->st_aux) if (s) (void)hipStreamDestroy(s);
     if (ctx->st) (void)hipStreamDestroy(ctx->st);
@@ -987,6 +1005,7 @@ static int encode_impl(sfq_ctx* ctx, const u8* d_fastq, u64 nbytes, const sfq_pa
     HIPC(hipSetDevice(ctx->dev));
     Settle settle(ctx);
     ctx->crcs.clear(); ctx->text_crc = 0;
+    ctx->stats_valid = false;
     const int rc = encode_body(ctx, d_fastq, nbytes, pp, d_out, out_cap, res, force_models, priors_only);
     settle.ok = rc == SFQ_OK;
     if (rc == SFQ_OK && !priors_only) ctx->blobs_from_encode = true;       // (sfq_build_priors leaves installed priors: SFQ_PRIOR_GIVEN reads them)
@@ -1182,6 +1201,18 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
         launch_crc_block_bounds((const u64*)ctx->line_off.p, 4ull * block_reads, nblocks, nbytes_in, (u64*)ctx->crc_bounds.p, ctx->st_crc);
         if ((rc = crc_queue(ctx, d_fastq_in, nbytes_in, nblocks, ctx->st_crc))) return rc;
         HIPC(hipEventRecord(ctx->crc_ev[CRC_EV_DONE], ctx->st_crc));
+    }
+    // text statistics: one pass over the whole file's text and line index (d_file: the oversize records included) on a stream of
+    // its own; taken in at the end of the call
+    const bool stats_pass = ctx->stats_on && !priors_only;
+    if (stats_pass) {
+        if ((rc = stats_ready(ctx))) return rc;
+        HIPC(hipEventRecord(ctx->stats_ev[0], st));
+        HIPC(hipStreamWaitEvent(ctx->st_stats, ctx->stats_ev[0], 0));
+        HIPC(hipMemsetAsync(ctx->stats_acc.p, 0, (size_t)text_stats_acc_bytes(), ctx->st_stats));
+        launch_text_stats(d_file, nbytes_in, (const u64*)(n_over ? ctx->line_off_o.p : ctx->line_off.p), nrec_file, ctx->stats_acc.p, ctx->st_stats);
+        HIPC(hipMemcpyAsync(ctx->stats_pin, ctx->stats_acc.p, sizeof(sfq_text_stats), hipMemcpyDeviceToHost, ctx->st_stats));
+        HIPC(hipEventRecord(ctx->stats_ev[1], ctx->st_stats));
     }
     // (format 6 with oversize records: three more regions behind the block's, for "usr.lrec" / "usr.lgen" / "usr.lqlt")
     const u64 arena_main = (((u64)nbytes * 17 / 2 + (u64)nblocks * 1024 + 4096) + 15) & ~15ull;      // frame.hip k_block_prepare
@@ -1780,6 +1811,11 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     if (crc_pass) {
         HIPC(hipEventSynchronize(ctx->crc_ev[CRC_EV_DONE]));
         crc_take(ctx, nblocks);
+    }
+    if (stats_pass) {
+        HIPC(hipEventSynchronize(ctx->stats_ev[1]));
+        memcpy(&ctx->stats, ctx->stats_pin, sizeof ctx->stats);
+        ctx->stats_valid = true;
     }
     return SFQ_OK;
 }
@@ -2748,6 +2784,17 @@ int sfq_ctx_set_checksums(sfq_ctx* ctx, int on) {
     if (!ctx) return SFQ_E_ARG;
     ctx->crc_on = on != 0;
     return SFQ_OK;
+}
+int sfq_ctx_set_stats(sfq_ctx* ctx, int on) {
+    if (!ctx) return SFQ_E_ARG;
+    ctx->stats_on = on != 0;
+    return SFQ_OK;
+}
+int sfq_get_text_stats(sfq_ctx* ctx, sfq_text_stats* out) {
+    if (!ctx || !out) return SFQ_E_ARG;
+    if (!ctx->stats_valid) return 0;
+    *out = ctx->stats;
+    return 1;
 }
 int sfq_get_checksums(sfq_ctx* ctx, uint32_t* h_block_crc, uint32_t cap, uint32_t* h_text_crc) {
     if (!ctx) return SFQ_E_ARG;

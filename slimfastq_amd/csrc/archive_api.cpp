@@ -36,6 +36,22 @@ int64_t sfq_pack_block_index(const sfq_block_info* blocks, uint32_t n, uint8_t* 
     return (int64_t)v.size();
 }
 
+void sfq_text_stats_merge(sfq_text_stats* into, const sfq_text_stats* add) {
+    if (into && add) sfqc::merge_text_stats(*into, *add);
+}
+int64_t sfq_pack_text_stats(const sfq_text_stats* stats, uint8_t* out, uint64_t cap) {
+    if (!stats) return SFQ_E_ARG;
+    const std::vector<uint8_t> v = sfqc::pack_text_stats(*stats);
+    if (!out) return (int64_t)v.size();
+    if (v.size() > cap) return SFQ_E_OVERFLOW;
+    memcpy(out, v.data(), v.size());
+    return (int64_t)v.size();
+}
+int sfq_unpack_text_stats(const uint8_t* bytes, uint64_t n, sfq_text_stats* out) {
+    if (!out || (n && !bytes)) return SFQ_E_ARG;
+    return sfqc::unpack_text_stats(std::vector<uint8_t>(bytes, bytes + n), *out) ? SFQ_OK : SFQ_E_CORRUPT;
+}
+
 int sfq_archive_write_segments(const char* path, const char* orig_name, int level, uint32_t tables, int shared_prior,
                                uint32_t n, const sfq_segment* segs) {
     if (!path || !orig_name || (n && !segs) || (tables != SFQ_TABLES_FROZEN && tables != SFQ_TABLES_ADAPTIVE)) return SFQ_E_ARG;

@@ -7,6 +7,7 @@
 //               frozen tables (rows built by counting passes, one chain per GPU lane)
 //   -g dev    : HIP device
 //   -K        : store the CRC-32 of every block's text ("blk.crc") and of the file (info key "crc32"); a decode checks them
+//   -Y        : count the statistics of the text on the GPU while it is coded and store them ("txt.stat"); -s prints them
 //   -R F:N    : with -d: records F .. F + N - 1 only (numbered from 0 over the archive) -- the blocks that hold them are decoded, no others
 // All model / coder work happens in libslimfastq_amd.so on the GPU; this file parses arguments, reads and
 // writes files and fills the info page.
@@ -85,6 +86,8 @@ static void usage() {
            "-C reads         : frozen tables: records per chain (default: automatic)\n"
            "-K               : checksums: store the CRC-32 of every block's text and of the whole file (computed on the GPU);\n"
            "                   decoding checks them and fails on a mismatch (needs the block format: not with -B 0)\n"
+           "-Y               : text statistics: count bases, GC / N share, Q20 / Q30 share, read lengths and the mean quality per cycle\n"
+           "                   on the GPU while the text is coded, and store them in the archive; -s prints them (works with -B 0 too)\n"
            "-R first:count   : with -d: write records first .. first+count-1 only (numbered from 0 over the whole archive; count is\n"
            "                   clipped at the end): only the blocks that hold them are decoded (and, under a base model, what the\n"
            "                   format makes them depend on); with -b: of every job\n"
@@ -117,6 +120,7 @@ struct Opts {
     bool force_frozen = false;                                         // -F
     long chain_reads = 0;                                              // -C
     bool checksum = false;                                             // -K
+    bool stats = false;                                                // -Y
     bool range = false; uint64_t r_first = 0, r_count = 0;             // -R first:count
 };
 // "FIRST:COUNT", both decimal, COUNT > 0
@@ -181,7 +185,7 @@ static size_t whole_records(const uint8_t* p, size_t n, uint64_t nl) {
 }
 
 // One finished library call (a segment of raw bytes of text) into the archive's index.
-static void collect(sfq_ctx* ctx, const sfq_result& res, uint64_t raw, sfqc::SegmentedIndex& idx, bool checksum) {
+static void collect(sfq_ctx* ctx, const sfq_result& res, uint64_t raw, sfqc::SegmentedIndex& idx, bool checksum, bool stats) {
     std::vector<sfq_block_info> blocks(res.n_blocks);
     sfq_get_block_index(ctx, blocks.data(), res.n_blocks);
     std::vector<uint8_t> first((size_t)res.first_hdr_bytes + 1);
@@ -202,7 +206,44 @@ static void collect(sfq_ctx* ctx, const sfq_result& res, uint64_t raw, sfqc::Seg
         crc.resize(res.n_blocks + 1);
         if (sfq_get_checksums(ctx, crc.data(), res.n_blocks, &text_crc) != (int)res.n_blocks) croak("checksums: the library returned none for this call");
     }
-    idx.add(g, checksum ? crc.data() : nullptr, text_crc);
+    sfq_text_stats ts;
+    if (stats && sfq_get_text_stats(ctx, &ts) != 1) croak("text statistics: the library returned none for this call");   // -Y (sfq_ctx_set_stats in encode_file)
+    idx.add(g, checksum ? crc.data() : nullptr, text_crc, stats ? &ts : nullptr);
+}
+
+// -s: the third section, from "txt.stat" (archives written with -Y)
+static void print_text_stats(const std::vector<uint8_t>& bytes) {
+    sfq_text_stats t;
+    fprintf(stderr, "\n:::: Text ::::\n");
+    if (!sfqc::unpack_text_stats(bytes, t)) { fprintf(stderr, "txt.stat: damaged (%zu bytes): no text statistics\n", bytes.size()); return; }
+    auto row = [](const char* key, const std::string& val) { fprintf(stderr, "%-16s = %s\n", key, val.c_str()); };
+    auto fixed = [](double v, int digits) { char b[64]; snprintf(b, sizeof b, "%.*f", digits, v); return std::string(b); };
+    auto pct = [&](uint64_t part, uint64_t all) { return fixed(all ? 100.0 * (double)part / (double)all : 0.0, 2); };
+    row("records", std::to_string(t.n_records));
+    row("bases", std::to_string(t.seq_bytes));
+    row("seq_len_min", std::to_string(t.seq_len_min));
+    row("seq_len_max", std::to_string(t.seq_len_max));
+    row("seq_len_mean", fixed(t.n_records ? (double)t.seq_bytes / (double)t.n_records : 0.0, 2));
+    row("gc_pct", pct(t.seq_hist['G'] + t.seq_hist['C'] + t.seq_hist['g'] + t.seq_hist['c'], t.seq_bytes));
+    row("n_pct", pct(t.seq_hist['N'] + t.seq_hist['n'] + t.seq_hist['.'], t.seq_bytes));
+    uint64_t q20 = 0, q30 = 0;
+    int qmin = -1, qmax = -1;
+    for (int b = 0; b < 256; b++) {
+        if (b >= '5') q20 += t.qlt_hist[b];
+        if (b >= '?') q30 += t.qlt_hist[b];
+        if (t.qlt_hist[b]) { if (qmin < 0) qmin = b; qmax = b; }
+    }
+    row("q20_pct", pct(q20, t.qlt_bytes));
+    row("q30_pct", pct(q30, t.qlt_bytes));
+    row("qlt_min", qmin < 0 ? std::string() : std::string(1, (char)qmin));
+    row("qlt_max", qmax < 0 ? std::string() : std::string(1, (char)qmax));
+    std::string cyc;
+    int last = -1;
+    for (int c = 0; c < SFQ_STATS_CYCLES; c++) if (t.cyc_n[c]) last = c;
+    auto mean_q = [&](int c) { return fixed(t.cyc_n[c] ? (double)t.cyc_qsum[c] / (double)t.cyc_n[c] - 33.0 : 0.0, 1); };
+    for (int c = 0; c <= last; c++) { if (c) cyc += ","; cyc += mean_q(c); }
+    if (t.cyc_n[SFQ_STATS_CYCLES]) { if (!cyc.empty()) cyc += ","; cyc += mean_q(SFQ_STATS_CYCLES); }
+    row("cycle_mean_q", cyc);
 }
 
 static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, const std::string& fil) {
@@ -217,6 +258,7 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     }
     const bool legacy = o.block_reads == 0;
     if (sfq_ctx_set_checksums(ctx, o.checksum ? 1 : 0)) croak("%s", sfq_last_error(ctx));
+    if (sfq_ctx_set_stats(ctx, o.stats ? 1 : 0)) croak("%s", sfq_last_error(ctx));
     sfq_params p; memset(&p, 0, sizeof p);
     p.level = o.level; p.block_reads = o.block_reads < 0 ? SFQ_BLOCK_AUTO : (uint32_t)o.block_reads;
     p.prior_step = legacy ? 0 : SFQ_PRIOR_AUTO;                        // warm start needs the block format
@@ -356,7 +398,7 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             }
             if (rc) croak("%s", sfq_last_error(ctx));
             tick("sfq_encode_blocks_host");
-            collect(ctx, res, use, idx, o.checksum);
+            collect(ctx, res, use, idx, o.checksum, o.stats);
             tick("collect slab");
             writer.join();
             {
@@ -401,7 +443,7 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         const int rc = sfq_encode_blocks_host(ctx, text, use, &p, out.p, bound, &res);
         if (rc) croak("%s", sfq_last_error(ctx));
         tick("sfq_encode_blocks_host");
-        collect(ctx, res, use, idx, o.checksum);
+        collect(ctx, res, use, idx, o.checksum, o.stats);
         for (int s = 0; s < SFQ_NSTREAMS; s++)
             streams[s].insert(streams[s].end(), out.p + res.stream_offset[s], out.p + res.stream_offset[s] + res.stream_bytes[s]);
         memmove(fq.p, fq.p + use, fq.n - use); fq.n -= use;               // keep the partial record for the next slab
@@ -438,6 +480,7 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     }
     for (int s = 0; s < SFQ_NSTREAMS; s++) if (!streams[s].empty()) a.add(sfq_stream_name(s), std::move(streams[s]));
     if (!legacy) for (auto& s : idx.streams(frozen)) a.add(s.first, std::move(s.second));
+    else if (o.stats) a.add("txt.stat", sfqc::pack_text_stats(idx.stats));      // (a stream of its own: the reference's decoder does not look at it)
     std::string err;
     tick("build archive");
     if (!sfqc::write_file(fil, a, err)) croak("%s", err.c_str());
@@ -638,7 +681,7 @@ int main(int argc, char** argv) {
     Opts o;
     bool statistics = false;
     if (argc == 1) usage();
-    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFK1234u:f:l:B:g:S:T:C:t:R:")) != -1;) {
+    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKY1234u:f:l:B:g:S:T:C:t:R:")) != -1;) {
         switch (opt) {
         case 'u': g_usr = optarg; break;
         case 'f': fil = optarg; break;
@@ -657,6 +700,7 @@ int main(int argc, char** argv) {
         case 'A': o.adaptive = true; break;
         case 'F': o.force_frozen = true; break;
         case 'K': o.checksum = true; break;
+        case 'Y': o.stats = true; break;
         case 'R': if (!parse_range(optarg, o.r_first, o.r_count)) usage(); o.range = true; break;
         case 'C': o.chain_reads = strtol(optarg, 0, 0); break;
         case 't': o.io_threads = std::min(64, std::max(1, atoi(optarg))); break;
@@ -733,6 +777,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "\n:::: Files stream ::::\n i: name      : bytes\n");
         int i = 1;
         for (auto& s : a.streams) fprintf(stderr, "%2d: %-10s: %zu\n", i++, s.first.c_str(), s.second.size());
+        if (const std::vector<uint8_t>* ts = a.find("txt.stat")) print_text_stats(*ts);
         return 0;
     }
 

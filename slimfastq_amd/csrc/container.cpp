@@ -361,9 +361,56 @@ bool unpack_block_checksums(const std::vector<uint8_t>& bytes, size_t nblocks, s
     return true;
 }
 
-void SegmentedIndex::add(const sfq_segment& s, const uint32_t* block_crc, uint32_t call_crc) {
+// ---- text statistics ("txt.stat") ------------------------------------------------------------------------------
+static const uint8_t kTextStatsVersion = 1;
+void merge_text_stats(sfq_text_stats& into, const sfq_text_stats& add) {
+    if (!add.n_records) return;
+    if (!into.n_records) { into = add; return; }
+    into.n_records += add.n_records;
+    into.hdr_bytes += add.hdr_bytes; into.seq_bytes += add.seq_bytes; into.plus_bytes += add.plus_bytes; into.qlt_bytes += add.qlt_bytes;
+    into.seq_len_min = std::min(into.seq_len_min, add.seq_len_min);
+    into.seq_len_max = std::max(into.seq_len_max, add.seq_len_max);
+    for (int i = 0; i < 256; i++) { into.seq_hist[i] += add.seq_hist[i]; into.qlt_hist[i] += add.qlt_hist[i]; }
+    for (int i = 0; i <= SFQ_STATS_CYCLES; i++) { into.cyc_n[i] += add.cyc_n[i]; into.cyc_qsum[i] += add.cyc_qsum[i]; }
+}
+// an array as the number of entries up to the last non-zero one, then those entries
+static void put_array(std::vector<uint8_t>& o, const uint64_t* v, size_t n) {
+    while (n && !v[n - 1]) n--;
+    put_v(o, n);
+    for (size_t i = 0; i < n; i++) put_v(o, v[i]);
+}
+static bool get_array(const std::vector<uint8_t>& b, size_t& p, uint64_t* v, size_t cap) {
+    uint64_t n;
+    if (!get_v(b, p, n) || n > cap) return false;
+    for (size_t i = 0; i < (size_t)n; i++) if (!get_v(b, p, v[i])) return false;
+    return true;
+}
+std::vector<uint8_t> pack_text_stats(const sfq_text_stats& t) {
+    std::vector<uint8_t> o;
+    o.push_back(kTextStatsVersion);
+    put_v(o, t.n_records); put_v(o, t.hdr_bytes); put_v(o, t.seq_bytes); put_v(o, t.plus_bytes); put_v(o, t.qlt_bytes);
+    put_v(o, t.seq_len_min); put_v(o, t.seq_len_max);
+    put_array(o, t.seq_hist, 256); put_array(o, t.qlt_hist, 256);
+    put_array(o, t.cyc_n, SFQ_STATS_CYCLES + 1); put_array(o, t.cyc_qsum, SFQ_STATS_CYCLES + 1);
+    return o;
+}
+bool unpack_text_stats(const std::vector<uint8_t>& b, sfq_text_stats& t) {
+    memset(&t, 0, sizeof t);
+    if (b.empty() || b[0] != kTextStatsVersion) return false;
+    size_t p = 1; uint64_t mn, mx;
+    if (!get_v(b, p, t.n_records) || !get_v(b, p, t.hdr_bytes) || !get_v(b, p, t.seq_bytes) || !get_v(b, p, t.plus_bytes) || !get_v(b, p, t.qlt_bytes)) return false;
+    if (!get_v(b, p, mn) || !get_v(b, p, mx) || mn > 0xFFFFFFFFull || mx > 0xFFFFFFFFull) return false;
+    t.seq_len_min = (uint32_t)mn; t.seq_len_max = (uint32_t)mx;
+    if (!get_array(b, p, t.seq_hist, 256) || !get_array(b, p, t.qlt_hist, 256)) return false;
+    if (!get_array(b, p, t.cyc_n, SFQ_STATS_CYCLES + 1) || !get_array(b, p, t.cyc_qsum, SFQ_STATS_CYCLES + 1)) return false;
+    return p == b.size();
+}
+
+void SegmentedIndex::add(const sfq_segment& s, const uint32_t* block_crc, uint32_t call_crc, const sfq_text_stats* call_stats) {
     if (!s.n_blocks) return;
     if (!block_crc) crc_all = false;
+    if (!call_stats) stats_all = false;
+    if (stats_all) merge_text_stats(stats, *call_stats);
     if (crc_all) {
         crcs.insert(crcs.end(), block_crc, block_crc + s.n_blocks);
         text_crc = sfq_crc32_combine(text_crc, call_crc, s.raw_bytes);
@@ -412,6 +459,7 @@ std::vector<std::pair<std::string, std::vector<uint8_t>>> SegmentedIndex::stream
     if (!recpri.empty()) out.emplace_back("rec.pri", recpri);
     if (segs.size() > 1) out.emplace_back("seg.idx", pack_segment_index(segs, frozen));
     if (crc_all && !segs.empty()) out.emplace_back("blk.crc", pack_block_checksums(crcs));
+    if (stats_all && !segs.empty()) out.emplace_back("txt.stat", pack_text_stats(stats));
     return out;
 }
 

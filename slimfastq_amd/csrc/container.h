@@ -84,6 +84,12 @@ bool unpack_segment_index(const std::vector<uint8_t>& bytes, std::vector<Segment
 std::vector<uint8_t> pack_block_checksums(const std::vector<uint32_t>& crcs);
 bool unpack_block_checksums(const std::vector<uint8_t>& bytes, size_t nblocks, std::vector<uint32_t>& crcs);
 
+// "txt.stat": the statistics of the archive's text (sfq_text_stats): a version byte, the scalar fields in
+// struct order as varints, then each array as the number of entries up to its last non-zero one and those entries
+void merge_text_stats(sfq_text_stats& into, const sfq_text_stats& add);
+std::vector<uint8_t> pack_text_stats(const sfq_text_stats& t);
+bool unpack_text_stats(const std::vector<uint8_t>& bytes, sfq_text_stats& t);
+
 // The block format's index, collected one library call at a time: the calls' blocks (first_record / first_hdr_off re-based
 // onto the archive), first headers, "qlt.pri" / "chn.idx" / "rec.pri" blobs and segments.  A call without blocks adds nothing.
 // The payload streams are the caller's: it writes them, in the calls' order, beside the index streams this hands back.
@@ -94,12 +100,15 @@ struct SegmentedIndex {
     uint64_t records = 0, raw = 0;
     // checksums: kept while every call with blocks came with them ("blk.crc" and info key "crc32", the whole text's)
     std::vector<uint32_t> crcs; uint32_t text_crc = 0; bool crc_all = true;
+    // text statistics: the calls' merged, kept while every call with blocks came with them ("txt.stat")
+    sfq_text_stats stats = {}; bool stats_all = true;
 
-    // reads everything but the payload streams; block_crc / text_crc: the call's checksums (block_crc NULL: it has none)
-    void add(const sfq_segment& s, const uint32_t* block_crc = nullptr, uint32_t text_crc = 0);
+    // reads everything but the payload streams; block_crc / text_crc: the call's checksums (block_crc NULL: it has none);
+    // call_stats: its text statistics (NULL: none)
+    void add(const sfq_segment& s, const uint32_t* block_crc = nullptr, uint32_t text_crc = 0, const sfq_text_stats* call_stats = nullptr);
     // info keys of the archive, in the order they are written
     std::vector<std::pair<std::string, std::string>> info(int level, const std::string& orig_name, bool frozen, bool shared_prior) const;
-    // "blk.idx", "blk.hdr", "qlt.pri", "chn.idx", "rec.pri", "seg.idx", "blk.crc" (each where the archive has one)
+    // "blk.idx", "blk.hdr", "qlt.pri", "chn.idx", "rec.pri", "seg.idx", "blk.crc", "txt.stat" (each where the archive has one)
     std::vector<std::pair<std::string, std::vector<uint8_t>>> streams(bool frozen) const;
 };
 

@@ -267,3 +267,8 @@ void launch_crc32(const u8* d, const u64* d_bounds, u32 n_ranges, u32 whole, u64
                   const u32* tab, hipStream_t st);
 // bounds[0..nblocks] of a call's blocks: 0, offs[b * stride] (0 < b < nblocks), total
 void launch_crc_block_bounds(const u64* offs, u64 stride, u32 nblocks, u64 total, u64* bounds, hipStream_t st);
+
+// The statistics of a text (stats.hip, sfq_text_stats): acc = text_stats_acc_bytes() zeroed bytes, which begin with the struct once
+// the three kernels are through; line_off: the index of the text's 4 * nrec lines (line_off[4 * nrec] = n)
+u64  text_stats_acc_bytes();
+void launch_text_stats(const u8* fq, u64 n, const u64* line_off, u64 nrec, void* acc, hipStream_t st);
