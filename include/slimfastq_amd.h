@@ -330,6 +330,34 @@ int64_t sfq_pack_text_stats(const sfq_text_stats* stats, uint8_t* out, uint64_t 
 /* SFQ_E_CORRUPT: truncated, trailing bytes, an unknown version, an array longer than the struct's. */
 int  sfq_unpack_text_stats(const uint8_t* bytes, uint64_t n, sfq_text_stats* out);
 
+/* ---- quality binning ---------------------------------------------------------------------------------------------------
+ * The one LOSSY option, strictly opt-in: every byte of every 4th line of a FASTQ text (line number & 3 == 3 counted from the start
+ * of the buffer; the '\n' excluded) goes through a 256-byte table, in place on the device (qmap.hip), before an encode frames the
+ * text.  The pass is text to text: the streams, the checksums, the statistics and every decoder see the mapped text and nothing
+ * else.  The reference has no counterpart.  A text without a final '\n' is handled: its last line is a line.  Like sfq_crc32 the
+ * pass reads the whole aligned 16-byte units of the text's first and last byte; it writes nothing outside the text.
+ * Presets, Phred+33 (Q = byte - 33); Q0 and Q1 ('!' and '"': "no call", and the '!' <-> N coupling of gens.cpp) stay, both are idempotent:
+ *   SFQ_QMAP_ILLUMINA8: 2-9 -> 6, 10-19 -> 15, 20-24 -> 22, 25-29 -> 27, 30-34 -> 33, 35-39 -> 37, 40-93 -> 40
+ *   SFQ_QMAP_NOVASEQ4:  2 -> 2, 3-14 -> 12, 15-29 -> 23, 30-93 -> 37   (the values of sfq_synth_fastq kind 2: such a text is a fixed point) */
+#define SFQ_QMAP_ILLUMINA8 1
+#define SFQ_QMAP_NOVASEQ4  2
+/* host only, no GPU: fills lut[256]; SFQ_E_ARG for an unknown preset */
+int sfq_quality_map_preset(int preset, uint8_t lut[256]);
+/* host only: SFQ_OK, or SFQ_E_ARG unless lut[b] == b for every b < 33 or b > 126, and 33 <= lut[b] <= 126 for every other b
+ * (a table can neither move nor make a line end, a control byte or a byte outside ASCII) */
+int sfq_quality_map_check(const uint8_t lut[256]);
+/* in place, on the context's stream, synchronises once; *changed (may be NULL) = bytes whose value changed.  SFQ_E_ARG for a table
+ * that sfq_quality_map_check refuses (the text is not touched). */
+int sfq_map_qualities(sfq_ctx* ctx, uint8_t* d_fastq, uint64_t nbytes, const uint8_t lut[256], uint64_t* changed);
+/* lut != NULL: every *_host encode entry (sfq_encode_blocks_host) maps its staged copy of the text before it frames it; the
+ * caller's host buffer is not touched.  NULL: off (default): nothing is launched or allocated.  SFQ_E_ARG for a table that
+ * sfq_quality_map_check refuses (the installed map stays as it was).
+ * The entries that take CONST device text -- sfq_encode_blocks, sfq_encode_qlt_blocks, sfq_build_priors, sfq_count_priors --
+ * cannot apply a map: while one is installed they return SFQ_E_UNSUPPORTED (call sfq_map_qualities on the buffer instead). */
+int sfq_ctx_set_quality_map(sfq_ctx* ctx, const uint8_t* lut);
+/* bytes changed by the last encode call's map (0 where none ran) */
+uint64_t sfq_get_quality_map_changed(const sfq_ctx* ctx);
+
 /* ---- the ".sfq" container (host only) ----------------------------------------------------------
  * Replaces FilerSave + the info page (filer.cpp:217-242, config.cpp:334-347) for hosts that assemble an archive
  * themselves: info_text is the info page ("key=value\n" lines), then n_streams named byte streams (names of at most

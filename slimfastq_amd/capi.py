@@ -18,6 +18,8 @@ PRIOR_COUNTS = 0xFFFFFFFD
 BLOCK_AUTO = 0xFFFFFFFF
 TABLES_ADAPTIVE, TABLES_FROZEN, TABLES_AUTO = 0, 1, 2
 LDS_ROWS_NONE = 0xFFFFFFFF
+QMAP_ILLUMINA8, QMAP_NOVASEQ4 = 1, 2
+QMAP_PRESETS = {"illumina8": QMAP_ILLUMINA8, "novaseq4": QMAP_NOVASEQ4}
 
 EXPORTS = [
     "sfq_stream_name", "sfq_ctx_create", "sfq_ctx_destroy", "sfq_last_error", "sfq_ctx_set_table_budget",
@@ -29,6 +31,7 @@ EXPORTS = [
     "sfq_archive_write_segments", "sfq_crc32", "sfq_crc32_combine", "sfq_ctx_set_checksums", "sfq_get_checksums",
     "sfq_set_block_checksums", "sfq_decode_block_range", "sfq_decode_block_range_host",
     "sfq_ctx_set_stats", "sfq_get_text_stats", "sfq_text_stats_merge", "sfq_pack_text_stats", "sfq_unpack_text_stats",
+    "sfq_quality_map_preset", "sfq_quality_map_check", "sfq_map_qualities", "sfq_ctx_set_quality_map", "sfq_get_quality_map_changed",
 ]
 
 
@@ -184,6 +187,12 @@ def lib():
         L.sfq_pack_text_stats.argtypes = [tsp, u8p, u64]
         L.sfq_pack_text_stats.restype = C.c_int64
         L.sfq_unpack_text_stats.argtypes = [u8p, u64, tsp]
+        L.sfq_quality_map_preset.argtypes = [C.c_int, C.c_char_p]
+        L.sfq_quality_map_check.argtypes = [C.c_char_p]
+        L.sfq_map_qualities.argtypes = [vp, u8p, u64, C.c_char_p, C.POINTER(u64)]
+        L.sfq_ctx_set_quality_map.argtypes = [vp, C.c_char_p]
+        L.sfq_get_quality_map_changed.argtypes = [vp]
+        L.sfq_get_quality_map_changed.restype = u64
         _lib = L
     return _lib
 
@@ -230,6 +239,30 @@ def archive_write_segments(path: str, parts, level: int, orig_name: str, tables=
 def crc32_combine(crc_a, crc_b, len_b):
     """zlib's crc32_combine: the CRC-32 of A followed by B from crc(A), crc(B) and len(B) (host only)."""
     return int(lib().sfq_crc32_combine(crc_a & 0xFFFFFFFF, crc_b & 0xFFFFFFFF, int(len_b)))
+
+
+def quality_map_preset(name_or_id) -> bytes:
+    """The 256-byte table of a quality binning preset ("illumina8" / "novaseq4", or QMAP_*); host only."""
+    pid = QMAP_PRESETS.get(name_or_id, name_or_id) if isinstance(name_or_id, str) else int(name_or_id)
+    buf = C.create_string_buffer(256)
+    rc = lib().sfq_quality_map_preset(pid if isinstance(pid, int) else -1, buf)
+    if rc:
+        raise SfqError(rc, "no quality map preset %r" % (name_or_id,))
+    return buf.raw
+
+
+def quality_map_check(lut: bytes) -> int:
+    """SFQ_OK (0) for a table a quality map may use, SFQ_E_ARG (-1) otherwise; host only."""
+    if len(lut) != 256:
+        return -1
+    return int(lib().sfq_quality_map_check(bytes(lut)))
+
+
+def _lut_arg(lut):
+    lut = bytes(lut)
+    if len(lut) != 256:
+        raise SfqError(-1, "a quality map is a table of 256 bytes")
+    return lut
 
 
 def stats_merge(into: TextStats, add: TextStats) -> TextStats:
@@ -355,6 +388,21 @@ class Context:
         if rc < 0:
             self._check(rc)
         return t if rc == 1 else None
+
+    def map_qualities(self, d_ptr, nbytes, lut) -> int:
+        """Every quality byte of the FASTQ text in the device buffer at d_ptr through the 256-byte table, in place; returns the
+        number of bytes whose value changed."""
+        changed = C.c_uint64()
+        self._check(lib().sfq_map_qualities(self._h, C.c_void_p(d_ptr), int(nbytes), _lut_arg(lut), C.byref(changed)))
+        return int(changed.value)
+
+    def set_quality_map(self, lut):
+        """A 256-byte table: encode_host maps the qualities of its text through it before it codes them (LOSSY).  None: off."""
+        self._check(lib().sfq_ctx_set_quality_map(self._h, None if lut is None else _lut_arg(lut)))
+
+    def quality_map_changed(self) -> int:
+        """Bytes changed by the last encode call's quality map (0 where none ran)."""
+        return int(lib().sfq_get_quality_map_changed(self._h))
 
     def set_block_checksums(self, crcs):
         """The expected CRCs of the next decode call's blocks (consumed by it)."""

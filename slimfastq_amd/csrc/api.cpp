@@ -183,6 +183,11 @@ struct sfq_ctx {
     DevBuf stats_acc;
     void* stats_pin = nullptr; size_t stats_pin_cap = 0;
     sfq_text_stats stats; bool stats_valid = false;   // the last encode call's
+    // quality binning (qmap.hip): like the checksums, nothing of this exists until a caller installs a map or calls sfq_map_qualities
+    bool qmap_on = false; u8 qmap_lut[256] = {};      // sfq_ctx_set_quality_map: the *_host encode entry maps its staged text
+    DevBuf qmap_dev;                                  // [0, 256) the table, [256, 264) the changed bytes, from 512 on the pass's scratch
+    void* qmap_pin = nullptr; size_t qmap_pin_cap = 0;        // the same two, page-locked: the table on its way in, the count on its way out
+    u64 qmap_changed = 0;                             // the last encode call's
 };
 
 namespace {
@@ -944,7 +949,7 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
         &ctx->hcnt, &ctx->hfreq, &ctx->rrows, &ctx->rdec, &ctx->rmap, &ctx->rflags, &ctx->rtok, &ctx->ptmp, &ctx->qrows, &ctx->qdec, &ctx->qesc, &ctx->qw, &ctx->csz, &ctx->coff, &ctx->gcnt, &ctx->grows, &ctx->glog, &ctx->gcost, &ctx->gbins, &ctx->gfill, &ctx->gm_T, &ctx->gm_slen, &ctx->gm_boff, &ctx->gm_soff, &ctx->gm_scan, &ctx->gm_stage, &ctx->gm_tok, &ctx->gm_csz, &ctx->gm_idx, &ctx->excf, &ctx->cflags, &ctx->segn, &ctx->segoff, &ctx->segrec, &ctx->pslot, &ctx->plist, &ctx->chn_len, &ctx->chn_off, &ctx->chn_out,
         &ctx->oflags, &ctx->okbytes, &ctx->ofpos, &ctx->okoff, &ctx->ofilt, &ctx->orecmap, &ctx->olist, &ctx->line_off_o, &ctx->ono, &ctx->opiece,
         &ctx->otxt[0], &ctx->otxt[1], &ctx->otxt[2], &ctx->osize_all, &ctx->oroff_all, &ctx->oroff_k, &ctx->ocnt,
-        &ctx->crc_tab, &ctx->crc_tiles, &ctx->crc_grps, &ctx->crc_bounds, &ctx->crc_out, &ctx->stats_acc };
+        &ctx->crc_tab, &ctx->crc_tiles, &ctx->crc_grps, &ctx->crc_bounds, &ctx->crc_out, &ctx->stats_acc, &ctx->qmap_dev };
     for (DevBuf* b : all) release(*b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->pin2) (void)hipHostFree(ctx->pin2);
@@ -952,6 +957,7 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
     for (auto& e : ctx->crc_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->st_crc) (void)hipStreamDestroy(ctx->st_crc);
     if (ctx->stats_pin) (void)hipHostFree(ctx->stats_pin);
+    if (ctx->qmap_pin) (void)hipHostFree(ctx->qmap_pin);
     for (auto& e : ctx->stats_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->st_stats) (void)hipStreamDestroy(ctx->st_stats);
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
@@ -1006,6 +1012,7 @@ static int encode_impl(sfq_ctx* ctx, const u8* d_fastq, u64 nbytes, const sfq_pa
     Settle settle(ctx);
     ctx->crcs.clear(); ctx->text_crc = 0;
     ctx->stats_valid = false;
+    ctx->qmap_changed = 0;
     const int rc = encode_body(ctx, d_fastq, nbytes, pp, d_out, out_cap, res, force_models, priors_only);
     settle.ok = rc == SFQ_OK;
     if (rc == SFQ_OK && !priors_only) ctx->blobs_from_encode = true;       // (sfq_build_priors leaves installed priors: SFQ_PRIOR_GIVEN reads them)
@@ -1820,20 +1827,47 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     return SFQ_OK;
 }
 
+// The entries that take const device text cannot apply an installed quality map, and coding the unmapped text without a word
+// would be the worst they could do: they refuse.
+static int refuse_mapped(sfq_ctx* ctx, const char* entry) {
+    if (!ctx || !ctx->qmap_on) return SFQ_OK;
+    return fail(ctx, SFQ_E_UNSUPPORTED, "%s takes const device text and cannot apply the context's quality map: call sfq_map_qualities on the buffer instead "
+                "(and sfq_ctx_set_quality_map(ctx, NULL))", entry);
+}
+// Queues the quality map of [d, d + n) on the context's stream; the count of changed bytes is in qmap_pin + 256 once the stream is through.
+static int qmap_queue(sfq_ctx* ctx, u8* d, u64 n, const u8* lut) {
+    const QmapScratch q = qmap_scratch(d, n);
+    int rc;
+    if ((rc = reserve(ctx, ctx->qmap_dev, 512 + (size_t)q.bytes))) return rc;
+    if ((rc = reserve_pinned_buf(ctx, ctx->qmap_pin, ctx->qmap_pin_cap, 512))) return rc;
+    u8* dev = (u8*)ctx->qmap_dev.p;
+    u8* pin = (u8*)ctx->qmap_pin;
+    memcpy(pin, lut, 256);
+    memset(pin + 256, 0, 8);
+    HIPC(hipMemcpyAsync(dev, pin, 256, hipMemcpyHostToDevice, ctx->st));
+    HIPC(hipMemsetAsync(dev + 256, 0, 8, ctx->st));
+    launch_quality_map(d, n, dev, dev + 512, (u64*)(dev + 256), ctx->st);
+    HIPC(hipMemcpyAsync(pin + 256, dev + 256, 8, hipMemcpyDeviceToHost, ctx->st));
+    return SFQ_OK;
+}
 int sfq_encode_blocks(sfq_ctx* ctx, const uint8_t* d_fastq, uint64_t nbytes, const sfq_params* params,
                       uint8_t* d_out, uint64_t out_cap, sfq_result* result) {
+    if (int rc = refuse_mapped(ctx, "sfq_encode_blocks")) return rc;
     return encode_impl(ctx, d_fastq, nbytes, params, d_out, out_cap, result, 0);
 }
 int sfq_encode_qlt_blocks(sfq_ctx* ctx, const uint8_t* d_fastq, uint64_t nbytes, const sfq_params* params,
                           uint8_t* d_out, uint64_t out_cap, sfq_result* result) {
+    if (int rc = refuse_mapped(ctx, "sfq_encode_qlt_blocks")) return rc;
     return encode_impl(ctx, d_fastq, nbytes, params, d_out, out_cap, result, SFQ_M_QLT);
 }
 int sfq_build_priors(sfq_ctx* ctx, const uint8_t* d_fastq, uint64_t nbytes, const sfq_params* params) {
+    if (int rc = refuse_mapped(ctx, "sfq_build_priors")) return rc;
     sfq_result res;
     return encode_impl(ctx, d_fastq, nbytes, params, nullptr, 0, &res, 0, true);
 }
 int sfq_count_priors(sfq_ctx* ctx, const uint8_t* d_fastq, uint64_t nbytes, const sfq_params* params, uint32_t sample_scale) {
     if (!ctx || !params) return fail(ctx, SFQ_E_ARG, "null argument");
+    if (int rc = refuse_mapped(ctx, "sfq_count_priors")) return rc;
     if (params->prior_step == SFQ_PRIOR_GIVEN || params->prior_step == SFQ_PRIOR_COUNTS || !params->block_reads)
         return fail(ctx, SFQ_E_ARG, "sfq_count_priors: a sample of this text's own, in the block format (prior_step: a step or SFQ_PRIOR_AUTO)");
     sfq_result res;
@@ -1882,11 +1916,15 @@ int sfq_encode_blocks_host(sfq_ctx* ctx, const uint8_t* h_fastq, uint64_t nbytes
     const u64 bound = sfq_encode_bound(nbytes);
     if ((rc = reserve(ctx, ctx->out_stage, (size_t)bound))) return rc;
     HIPC(hipMemcpyAsync(ctx->in_stage.p, h_fastq, (size_t)nbytes, hipMemcpyHostToDevice, ctx->st));
+    const bool mapped = ctx->qmap_on && nbytes;            // the staged copy is the context's own: it can be mapped where it lies
+    ctx->qmap_changed = 0;
+    if (mapped && (rc = qmap_queue(ctx, (u8*)ctx->in_stage.p, nbytes, ctx->qmap_lut))) return rc;
     rc = encode_impl(ctx, (const u8*)ctx->in_stage.p, nbytes, params, (u8*)ctx->out_stage.p, bound, result, 0);
     if (rc) return rc;
     if (result->total_bytes > out_cap) return fail(ctx, SFQ_E_OVERFLOW, "output needs %llu bytes", (unsigned long long)result->total_bytes);
     HIPC(hipMemcpyAsync(h_out, ctx->out_stage.p, (size_t)result->total_bytes, hipMemcpyDeviceToHost, ctx->st));
     HIPC(hipStreamSynchronize(ctx->st));
+    if (mapped) memcpy(&ctx->qmap_changed, (const u8*)ctx->qmap_pin + 256, 8);
     return SFQ_OK;
 }
 
@@ -2785,6 +2823,30 @@ int sfq_ctx_set_checksums(sfq_ctx* ctx, int on) {
     ctx->crc_on = on != 0;
     return SFQ_OK;
 }
+int sfq_map_qualities(sfq_ctx* ctx, uint8_t* d_fastq, uint64_t nbytes, const uint8_t lut[256], uint64_t* changed) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!lut || (nbytes && !d_fastq)) return fail(ctx, SFQ_E_ARG, "null argument");
+    if (sfq_quality_map_check(lut)) return fail(ctx, SFQ_E_ARG, "quality map: a table must keep every byte below 33 and above 126 and map the others into 33 .. 126");
+    if (changed) *changed = 0;
+    if (!nbytes) return SFQ_OK;
+    HIPC(hipSetDevice(ctx->dev));
+    Settle settle(ctx);
+    int rc;
+    if ((rc = qmap_queue(ctx, d_fastq, nbytes, lut))) return rc;
+    HIPC(hipStreamSynchronize(ctx->st));
+    if (changed) memcpy(changed, (const u8*)ctx->qmap_pin + 256, 8);
+    settle.ok = true;
+    return SFQ_OK;
+}
+int sfq_ctx_set_quality_map(sfq_ctx* ctx, const uint8_t* lut) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!lut) { ctx->qmap_on = false; return SFQ_OK; }
+    if (sfq_quality_map_check(lut)) return fail(ctx, SFQ_E_ARG, "quality map: a table must keep every byte below 33 and above 126 and map the others into 33 .. 126");
+    memcpy(ctx->qmap_lut, lut, 256);
+    ctx->qmap_on = true;
+    return SFQ_OK;
+}
+uint64_t sfq_get_quality_map_changed(const sfq_ctx* ctx) { return ctx ? ctx->qmap_changed : 0; }
 int sfq_ctx_set_stats(sfq_ctx* ctx, int on) {
     if (!ctx) return SFQ_E_ARG;
     ctx->stats_on = on != 0;

@@ -52,6 +52,30 @@ int sfq_unpack_text_stats(const uint8_t* bytes, uint64_t n, sfq_text_stats* out)
     return sfqc::unpack_text_stats(std::vector<uint8_t>(bytes, bytes + n), *out) ? SFQ_OK : SFQ_E_CORRUPT;
 }
 
+// Quality binning: the preset tables and the check of a caller's table (the pass itself: qmap.hip).  Phred+33.
+int sfq_quality_map_preset(int preset, uint8_t lut[256]) {
+    struct Bin { int lo, hi, to; };
+    static const Bin illumina8[] = { {2, 9, 6}, {10, 19, 15}, {20, 24, 22}, {25, 29, 27}, {30, 34, 33}, {35, 39, 37}, {40, 93, 40} };
+    static const Bin novaseq4[] = { {2, 2, 2}, {3, 14, 12}, {15, 29, 23}, {30, 93, 37} };      // synth.cpp kind 2 writes these four
+    if (!lut) return SFQ_E_ARG;
+    const Bin* bins; size_t n;
+    if (preset == SFQ_QMAP_ILLUMINA8) { bins = illumina8; n = sizeof illumina8 / sizeof *illumina8; }
+    else if (preset == SFQ_QMAP_NOVASEQ4) { bins = novaseq4; n = sizeof novaseq4 / sizeof *novaseq4; }
+    else return SFQ_E_ARG;
+    for (int b = 0; b < 256; b++) lut[b] = (uint8_t)b;         // Q0 and Q1 among them: "no call", and the '!' of an N (gens.cpp)
+    for (size_t i = 0; i < n; i++)
+        for (int q = bins[i].lo; q <= bins[i].hi; q++) lut[33 + q] = (uint8_t)(33 + bins[i].to);
+    return SFQ_OK;
+}
+int sfq_quality_map_check(const uint8_t lut[256]) {
+    if (!lut) return SFQ_E_ARG;
+    for (int b = 0; b < 256; b++) {
+        if (b < 33 || b > 126) { if (lut[b] != b) return SFQ_E_ARG; }
+        else if (lut[b] < 33 || lut[b] > 126) return SFQ_E_ARG;
+    }
+    return SFQ_OK;
+}
+
 int sfq_archive_write_segments(const char* path, const char* orig_name, int level, uint32_t tables, int shared_prior,
                                uint32_t n, const sfq_segment* segs) {
     if (!path || !orig_name || (n && !segs) || (tables != SFQ_TABLES_FROZEN && tables != SFQ_TABLES_ADAPTIVE)) return SFQ_E_ARG;

@@ -8,6 +8,8 @@
 //   -g dev    : HIP device
 //   -K        : store the CRC-32 of every block's text ("blk.crc") and of the file (info key "crc32"); a decode checks them
 //   -Y        : count the statistics of the text on the GPU while it is coded and store them ("txt.stat"); -s prints them
+//   -Q name   : LOSSY, encode only: bin the qualities on the GPU before they are coded (illumina8: 8 levels, novaseq4: 4 levels);
+//               info keys "qlt.map" / "qlt.map.changed"
 //   -R F:N    : with -d: records F .. F + N - 1 only (numbered from 0 over the archive) -- the blocks that hold them are decoded, no others
 // All model / coder work happens in libslimfastq_amd.so on the GPU; this file parses arguments, reads and
 // writes files and fills the info page.
@@ -88,6 +90,9 @@ static void usage() {
            "                   decoding checks them and fails on a mismatch (needs the block format: not with -B 0)\n"
            "-Y               : text statistics: count bases, GC / N share, Q20 / Q30 share, read lengths and the mean quality per cycle\n"
            "                   on the GPU while the text is coded, and store them in the archive; -s prints them (works with -B 0 too)\n"
+           "-Q illumina8|novaseq4 : LOSSY: bin the qualities on the GPU before they are coded -- Illumina's 8 levels or NovaSeq's 4\n"
+           "                   (Phred+33; Q0 and Q1 stay) -- the archive holds, checks (-K) and counts (-Y) the binned text; -s names\n"
+           "                   the map and the bytes it changed (encode only; works with -B 0)\n"
            "-R first:count   : with -d: write records first .. first+count-1 only (numbered from 0 over the whole archive; count is\n"
            "                   clipped at the end): only the blocks that hold them are decoded (and, under a base model, what the\n"
            "                   format makes them depend on); with -b: of every job\n"
@@ -122,6 +127,7 @@ struct Opts {
     bool checksum = false;                                             // -K
     bool stats = false;                                                // -Y
     bool range = false; uint64_t r_first = 0, r_count = 0;             // -R first:count
+    int qmap = 0; std::string qmap_name;                               // -Q: SFQ_QMAP_* (0 = none) and its name
 };
 // "FIRST:COUNT", both decimal, COUNT > 0
 static bool parse_range(const char* t, uint64_t& first, uint64_t& count) {
@@ -259,6 +265,10 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     const bool legacy = o.block_reads == 0;
     if (sfq_ctx_set_checksums(ctx, o.checksum ? 1 : 0)) croak("%s", sfq_last_error(ctx));
     if (sfq_ctx_set_stats(ctx, o.stats ? 1 : 0)) croak("%s", sfq_last_error(ctx));
+    uint8_t qlut[256];
+    if (o.qmap && sfq_quality_map_preset(o.qmap, qlut)) croak("-Q: no such preset");
+    if (sfq_ctx_set_quality_map(ctx, o.qmap ? qlut : nullptr)) croak("%s", sfq_last_error(ctx));      // (a -b worker's context: set for every job)
+    uint64_t qmap_changed = 0;                                         // over the slabs
     sfq_params p; memset(&p, 0, sizeof p);
     p.level = o.level; p.block_reads = o.block_reads < 0 ? SFQ_BLOCK_AUTO : (uint32_t)o.block_reads;
     p.prior_step = legacy ? 0 : SFQ_PRIOR_AUTO;                        // warm start needs the block format
@@ -398,6 +408,7 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             }
             if (rc) croak("%s", sfq_last_error(ctx));
             tick("sfq_encode_blocks_host");
+            qmap_changed += sfq_get_quality_map_changed(ctx);
             collect(ctx, res, use, idx, o.checksum, o.stats);
             tick("collect slab");
             writer.join();
@@ -443,6 +454,7 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         const int rc = sfq_encode_blocks_host(ctx, text, use, &p, out.p, bound, &res);
         if (rc) croak("%s", sfq_last_error(ctx));
         tick("sfq_encode_blocks_host");
+        qmap_changed += sfq_get_quality_map_changed(ctx);
         collect(ctx, res, use, idx, o.checksum, o.stats);
         for (int s = 0; s < SFQ_NSTREAMS; s++)
             streams[s].insert(streams[s].end(), out.p + res.stream_offset[s], out.p + res.stream_offset[s] + res.stream_bytes[s]);
@@ -470,6 +482,10 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         a.set("num_records", (long long)idx.records);
         if (!o.quiet && b.extra_hi) a.set("qlt.extra.hi", b.extra_hi);
     } else a.info = idx.info(o.level, orig_name, frozen, false);
+    if (o.qmap) {                                                      // (the reference reads its info page into a map: keys it does not know are no harm)
+        a.set("qlt.map", o.qmap_name);
+        a.set("qlt.map.changed", (long long)qmap_changed);
+    }
     if (streamed) {
         for (auto& s : idx.streams(frozen)) pw.append(pw.stream(s.first), s.second.data(), s.second.size());
         std::string werr;
@@ -681,7 +697,7 @@ int main(int argc, char** argv) {
     Opts o;
     bool statistics = false;
     if (argc == 1) usage();
-    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKY1234u:f:l:B:g:S:T:C:t:R:")) != -1;) {
+    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKY1234u:f:l:B:g:S:T:C:t:R:Q:")) != -1;) {
         switch (opt) {
         case 'u': g_usr = optarg; break;
         case 'f': fil = optarg; break;
@@ -701,6 +717,10 @@ int main(int argc, char** argv) {
         case 'F': o.force_frozen = true; break;
         case 'K': o.checksum = true; break;
         case 'Y': o.stats = true; break;
+        case 'Q':
+            o.qmap_name = optarg;
+            o.qmap = o.qmap_name == "illumina8" ? SFQ_QMAP_ILLUMINA8 : o.qmap_name == "novaseq4" ? SFQ_QMAP_NOVASEQ4 : -1;
+            break;
         case 'R': if (!parse_range(optarg, o.r_first, o.r_count)) usage(); o.range = true; break;
         case 'C': o.chain_reads = strtol(optarg, 0, 0); break;
         case 't': o.io_threads = std::min(64, std::max(1, atoi(optarg))); break;
@@ -713,6 +733,15 @@ int main(int argc, char** argv) {
     o.level = clamp_level(o.level);                                    // clamp at parse time (the reference records the clamped value only)
     if (o.checksum && o.block_reads == 0) {
         fprintf(stderr, "slimfastq: -K (checksums) needs the block format: -B 0 writes the reference's own format-6 file, which has no place for them\n");
+        return 1;
+    }
+
+    if (o.qmap < 0) {
+        fprintf(stderr, "slimfastq: -Q %s: no such quality map (illumina8 or novaseq4)\n", o.qmap_name.c_str());
+        return 1;
+    }
+    if (o.qmap && !g_encode) {
+        fprintf(stderr, "slimfastq: -Q (quality binning) goes with a compress run: it changes the text before it is coded, a decode writes what the archive holds\n");
         return 1;
     }
 

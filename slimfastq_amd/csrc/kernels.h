@@ -272,3 +272,10 @@ void launch_crc_block_bounds(const u64* offs, u64 stride, u32 nblocks, u64 total
 // the three kernels are through; line_off: the index of the text's 4 * nrec lines (line_off[4 * nrec] = n)
 u64  text_stats_acc_bytes();
 void launch_text_stats(const u8* fq, u64 n, const u64* line_off, u64 nrec, void* acc, hipStream_t st);
+
+// Quality binning (qmap.hip): every byte of every 4th line of the text [d, d + n) through the 256-byte table d_lut, in place; the
+// bytes whose value changed are added to *d_changed (zeroed by the caller).  scratch: qmap_scratch(d, n).bytes bytes, 16-byte
+// aligned.  Reads the whole aligned 16-byte units of the text's first and last byte, writes nothing outside the text.
+struct QmapScratch { u64 nspans = 0, cnt_off = 0, before_off = 0, tmp_off = 0, bytes = 0; };
+QmapScratch qmap_scratch(const u8* d, u64 n);
+void launch_quality_map(u8* d, u64 n, const u8* d_lut, u8* scratch, u64* d_changed, hipStream_t st);

@@ -123,6 +123,7 @@ def main(argv=None):
     ap.add_argument("-B", "--block_reads", type=int, default=-1)
     ap.add_argument("-O", "--overwrite", action="store_true")
     ap.add_argument("-K", "--checksum", action="store_true", help="store the CRC-32 of every block and of the file (slimfastq-amd -K)")
+    ap.add_argument("-Q", "--quality_map", choices=("illumina8", "novaseq4"), help="LOSSY: bin the qualities before they are coded (slimfastq-amd -Q)")
     ap.add_argument("-v", "--verbose", action="store_true")
     args = ap.parse_args(argv)
 
@@ -154,7 +155,8 @@ def main(argv=None):
     gpus = [int(g) for g in args.gpus.split(",") if g.strip() != ""] or visible_gpus()
     nworkers = max(1, min(args.count or len(gpus), jobs.qsize()))
     cmd = [args.exe, "-b", "-l", str(args.level)] + (["-B", str(args.block_reads)] if args.block_reads >= 0 else []) + \
-          (["-d"] if args.decompress else []) + (["-O"] if args.overwrite else []) + (["-K"] if args.checksum and not args.decompress else [])
+          (["-d"] if args.decompress else []) + (["-O"] if args.overwrite else []) + (["-K"] if args.checksum and not args.decompress else []) + \
+          (["-Q", args.quality_map] if args.quality_map and not args.decompress else [])
     per_gpu = (nworkers + len(gpus) - 1) // len(gpus)
     if per_gpu > 1:                                  # workers sharing a GPU share its memory: model tables take most of it
         cmd += ["-T", str(max(5, 60 // per_gpu))]
