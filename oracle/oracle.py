@@ -446,14 +446,16 @@ def gm_encode_chains(buf: bytes, goff, glen, table_bits, block_reads, chain_read
     return _take(out, n), sizes, on.value
 
 
-def gm_decode_chains(streams: bytes, sizes, glen, table_bits, block_reads, chain_reads):
-    """The base chains of a call under the match model decoded on the CPU -> the bases' codes (uint8, 0..3), records back to back."""
+def gm_decode_chains(streams: bytes, sizes, glen, table_bits, block_reads, chain_reads, steer=False):
+    """The base chains of a call under the match model decoded on the CPU -> the bases' codes (uint8, 0..3), records back to back.
+    steer: the streams are targets that bases are minted from (sfqo_gm_steer_chains), not streams an encoder wrote."""
     L = lib()
     sizes, ps = _arr(sizes, np.uint32); glen, pl = _arr(glen, np.uint32)
     out = np.zeros(int(glen.sum()), np.uint8)
-    L.sfqo_gm_decode_chains.restype = C.c_int
-    L.sfqo_gm_decode_chains.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p]
-    if L.sfqo_gm_decode_chains(streams, ps, pl, len(glen), table_bits, block_reads, chain_reads, out.ctypes.data_as(C.c_void_p)) != 0:
+    f = L.sfqo_gm_steer_chains if steer else L.sfqo_gm_decode_chains
+    f.restype = C.c_int
+    f.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p]
+    if f(streams, ps, pl, len(glen), table_bits, block_reads, chain_reads, out.ctypes.data_as(C.c_void_p)) != 0:
         raise _err()
     return out
 
@@ -532,3 +534,106 @@ def rec_encode_pre5(buf: bytes, off, length) -> bytes:
     if L.sfqo_rec_encode_pre5(buf, po, pl, len(off), C.byref(out), C.byref(n)) != 0:
         raise _err()
     return _take(out, n)
+
+
+# ---- the range coder's interval clamp (coder.hpp:76-77): counting it, and minting text that takes it (sfq_oracle.c "MINTING") ----
+def rc_clamps(reset=True) -> int:
+    """Times any coder of the oracle took the interval clamp since the last reset."""
+    L = lib()
+    L.sfqo_rc_clamps.restype = C.c_ulonglong
+    L.sfqo_rc_clamps.argtypes = [C.c_int]
+    return int(L.sfqo_rc_clamps(int(reset)))
+
+
+def _adm(adm):
+    if adm is None:
+        return None, None
+    flags = np.zeros(64, np.uint8)
+    flags[np.asarray(sorted(adm), np.int64)] = 1
+    return flags, flags.ctypes.data_as(C.c_void_p)
+
+
+def _line_buffer(off, length):
+    return C.create_string_buffer(int((np.asarray(off, np.uint64) + np.asarray(length, np.uint64)).max()) + 1 if len(off) else 1)
+
+
+def qlt_decode_chains(streams: bytes, sizes, off, length, level, block_reads, chain_reads, frozen_rows, adm=None) -> bytes:
+    """qlt_encode_chains' mirror -> a buffer holding the quality lines at off[i] (zeros elsewhere).  adm: the symbols (quality - 33) the
+    text may hold -- then `streams` are targets that text is minted from."""
+    L = lib()
+    sizes, ps = _arr(sizes, np.uint32); off, po = _arr(off, np.uint64); length, pl = _arr(length, np.uint32)
+    frozen_rows = np.ascontiguousarray(frozen_rows, np.uint32)
+    flags, pa = _adm(adm)
+    dst = _line_buffer(off, length)
+    L.sfqo_qlt_decode_chains.restype = C.c_int
+    L.sfqo_qlt_decode_chains.argtypes = [C.c_char_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t,
+                                         C.c_void_p, C.c_void_p]
+    assert len(sizes) == _nchains(len(off), block_reads, chain_reads) and int(sizes.sum()) <= len(streams)
+    if L.sfqo_qlt_decode_chains(streams, ps, dst, po, pl, len(off), level, block_reads, chain_reads, frozen_rows.ctypes.data_as(C.c_void_p), pa) != 0:
+        raise _err()
+    return dst.raw[:-1]
+
+
+def qlt_decode_segs(streams: bytes, sizes, off, length, other_len, level, seg_len, frozen_rows, adm=None) -> bytes:
+    """qlt_encode_segs' mirror (chains that are segments of one record)."""
+    L = lib()
+    assert len(sizes) == int(seg_counts(length, other_len, seg_len).sum())
+    sizes, ps = _arr(sizes, np.uint32); off, po = _arr(off, np.uint64); length, pl = _arr(length, np.uint32); other_len, pt = _arr(other_len, np.uint32)
+    frozen_rows = np.ascontiguousarray(frozen_rows, np.uint32)
+    flags, pa = _adm(adm)
+    dst = _line_buffer(off, length)
+    L.sfqo_qlt_decode_segs.restype = C.c_int
+    L.sfqo_qlt_decode_segs.argtypes = [C.c_char_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32,
+                                       C.c_void_p, C.c_void_p]
+    assert int(sizes.sum()) <= len(streams)
+    if L.sfqo_qlt_decode_segs(streams, ps, dst, po, pl, pt, len(off), level, seg_len, frozen_rows.ctypes.data_as(C.c_void_p), pa) != 0:
+        raise _err()
+    return dst.raw[:-1]
+
+
+def gen_decode_chains(streams: bytes, sizes, goff, glen, gen_bits, block_reads, chain_reads, step, gen_on, steer=False) -> bytes:
+    """gen_encode_chains' mirror (whole-record chains, generation tables) -> a buffer holding the base lines (ACGT) at goff[i].
+    steer: the streams are targets that bases are minted from (sfqo_gen_steer_chains)."""
+    L = lib()
+    sizes, ps = _arr(sizes, np.uint32); goff, po = _arr(goff, np.uint64); glen, pl = _arr(glen, np.uint32)
+    dst = _line_buffer(goff, glen)
+    f = L.sfqo_gen_steer_chains if steer else L.sfqo_gen_decode_chains
+    f.restype = C.c_int
+    f.argtypes = [C.c_char_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t,
+                                         C.c_uint32, C.c_int]
+    assert len(sizes) == _nchains(len(goff), block_reads, chain_reads) and int(sizes.sum()) <= len(streams)
+    if f(streams, ps, dst, po, pl, len(goff), gen_bits, block_reads, chain_reads, step, int(gen_on)) != 0:
+        raise _err()
+    return dst.raw[:-1]
+
+
+def qlt_steer_blocks(streams: bytes, sizes, off, length, level, block_reads, adm, prior_rows=None) -> bytes:
+    """Adaptive rows: block b's quality lines minted from target stream b, holding only the symbols of adm (block_reads >= records: format
+    6's one stream; prior_rows as for qlt_encode_blocks)."""
+    L = lib()
+    sizes, ps = _arr(sizes, np.uint32); off, po = _arr(off, np.uint64); length, pl = _arr(length, np.uint32)
+    flags, pa = _adm(adm)
+    pr = None
+    if prior_rows is not None:
+        prior_rows = np.ascontiguousarray(prior_rows, np.uint32)
+        pr = prior_rows.ctypes.data_as(C.c_void_p)
+    dst = _line_buffer(off, length)
+    L.sfqo_qlt_steer_blocks.restype = C.c_int
+    L.sfqo_qlt_steer_blocks.argtypes = [C.c_char_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]
+    assert len(sizes) == -(-len(off) // block_reads) and int(sizes.sum()) <= len(streams)
+    if L.sfqo_qlt_steer_blocks(streams, ps, dst, po, pl, len(off), level, block_reads, pr, pa) != 0:
+        raise _err()
+    return dst.raw[:-1]
+
+
+def gen_steer_blocks(streams: bytes, sizes, goff, glen, gen_bits, block_reads) -> bytes:
+    """Adaptive Base2 rows, every block cold: block b's base lines (ACGT) minted from target stream b."""
+    L = lib()
+    sizes, ps = _arr(sizes, np.uint32); goff, po = _arr(goff, np.uint64); glen, pl = _arr(glen, np.uint32)
+    dst = _line_buffer(goff, glen)
+    L.sfqo_gen_steer_blocks.restype = C.c_int
+    L.sfqo_gen_steer_blocks.argtypes = [C.c_char_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t]
+    assert len(sizes) == -(-len(goff) // block_reads) and int(sizes.sum()) <= len(streams)
+    if L.sfqo_gen_steer_blocks(streams, ps, dst, po, pl, len(goff), gen_bits, block_reads) != 0:
+        raise _err()
+    return dst.raw[:-1]

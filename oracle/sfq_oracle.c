@@ -343,6 +343,10 @@ void sfqo_archive_free(sfqo_archive* a) {
 
 typedef struct { u64 low, code; u32 range; wr* out; rd* in; } rcoder;
 
+/* How often a coder of this file (RCoder here, the chains' chenc / chdec further down) took the interval clamp of coder.hpp:76-77 */
+static unsigned long long g_rc_clamps;
+unsigned long long sfqo_rc_clamps(int reset) { const unsigned long long n = g_rc_clamps; if (reset) g_rc_clamps = 0; return n; }
+
 static void rc_init_save(rcoder* c, wr* out) { c->out = out; c->in = NULL; c->low = 0; c->range = (u32)-1; c->code = 0; }  /* coder.hpp:34-39 */
 static void rc_init_load(rcoder* c, rd* in) {                                 /* coder.hpp:41-49 */
     c->in = in; c->out = NULL; c->low = 0; c->range = (u32)-1; c->code = 0;
@@ -360,8 +364,10 @@ static inline void rc_encode(rcoder* c, u32 cum, u32 freq, u32 tot) {         /*
     c->range *= freq;
     int guard = 0;
     while (c->range < TOP) {
-        if ((c->low ^ (c->low + c->range)) & (0xffULL << 56))
+        if ((c->low ^ (c->low + c->range)) & (0xffULL << 56)) {
             c->range = (((u32)c->low | (u32)(TOP - 1)) - (u32)c->low);
+            g_rc_clamps++;
+        }
         wr_put(c->out, (u8)(c->low >> 56));
         c->range <<= 8;
         c->low   <<= 8;
@@ -382,8 +388,10 @@ static inline void rc_decode(rcoder* c, u32 cum, u32 freq, u32 tot) {         /*
     c->range *= freq;
     int guard = 0;
     while (c->range < TOP) {
-        if ((c->low ^ (c->low + c->range)) & (0xffULL << 56))
+        if ((c->low ^ (c->low + c->range)) & (0xffULL << 56)) {
             c->range = (((u32)c->low | (u32)(TOP - 1)) - (u32)c->low);
+            g_rc_clamps++;
+        }
         c->code <<= 8;
         c->code |= rd_get(c->in);
         c->range <<= 8;
@@ -1593,7 +1601,7 @@ static void ch_put(chenc* c, u8 b) {
 static void ch_renorm(chenc* c) {                                             /* coder.hpp:74-80 */
     int guard = 0;
     while (c->range < TOP) {
-        if ((c->low ^ (c->low + c->range)) & (0xffULL << 56)) c->range = (((u32)c->low | (u32)(TOP - 1)) - (u32)c->low);
+        if ((c->low ^ (c->low + c->range)) & (0xffULL << 56)) { c->range = (((u32)c->low | (u32)(TOP - 1)) - (u32)c->low); g_rc_clamps++; }
         ch_put(c, (u8)(c->low >> 56));
         c->range <<= 8; c->low <<= 8;
         if (++guard > 64) { fail("coder stuck"); return; }
@@ -2079,19 +2087,28 @@ static long long gm_encode_x(const u8* base, const u64* goff, const u32* glen, s
 }
 /* ---- the way back (CPU; what tests/test_oracle.py checks the rule's decodability with -- the product's decoder is gm.hip) ----
    A chain's stream read as RCoder reads (coder.hpp:40-48, 83-102): the four elided zero bytes, then the stored ones, zeros behind the end. */
-typedef struct { const u8* p; size_t n, pos; u64 low, code; u32 range; } chdec;
+/* steer (tests only; the sfqo_*_steer_* entries below): the stream is not one an encoder wrote but a TARGET the text is
+   minted from -- where the symbol taken does not hold the code value (the caller took the nearest one it admits, the value lies in the gap
+   range / tot leaves, or the clamp cut the interval below it) the value is put back into the middle of the interval instead of decoding garbage from
+   there on.  The (low, range) states are the ones an encoder of the text that comes out runs through, so it clamps where this decoder does. */
+typedef struct { const u8* p; size_t n, pos; u64 low, code; u32 range; int steer; } chdec;
 static u8 chd_get(chdec* d) { const u8 b = d->pos < d->n ? d->p[d->pos] : 0; d->pos++; return b; }
 static void chd_init(chdec* d, const u8* p, size_t n) {
-    d->p = p; d->n = n; d->pos = 0; d->low = 0; d->range = (u32)-1; d->code = 0;
+    d->p = p; d->n = n; d->pos = 0; d->low = 0; d->range = (u32)-1; d->code = 0; d->steer = 0;
     for (int i = 0; i < 4; i++) d->code = (d->code << 8) | chd_get(d);        /* (code's first four bytes are the elided zeros) */
 }
-static u32 chd_freq(chdec* d, u32 tot) { d->range /= tot; return (u32)(d->code / d->range); }
+static u32 chd_freq(chdec* d, u32 tot) { d->range /= tot; const u64 q = d->code / d->range; return d->steer && q > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)q; }
 static void chd_decode(chdec* d, u32 cum, u32 freq) {
     const u32 temp = cum * d->range;
     d->low += temp; d->code -= temp; d->range *= freq;
+    if (d->steer && d->code >= d->range) d->code = d->range >> 1;
     int guard = 0;
     while (d->range < TOP) {
-        if ((d->low ^ (d->low + d->range)) & (0xffULL << 56)) d->range = (((u32)d->low | (u32)(TOP - 1)) - (u32)d->low);
+        if ((d->low ^ (d->low + d->range)) & (0xffULL << 56)) {
+            d->range = (((u32)d->low | (u32)(TOP - 1)) - (u32)d->low);
+            g_rc_clamps++;
+            if (d->steer && d->code >= d->range) d->code = d->range >> 1;
+        }
         d->code = (d->code << 8) | chd_get(d);
         d->range <<= 8; d->low <<= 8;
         if (++guard > 64) { fail("decoder stuck"); return; }
@@ -2132,7 +2149,7 @@ static void gm_unwalk(chdec* d, u8* st, const u64* T, int tb, u64 lim, u64 q0, s
 /* The chains of a call under the match model (gen_on = 1; whole-record chains) back to the bases' codes: codes[sum glen] in record order.
    The decoder knows the line lengths (the "usr" streams give them) and the chains' sizes ("chn.idx"); it indexes a generation
    when it has decoded it -- and must arrive at the bases the encoder started from.  Returns 0, or -1. */
-int sfqo_gm_decode_chains(const u8* streams, const u32* sizes, const u32* glen, size_t nrec, int tb, size_t block_reads, size_t chain_reads, u8* codes) {
+static int gm_decode_x(const u8* streams, const u32* sizes, const u32* glen, size_t nrec, int tb, size_t block_reads, size_t chain_reads, u8* codes, int steer) {
     g_failed = 0; g_err[0] = 0;
     const size_t nblocks = (nrec + block_reads - 1) / block_reads;
     size_t bound[48];
@@ -2152,7 +2169,7 @@ int sfqo_gm_decode_chains(const u8* streams, const u32* sizes, const u32* glen, 
             const size_t b0 = REC_OF(b), b1 = REC_OF(b + 1);
             for (size_t r0 = b0; r0 < b1; r0 += chain_reads, nc++) {
                 const size_t r1 = r0 + chain_reads < b1 ? r0 + chain_reads : b1;
-                chdec d; chd_init(&d, streams + at, sizes[nc]);
+                chdec d; chd_init(&d, streams + at, sizes[nc]); d.steer = steer;
                 for (size_t r = r0; r < r1; r++) gm_unwalk(&d, st, T, tb, lim, soff[r], glen[r]);
                 at += sizes[nc];
             }
@@ -2166,6 +2183,14 @@ int sfqo_gm_decode_chains(const u8* streams, const u32* sizes, const u32* glen, 
     return g_failed ? -1 : 0;
 }
 
+int sfqo_gm_decode_chains(const u8* streams, const u32* sizes, const u32* glen, size_t nrec, int tb, size_t block_reads, size_t chain_reads, u8* codes) {
+    return gm_decode_x(streams, sizes, glen, nrec, tb, block_reads, chain_reads, codes, 0);
+}
+/* the same with the chains' streams as TARGETS that bases are minted from (tests only; "MINTING" below) */
+int sfqo_gm_steer_chains(const u8* streams, const u32* sizes, const u32* glen, size_t nrec, int tb, size_t block_reads, size_t chain_reads, u8* codes) {
+    return gm_decode_x(streams, sizes, glen, nrec, tb, block_reads, chain_reads, codes, 1);
+}
+
 long long sfqo_gm_encode_chains(const u8* base, const u64* goff, const u32* glen, size_t nrec, int table_bits, size_t block_reads,
                                 size_t chain_reads, u8** out, size_t* out_len, u32* sizes, int* gen_on) {
     return gm_encode_x(base, goff, glen, nrec, table_bits, block_reads, chain_reads, out, out_len, sizes, gen_on, 0, NULL);
@@ -2173,6 +2198,204 @@ long long sfqo_gm_encode_chains(const u8* base, const u64* goff, const u32* glen
 long long sfqo_gm_encode_segs(const u8* base, const u64* goff, const u32* glen, const u32* other_len, size_t nrec, int table_bits, size_t block_reads,
                               u32 seg_len, u8** out, size_t* out_len, u32* sizes, int* gen_on) {
     return gm_encode_x(base, goff, glen, nrec, table_bits, block_reads, 1, out, out_len, sizes, gen_on, seg_len, other_len);
+}
+
+/* ---- the way back for the quality chains and the generation tables' base chains, and MINTING (tests only) -----------------------------
+   The interval clamp of coder.hpp:76-77 runs once in 2^32 renormalisations, so no ordinary text reaches it.  A decoder fed a crafted
+   stream does (a byte X != 0xFF, six 0xFF, a 0x00: the code value just below a multiple of 2^56 when X is the top byte), and the text it
+   writes makes an ENCODER clamp in the same places.  Two things keep that text legal: `adm` (64 flags: the symbols the text may hold; the
+   decoder takes the admitted symbol nearest to the code value and chdec's steer mode moves the value into it), and the same mode's repair
+   of a value left outside its interval.  adm = NULL is the plain decoder of what sfqo_qlt_encode_chains / _segs wrote. */
+static u32 steer_choose(u32 q, const u32* cum, const u32* f, const u8* adm) {      /* the symbol whose [cum, cum + f) holds q, else the nearest admitted one; 64: none */
+    u32 best = 64, bd = ~0u;
+    for (u32 s2 = 0; s2 < 64; s2++) {
+        if ((adm && !adm[s2]) || !f[s2]) continue;
+        const u32 d = q < cum[s2] ? cum[s2] - q : q >= cum[s2] + f[s2] ? q - (cum[s2] + f[s2]) + 1 : 0;
+        if (d < bd) { bd = d; best = s2; }
+    }
+    return best;
+}
+typedef struct { chdec* d; const u32* rows; const u8* adm; log64* ranger; } qpick;
+static u8 qfz_pick(qpick* k, u32 ctx) {                                        /* a frozen row (qfz_cb's mirror) */
+    const u32* row = k->rows + (size_t)ctx * 64;
+    u32 cum[64], f[64];
+    for (int i = 0; i < 64; i++) { cum[i] = row[i] & 0xffff; f[i] = row[i] >> 16; }
+    const u32 q = chd_freq(k->d, 65536);
+    const u32 sym = steer_choose(q, cum, f, k->adm);
+    if (sym >= 64 || (!k->adm && (q < cum[sym] || q >= cum[sym] + f[sym]))) { fail("corrupt qlt chain"); return 0; }
+    chd_decode(k->d, cum[sym], f[sym]);
+    if (sym < LAST_QLT) return (u8)sym;
+    u32 b = chd_freq(k->d, 65536) >> 8;                                        /* the escape row: all 256 values alike */
+    if (b > 255) { fail("corrupt qlt chain"); b = 255; }
+    chd_decode(k->d, b << 8, 256);
+    return (u8)b;
+}
+static u8 qad_pick(qpick* k, u32 ctx) {                                        /* an adaptive row (l64_get's arithmetic, l64_put's bookkeeping); no escapes: adm[63] = 0 */
+    log64* r = &k->ranger[ctx];
+    u32 cum[64], f[64], c = 0;
+    for (u32 i = 0; i < r->iend; i++) { const u32 sym = r->syms[i]; cum[sym] = c; f[sym] = r->freq[i] + 1u; c += f[sym]; }
+    for (u32 sym = r->iend; sym < 64; sym++) { cum[sym] = c + (sym - r->iend); f[sym] = 1; }        /* not seen yet: l64_put appends them in order, freq 0 */
+    const u32 q = chd_freq(k->d, r->total + L64_NSYM);
+    const u32 sym = steer_choose(q, cum, f, k->adm);
+    if (sym >= LAST_QLT) { fail("qlt steer: no admitted symbol below the escape"); return 0; }
+    chd_decode(k->d, cum[sym], f[sym]);
+    u32 i = 0;
+    if (r->iend <= sym) for (; r->iend <= sym; r->iend++) r->syms[r->iend] = (u8)r->iend;
+    for (; r->syms[i] != sym; i++);
+    l64_update(r, (int)i);
+    return (u8)sym;
+}
+static void qlt_unwalk(u8* buf, size_t size, int level, u8 (*pick)(qpick*, u32), qpick* k) {       /* qlt_load's walk */
+    if (level <= 2) {
+        u32 mask = level == 1 ? 0xFFF : 0xFFFF, last = 0;
+        for (u8* p = buf; p < buf + size && !g_failed; p++) { const u8 b = pick(k, last); *p = (u8)('!' + b); last = (b | (last << 6)) & mask; }
+        return;
+    }
+    u32 last = 0, delta = 5, di = 0; u8 q1 = 0, q2 = 0;
+    for (u8* p = buf; p < buf + size && !g_failed; p++) {
+        const u8 b = pick(k, last);
+        *p = (u8)('!' + b);
+        if (++di & 1) { last = calc_last_delta(&delta, b, q1, q2); q2 = b; }
+        else          { last = calc_last_delta(&delta, b, q2, q1); q1 = b; }
+    }
+}
+/* sfqo_qlt_encode_chains' mirror: the chains' streams back to back and their sizes -> the quality lines at dst + off[i] */
+int sfqo_qlt_decode_chains(const u8* streams, const u32* sizes, u8* dst, const u64* off, const u32* len, size_t nrec, int level, size_t block_reads,
+                           size_t chain_reads, const u32* frozen_rows, const u8* adm) {
+    g_failed = 0; g_err[0] = 0;
+    size_t nc = 0, at = 0;
+    for (size_t b0 = 0; b0 < nrec; b0 += block_reads) {
+        const size_t b1 = b0 + block_reads < nrec ? b0 + block_reads : nrec;
+        for (size_t r0 = b0; r0 < b1; r0 += chain_reads, nc++) {
+            const size_t r1 = r0 + chain_reads < b1 ? r0 + chain_reads : b1;
+            chdec d; chd_init(&d, streams + at, sizes[nc]); if (adm) d.steer = 1;
+            qpick k = { &d, frozen_rows, adm, NULL };
+            for (size_t i = r0; i < r1 && !g_failed; i++) qlt_unwalk(dst + off[i], len[i], level, qfz_pick, &k);
+            at += sizes[nc];
+        }
+    }
+    return g_failed ? -1 : 0;
+}
+/* sfqo_qlt_encode_segs' mirror */
+int sfqo_qlt_decode_segs(const u8* streams, const u32* sizes, u8* dst, const u64* off, const u32* len, const u32* other_len, size_t nrec, int level,
+                         u32 seg_len, const u32* frozen_rows, const u8* adm) {
+    g_failed = 0; g_err[0] = 0;
+    size_t nc = 0, at = 0;
+    for (size_t r = 0; r < nrec; r++) {
+        size_t n, L; seg_geometry(len[r], other_len[r], seg_len, &n, &L);
+        for (size_t sg = 0; sg < n; sg++, nc++) {
+            const size_t lo = sg * L < len[r] ? sg * L : len[r];
+            const size_t cnt = len[r] - lo < L ? len[r] - lo : L;
+            chdec d; chd_init(&d, streams + at, sizes[nc]); if (adm) d.steer = 1;
+            qpick k = { &d, frozen_rows, adm, NULL };
+            if (!g_failed) qlt_unwalk(dst + off[r] + lo, cnt, level, qfz_pick, &k);
+            at += sizes[nc];
+        }
+    }
+    return g_failed ? -1 : 0;
+}
+/* Adaptive rows (format 6: one block of all records, prior_rows = NULL; the block format: sfqo_qlt_encode_blocks' blocks): block b's quality
+   lines minted from target stream b (chain framing: the four leading zero bytes are not part of it, zeros behind its end) */
+int sfqo_qlt_steer_blocks(const u8* streams, const u32* sizes, u8* dst, const u64* off, const u32* len, size_t nrec, int level, size_t block_reads,
+                          const u32* prior_rows, const u8* adm) {
+    g_failed = 0; g_err[0] = 0;
+    if (!adm) { fail("qlt steer: no admitted symbols"); return -1; }
+    qltm q; qlt_alloc(&q, level);
+    size_t nb = 0, at = 0;
+    for (size_t r0 = 0; r0 < nrec && !g_failed; r0 += block_reads, nb++) {
+        const size_t r1 = r0 + block_reads < nrec ? r0 + block_reads : nrec;
+        if (prior_rows) for (size_t c = 0; c < q.cnt; c++) row_from_prior(&q.ranger[c], prior_rows + c * 66);
+        else memset(q.ranger, 0, q.cnt * sizeof(log64));
+        chdec d; chd_init(&d, streams + at, sizes[nb]); d.steer = 1;
+        qpick k = { &d, NULL, adm, q.ranger };
+        for (size_t i = r0; i < r1 && !g_failed; i++) qlt_unwalk(dst + off[i], len[i], level, qad_pick, &k);
+        at += sizes[nb];
+    }
+    free(q.ranger);
+    return g_failed ? -1 : 0;
+}
+/* The same for the bases under adaptive Base2 rows (gen_save's walk; every block starts cold): letters ACGT at dst + goff[i] */
+int sfqo_gen_steer_blocks(const u8* streams, const u32* sizes, u8* dst, const u64* goff, const u32* glen, size_t nrec, int gen_bits, size_t block_reads) {
+    g_failed = 0; g_err[0] = 0;
+    genm g; gen_alloc(&g, gen_bits);
+    size_t nb = 0, at = 0;
+    for (size_t r0 = 0; r0 < nrec && !g_failed; r0 += block_reads, nb++) {
+        const size_t r1 = r0 + block_reads < nrec ? r0 + block_reads : nrec;
+        if (nb) for (size_t i = 0; i <= g.mask; i++) g.ranger[i].v = B2_INIT;
+        chdec d; chd_init(&d, streams + at, sizes[nb]); d.steer = 1;
+        for (size_t k = r0; k < r1 && !g_failed; k++) {
+            u32 last = 0x007616c7;
+            for (u32 i = 0; i < glen[k]; i++) {
+                last &= (u32)g.mask;
+                base2* r = &g.ranger[last];
+                const u32 q = chd_freq(&d, (u32)((r->f[0] + r->f[1]) + (r->f[2] + r->f[3])));
+                u32 cum = 0, b = 0;
+                for (; b < 3 && q >= cum + r->f[b]; b++) cum += r->f[b];
+                chd_decode(&d, cum, r->f[b]);
+                b2_update(r, (int)b);
+                dst[goff[k] + i] = (u8)"ACGT"[b];
+                last = (last << 2) + b;
+            }
+        }
+        at += sizes[nb];
+    }
+    free(g.ranger);
+    return g_failed ? -1 : 0;
+}
+/* sfqo_gen_encode_chains' mirror (whole-record chains, the generation tables of Base2 rows; gen_on as the encoder decided it): letters ACGT at
+   dst + goff[i].  A generation's rows are counted from the generations decoded before it, as gen_encode_chains_x counts them from the text. */
+static void gunfz_line(chdec* d, const u32* rows, u32 mask, u8* line, u32 n) {
+    u32 last = 0x007616c7u;
+    for (u32 i = 0; i < n; i++) {
+        const u32 v = rows ? rows[last & mask] : B2_INIT;
+        const u32 f[4] = { v & 0xff, (v >> 8) & 0xff, (v >> 16) & 0xff, v >> 24 };
+        const u32 q = chd_freq(d, f[0] + f[1] + f[2] + f[3]);
+        u32 cum = 0, b = 0;
+        for (; b < 3 && q >= cum + f[b]; b++) cum += f[b];
+        chd_decode(d, cum, f[b]);
+        line[i] = (u8)"ACGT"[b];
+        last = (last << 2) | b;
+    }
+}
+static int gen_decode_x(const u8* streams, const u32* sizes, u8* dst, const u64* goff, const u32* glen, size_t nrec, int gen_bits, size_t block_reads,
+                        size_t chain_reads, u32 step, int gen_on, int steer) {
+    g_failed = 0; g_err[0] = 0;
+    const size_t nblocks = (nrec + block_reads - 1) / block_reads;
+    const size_t nctx = (size_t)1 << gen_bits; const u32 mask = (u32)nctx - 1;
+    size_t bound[48];
+    const size_t ngen = gen_bounds(nblocks, bound);
+    if (gen_on && ngen < 3) { fail("gen decode: tables on with %zu generations", ngen); return -1; }
+    u32* cnt = xcalloc(nctx * 4, 4);
+    u32* rows = gen_on ? xmalloc(nctx * 4) : NULL;
+#define REC_OF(b) ((b) * block_reads < nrec ? (b) * block_reads : nrec)
+    size_t at = 0, nc = 0;
+    for (size_t g = 0; g < ngen && !g_failed; g++) {
+        if (gen_on && g >= 2) for (size_t c = 0; c < nctx; c++) rows[c] = gen_row(cnt + c * 4, step);
+        for (size_t b = bound[g]; b < bound[g + 1]; b++) {
+            const size_t b0 = REC_OF(b), b1 = REC_OF(b + 1);
+            for (size_t r0 = b0; r0 < b1; r0 += chain_reads, nc++) {
+                const size_t r1 = r0 + chain_reads < b1 ? r0 + chain_reads : b1;
+                chdec d; chd_init(&d, streams + at, sizes[nc]); d.steer = steer;
+                for (size_t r = r0; r < r1; r++) gunfz_line(&d, gen_on && g >= 2 ? rows : NULL, mask, dst + goff[r], glen[r]);
+                at += sizes[nc];
+            }
+        }
+        if (gen_on && g + 1 < ngen) {
+            gcount gc = { cnt, NULL, 0, 0, 0 };
+            gen_walk_s(dst, goff, glen, REC_OF(bound[g]), REC_OF(bound[g + 1]), gen_count_stride((bound[g + 1] - bound[g]) * block_reads), mask, gcount_cb, &gc);
+        }
+    }
+#undef REC_OF
+    free(cnt); free(rows);
+    return g_failed ? -1 : 0;
+}
+int sfqo_gen_decode_chains(const u8* streams, const u32* sizes, u8* dst, const u64* goff, const u32* glen, size_t nrec, int gen_bits, size_t block_reads,
+                           size_t chain_reads, u32 step, int gen_on) {
+    return gen_decode_x(streams, sizes, dst, goff, glen, nrec, gen_bits, block_reads, chain_reads, step, gen_on, 0);
+}
+int sfqo_gen_steer_chains(const u8* streams, const u32* sizes, u8* dst, const u64* goff, const u32* glen, size_t nrec, int gen_bits, size_t block_reads,
+                          size_t chain_reads, u32 step, int gen_on) {                /* the streams are targets */
+    return gen_decode_x(streams, sizes, dst, goff, glen, nrec, gen_bits, block_reads, chain_reads, step, gen_on, 1);
 }
 
 /* ---- frozen tables: the base exceptions as adaptive Rice codes (round 4; chains.hip k_gen_exc_r) -------------------------

@@ -123,6 +123,26 @@ long long sfqo_gm_encode_segs(const uint8_t* base, const uint64_t* goff, const u
                               uint32_t seg_len, uint8_t** out, size_t* out_len, uint32_t* sizes, int* gen_on);
 /* the way back on the CPU (whole-record chains of a call that took the model): the bases' codes 0..3, codes[sum glen]; 0 or -1 */
 int sfqo_gm_decode_chains(const uint8_t* streams, const uint32_t* sizes, const uint32_t* glen, size_t nrec, int table_bits, size_t block_reads, size_t chain_reads, uint8_t* codes);
+/* the way back on the CPU for the quality chains (adm = NULL) and for base chains under the generation tables; with adm (64 flags: the
+   symbols the text may hold) and in the *_steer_* entries the streams are TARGETS that legal text is minted from, not streams an encoder
+   wrote (sfq_oracle.c "MINTING"): test input that makes an encoder take the range coder's interval clamp (coder.hpp:76-77) */
+int sfqo_qlt_decode_chains(const uint8_t* streams, const uint32_t* sizes, uint8_t* dst, const uint64_t* off, const uint32_t* len, size_t nrec, int level,
+                           size_t block_reads, size_t chain_reads, const uint32_t* frozen_rows, const uint8_t* adm);
+int sfqo_qlt_decode_segs(const uint8_t* streams, const uint32_t* sizes, uint8_t* dst, const uint64_t* off, const uint32_t* len, const uint32_t* other_len,
+                         size_t nrec, int level, uint32_t seg_len, const uint32_t* frozen_rows, const uint8_t* adm);
+int sfqo_gen_decode_chains(const uint8_t* streams, const uint32_t* sizes, uint8_t* dst, const uint64_t* goff, const uint32_t* glen, size_t nrec, int gen_bits,
+                           size_t block_reads, size_t chain_reads, uint32_t step, int gen_on);
+/* adaptive rows: block b's quality lines / base lines minted from target stream b (block_reads >= nrec: format 6's single stream) */
+int sfqo_qlt_steer_blocks(const uint8_t* streams, const uint32_t* sizes, uint8_t* dst, const uint64_t* off, const uint32_t* len, size_t nrec, int level,
+                          size_t block_reads, const uint32_t* prior_rows, const uint8_t* adm);
+int sfqo_gen_steer_blocks(const uint8_t* streams, const uint32_t* sizes, uint8_t* dst, const uint64_t* goff, const uint32_t* glen, size_t nrec, int gen_bits,
+                          size_t block_reads);
+/* sfqo_gm_decode_chains / sfqo_gen_decode_chains with the chains' streams as targets that bases are minted from */
+int sfqo_gm_steer_chains(const uint8_t* streams, const uint32_t* sizes, const uint32_t* glen, size_t nrec, int table_bits, size_t block_reads, size_t chain_reads, uint8_t* codes);
+int sfqo_gen_steer_chains(const uint8_t* streams, const uint32_t* sizes, uint8_t* dst, const uint64_t* goff, const uint32_t* glen, size_t nrec, int gen_bits,
+                          size_t block_reads, size_t chain_reads, uint32_t step, int gen_on);
+/* times any coder of the oracle took the interval clamp (coder.hpp:76-77) since the last reset */
+unsigned long long sfqo_rc_clamps(int reset);
 /* frozen tables, round 4: a block's three base-exception lists ("gen.Ns", "gen.Nn", "gen.lc") as adaptive Rice codes
    (chains.hip k_gen_exc_r; NOT the reference's XFile coding: DESIGN.md 4.10) and the way back */
 int sfqo_exc_rice_block(const uint8_t* base, const uint64_t* goff, const uint32_t* glen, const uint64_t* qoff, const uint32_t* qlen, size_t nrec,
