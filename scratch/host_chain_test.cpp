@@ -26,7 +26,7 @@ int main() {
             else if (mode == 1) { tot = 12; freq = 3; cum = 3 * (rand() % 4); }
             else { tot = 4 + rand() % 1017; freq = 1 + rand() % (tot < 256 ? tot : 255); if (freq > tot) freq = tot; cum = rand() % (tot - freq + 1); }
             if (mode == 0) { if (valid) a.encode16(cum, freq); b.encode16_if(valid ? ~0u : 0u, cum, freq); }
-            else { const u32 rc = fz_recip(tot); if (valid) a.encode(cum, freq, tot, rc); b.encode_if(valid ? ~0u : 0u, cum, freq, tot, rc); }
+            else { const u32 rc = rc_recip(tot); if (valid) a.encode(cum, freq, tot, rc); b.encode_if(valid ? ~0u : 0u, cum, freq, tot, rc); }
             if (++since == 4) { b.drain(); since = 0; }
         }
         const u32 s1 = a.finish(), s2 = b.finish();

@@ -988,7 +988,7 @@ __global__ __launch_bounds__(THREADS) void k_gen_encode_c(ChainArgs a, u32 c0, u
     __shared__ u32 rcp[FLAT ? 1 : 1024];                      // reciprocals of the row totals (<= 1020)
     __shared__ u8 lut[256];                                   // character -> code (gen_code_of)
     __shared__ u32 ring[LaneEncB<THREADS, GEN_RING>::LDS_DWORDS];
-    if constexpr (!FLAT) for (u32 i = threadIdx.x; i < 1024; i += THREADS) rcp[i] = i ? fz_recip(i) : 0u;
+    if constexpr (!FLAT) for (u32 i = threadIdx.x; i < 1024; i += THREADS) rcp[i] = i ? rc_recip(i) : 0u;
     for (u32 i = threadIdx.x; i < 256; i += THREADS) lut[i] = (u8)(gen_code_of(i) | (is_lower_base(i) ? 0x20u : 0u));    // 0x20: a lowercase base ("gen.lc")
     __syncthreads();
     const u32 c = c0 + blockIdx.x * THREADS + threadIdx.x;
@@ -1009,7 +1009,7 @@ __global__ __launch_bounds__(THREADS) void k_gen_encode_c(ChainArgs a, u32 c0, u
             a.exc_flag, cp.sub_lo, cp.sub_len);
     } else if (FLAT || !__any(rows != nullptr)) {
         // every lane of the wave codes with the initial row (3, 3, 3, 3): cum = 3 * code, freq 3 of 12, no lookups
-        const u32 r12 = fz_recip(12u);
+        const u32 r12 = rc_recip(12u);
         illegal = walk_bases_b(a, cp.r0, cp.nrec, live ? d->solid : 0u, 0u, lut, [&](u32, u32) {},
             [&](u32, u32 code, u32 vm) { rc.encode_if(vm, 3u * code, 3u, 12u, r12); },
             [&]() { rc.drain(); }, a.exc_flag, cp.sub_lo, cp.sub_len);
@@ -1221,7 +1221,7 @@ __device__ __forceinline__ u32 b2_pick(u32 v, LaneDecQ& rc, const u32* rcp) {
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void k_gen_decode_c(ChainArgs a, DecodeArgs da, u32 c0, u32 c1 /* the chains [c0, c1) */) {
     __shared__ u32 rcp[1024];
-    for (u32 i = threadIdx.x; i < 1024; i += THREADS) rcp[i] = i ? fz_recip(i) : 0u;
+    for (u32 i = threadIdx.x; i < 1024; i += THREADS) rcp[i] = i ? rc_recip(i) : 0u;
     __syncthreads();
     const u32 c = c0 + blockIdx.x * THREADS + threadIdx.x;
     if (c >= c1) return;
@@ -1232,7 +1232,7 @@ __global__ __launch_bounds__(THREADS) void k_gen_decode_c(ChainArgs a, DecodeArg
     const u32 alphabet = d->solid ? 0x33323130u /* "0123" */ : 0x54474341u /* "ACGT" */;    // gens.cpp:173-178
     const u32 mask = (1u << d->gen_bits) - 1u;
     const u32 INIT = 0x007616c7u;                                                           // gens.cpp:139
-    const u32 r12 = fz_recip(12u);
+    const u32 r12 = rc_recip(12u);
     u32 n_next = cp.nrec ? da.slen[cp.r0] : 0u; u64 off_next = cp.nrec ? da.soff[cp.r0] : 0ull;      // a record's length and place, a record ahead
     if (a.seg_len) {                                         // a segment of one record: its part of the base line
         const u32 ql = da.qlen[cp.r0];

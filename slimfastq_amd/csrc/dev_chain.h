@@ -21,9 +21,14 @@
 #define FZ_FREQ(e) ((e) >> 16)
 #define FZ_MAX_TOT 65535u
 
-__device__ __forceinline__ u32 fz_recip(u32 tot) {      // floor(2^32 / tot) for tot >= 2; tot == 1 keeps 2^32 - 1
-    const u32 m0 = 0xFFFFFFFFu / tot;
-    return (tot != 1 && (0xFFFFFFFFu - m0 * tot) == tot - 1) ? m0 + 1 : m0;
+// The flush of the framing above for a coder that has produced n bytes (the four elided ones included): the value whose top
+// five bytes are written, and tz = how many of the five are trailing zeros.
+__device__ __forceinline__ u64 chain_flush(u64 low, u32 n, u32& tz, u32& err) {
+    const u64 v = (low + 0xFFFFFFull) & ~0xFFFFFFull;
+    if (n < 4 && (v >> (32 + 8 * n))) err = 1;            // cannot happen: the elided bytes are zero (v < 2^(32 + 8 n))
+    const u32 top5_lo = (u32)(v >> 24);                  // flush bytes 1..4 (byte 0 = v >> 56)
+    if (top5_lo == 0) tz = (v >> 56) ? 4u : 5u; else tz = ((u32)__builtin_ctz(top5_lo)) >> 3;
+    return v;
 }
 
 struct LaneEnc {
@@ -40,20 +45,10 @@ struct LaneEnc {
         n++;
         if ((n & 3u) == 0 && n > 4 && n - 4 <= cap) *reinterpret_cast<u32*>(out + n - 8) = acc;
     }
-    __device__ __forceinline__ void renorm() {                              // coder.hpp:74-80
-        int guard = 0;
-#pragma nounroll
-        while (range < RC_TOP) {
-            if ((low ^ (low + range)) >> 56) range = (((u32)low | (RC_TOP - 1)) - (u32)low);
-            put((u32)(low >> 56));
-            range <<= 8; low <<= 8;
-            if (++guard > 12) { err = 1; range = 0xFFFFFFFFu; break; }    // the reference would spin; every chain must drain
-        }
-    }
-    // coder.hpp:66-73 with the divide as a multiply-high by recip = floor(2^32 / tot) plus one exact fix-up
+    __device__ __forceinline__ void renorm() { rc_renorm(low, range, err, [&] { put((u32)(low >> 56)); }); }     // coder.hpp:74-80
+    // coder.hpp:66-73, recip = rc_recip(tot)
     __device__ __forceinline__ void encode(u32 cum, u32 freq, u32 tot, u32 recip) {
-        u32 r = __umulhi(range, recip);
-        r += (range - r * tot) >= tot ? 1u : 0u;
+        const u32 r = rc_div(range, tot, recip);
         low += (u64)cum * r;                                 // cum * r < range: no 32-bit wrap (coder.hpp:69)
         range = r * freq;
         renorm();
@@ -67,12 +62,8 @@ struct LaneEnc {
     }
     // flush; returns the stream's size (the flush's own trailing zero bytes are dropped)
     __device__ __forceinline__ u32 finish() {
-        const u64 v = (low + 0xFFFFFFull) & ~0xFFFFFFull;
-        if (n < 4 && (v >> (32 + 8 * n))) err = 1;            // cannot happen: the elided bytes are zero (v < 2^(32 + 8 n))
-        const u32 top5_lo = (u32)(v >> 24);                  // flush bytes 1..4 (byte 0 = v >> 56)
-        u32 tz = 0;                                          // trailing zero bytes among the five
-        if (top5_lo == 0) tz = (v >> 56) ? 4u : 5u; else tz = ((u32)__builtin_ctz(top5_lo)) >> 3;
-        u64 t = v;
+        u32 tz;
+        u64 t = chain_flush(low, n, tz, err);
         for (int i = 0; i < 5; i++) { put((u32)(t >> 56)); t <<= 8; }
         const u32 stored = n - 4;                            // n >= 5
         const u32 pend = stored & 3u;                        // bytes still in acc (its top `pend` bytes)
@@ -103,7 +94,6 @@ struct LaneEncB {
     __device__ __forceinline__ void init(u32* lds_ring, u32 tid, u8* p, u32 c) {
         low = 0; range = 0xFFFFFFFFu; q = 12; dq = 16; ring = reinterpret_cast<u8*>(lds_ring) + tid * (RB + 4u); out = p; cap = c; err = 0;
     }
-    // (masks, not selects: the compiler turns a select between two computed values back into a branch)
     // the byte always goes to the ring's next free position (nothing live is there); it counts where nm is all ones
     __device__ __forceinline__ void put_if(u32 nm, u32 byte) {
         ring[q & (RB - 1u)] = (u8)byte;
@@ -111,16 +101,8 @@ struct LaneEncB {
     }
     __device__ __forceinline__ void step() {                                  // one round of coder.hpp:74-80, where range < TOP
         const u32 nm = range < RC_TOP ? ~0u : 0u;
-        const u32 lo = (u32)low, hi = (u32)(low >> 32);
-        // coder.hpp:76-77: [low, low + range) crosses a multiple of 2^56 -- with range < 2^24 only where bits 24..55 of low
-        // are all ones, once in 2^32 renormalisations: a cheap necessary test for the whole wavefront, the fix behind it
-        if (__any((hi | 0xFF000000u) == 0xFFFFFFFFu)) {
-            const u32 thi = (u32)((low + range) >> 32);
-            const u32 sm = ((thi ^ hi) >> 24) ? ~0u : 0u;
-            const u32 alt = ~lo & (RC_TOP - 1);                                // (lo | (TOP - 1)) - lo
-            range ^= (range ^ alt) & (nm & sm);
-        }
-        put_if(nm, hi >> 24);
+        rc_clamp_mask(low, range, nm);                                         // coder.hpp:76-77
+        put_if(nm, (u32)(low >> 56));
         const u32 sh = 8u & nm;
         range <<= sh; low <<= sh;
     }
@@ -130,19 +112,12 @@ struct LaneEncB {
 #pragma nounroll
         while (__any(range < RC_TOP)) {                                       // rare: a symbol of probability < 2^-8
             step();
-            if (++guard > 12) { err = 1; range = 0xFFFFFFFFu; break; }
+            if (++guard > RC_GUARD) { err = 1; range = 0xFFFFFFFFu; break; }
         }
     }
     // the arithmetic of encode() for the lanes whose mask vm is all ones; the others keep their state
     __device__ __forceinline__ void encode_if(u32 vm, u32 cum, u32 freq, u32 tot, u32 recip) {
-        u32 r = __umulhi(range, recip);
-        r += (range - r * tot) >= tot ? 1u : 0u;
-        low += (u64)(cum & vm) * r;
-        range ^= (range ^ (r * freq)) & vm;
-        renorm();
-    }
-    __device__ __forceinline__ void encode16_if(u32 vm, u32 cum, u32 freq) {
-        const u32 r = range >> 16;
+        const u32 r = rc_div(range, tot, recip);
         low += (u64)(cum & vm) * r;
         range ^= (range ^ (r * freq)) & vm;
         renorm();
@@ -153,19 +128,9 @@ struct LaneEncB {
         range ^= (range ^ (r * freq)) & vm;
         renorm();
     }
-    __device__ __forceinline__ void encode(u32 cum, u32 freq, u32 tot, u32 recip) {
-        u32 r = __umulhi(range, recip);
-        r += (range - r * tot) >= tot ? 1u : 0u;
-        low += (u64)cum * r;
-        range = r * freq;
-        renorm();
-    }
-    __device__ __forceinline__ void encode16(u32 cum, u32 freq) {
-        const u32 r = range >> 16;
-        low += (u64)cum * r;
-        range = r * freq;
-        renorm();
-    }
+    __device__ __forceinline__ void encode16_if(u32 vm, u32 cum, u32 freq) { encode_bits_if(vm, cum, freq, 16); }
+    __device__ __forceinline__ void encode(u32 cum, u32 freq, u32 tot, u32 recip) { encode_if(~0u, cum, freq, tot, recip); }
+    __device__ __forceinline__ void encode16(u32 cum, u32 freq) { encode16_if(~0u, cum, freq); }
     // 16-byte rows of the ring that are complete go to the chain's region (the ring holds 4 R bytes and at most 15 stay
     // behind: between two calls the coder may add 4 R - 15)
     __device__ __forceinline__ void drain() {
@@ -181,13 +146,8 @@ struct LaneEncB {
     }
     // flush; returns the stream's size (the flush's own trailing zero bytes are dropped)
     __device__ __forceinline__ u32 finish() {
-        const u64 v = (low + 0xFFFFFFull) & ~0xFFFFFFull;
-        const u32 n = q - 12u;
-        if (n < 4 && (v >> (32 + 8 * n))) err = 1;            // cannot happen: the elided bytes are zero
-        const u32 top5_lo = (u32)(v >> 24);
-        u32 tz = 0;
-        if (top5_lo == 0) tz = (v >> 56) ? 4u : 5u; else tz = ((u32)__builtin_ctz(top5_lo)) >> 3;
-        u64 t = v;
+        u32 tz;
+        u64 t = chain_flush(low, q - 12u, tz, err);
         for (int i = 0; i < 5; i++) { put_if(~0u, (u32)(t >> 56)); t <<= 8; }
         drain();
         for (u32 pos = dq; pos < q; pos++) { const u32 at = pos - 16u; if (at < cap) out[at] = ring[pos & (RB - 1u)]; else err |= 2; }
@@ -227,6 +187,8 @@ struct LaneOut {
 // LaneOut's sixteen-byte stores at any alignment dirty a sector twice or three times, a symbol-step apart -- 60 us --, and a quarter of a million half
 // written sectors do not wait in L2 that long: the quality decoder wrote 4.6 GB for 1.5 GB of text (profiles/r05z_pmc_summary.txt).  Two stores back to back
 // fill a sector at once.
+// (One template for both row widths, the waiting dwords in an array, was tried: k_qlt_decode_c and k_gen_decode_c came out with other
+// register counts and five decoders with other code, so the two stay written out.)
 struct LaneOut32 {
     u8* p; u32 n, acc; u32 w0, w1, w2, w3, w4, w5, w6;
     __device__ __forceinline__ void begin(u8* dst) { p = dst; n = 0; acc = 0; w0 = w1 = w2 = w3 = w4 = w5 = w6 = 0; }
@@ -294,8 +256,7 @@ struct LaneDec {
     }
     // coder.hpp:83-86
     __device__ __forceinline__ u32 get_freq(u32 tot, u32 recip) {
-        u32 r = __umulhi(range, recip);
-        r += (range - r * tot) >= tot ? 1u : 0u;
+        u32 r = rc_div(range, tot, recip);
         if (r == 0) { err = 1; r = 1; }
         range = r;
         if (code >> 32) { err = 1; return 0; }
@@ -314,16 +275,7 @@ struct LaneDec {
         const u32 temp = cum * range;
         low += temp; code -= temp;
         range *= freq;
-        int guard = 0;
-        // (not unrolled: the guard bounds the trip count, and thirteen copies of the refill -- with its end-of-stream byte loads -- per
-        //  decoded symbol site are what the compiler makes of that)
-#pragma nounroll
-        while (range < RC_TOP) {
-            if ((low ^ (low + range)) >> 56) range = (((u32)low | (RC_TOP - 1)) - (u32)low);
-            code = (code << 8) | get();
-            range <<= 8; low <<= 8;
-            if (++guard > 12) { err = 1; range = 0xFFFFFFFFu; break; }
-        }
+        rc_renorm(low, range, err, [&] { code = (code << 8) | get(); });
     }
 };
 
@@ -381,14 +333,7 @@ struct LaneDecQ {
     }
     __device__ __forceinline__ void step() {                 // one round of coder.hpp:93-100, where range < TOP
         const u32 nm = range < RC_TOP ? ~0u : 0u;
-        const u32 lo = (u32)low, hi = (u32)(low >> 32);
-        // coder.hpp:94-95: [low, low + range) crosses a multiple of 2^56 -- with range < 2^24 only where bits 24..55 of low are all
-        // ones: a cheap necessary test for the whole wavefront, the exact one behind it
-        if (__any((hi | 0xFF000000u) == 0xFFFFFFFFu)) {
-            const u32 thi = (u32)((low + range) >> 32);
-            const u32 sm = ((thi ^ hi) >> 24) ? ~0u : 0u;
-            range ^= (range ^ (~lo & (RC_TOP - 1))) & (nm & sm);
-        }
+        rc_clamp_mask(low, range, nm);                       // coder.hpp:94-95
         const u32 sh = 8u & nm;
         code = (code << sh) | ((u32)cur & 0xffu & nm);
         range <<= sh; low <<= sh; cur >>= sh;
@@ -401,7 +346,7 @@ struct LaneDecQ {
         while (__any(range < RC_TOP)) {                      // rare: a symbol of probability below 2^-16
             top_up();
             step();
-            if (++guard > 12) { err = 1; range = 0xFFFFFFFFu; break; }
+            if (++guard > RC_GUARD) { err = 1; range = 0xFFFFFFFFu; break; }
         }
     }
     // coder.hpp:83-86 for a row that totals 2^16; r = range >> 16 stays in `range`'s place until decode()
@@ -418,10 +363,9 @@ struct LaneDecQ {
         if (q >> bits) err = 1;
         return q & ((1u << bits) - 1u);
     }
-    // coder.hpp:83-86 for any total: range / tot as a multiply-high by recip = floor(2^32 / tot) plus one exact fix-up (dev_chain.h)
+    // coder.hpp:83-86 for any total, recip = rc_recip(tot)
     __device__ __forceinline__ u32 get_freq(u32 tot, u32 recip, u32& r) {
-        r = __umulhi(range, recip);
-        r += (range - r * tot) >= tot ? 1u : 0u;
+        r = rc_div(range, tot, recip);
         const u32 q = div_exact(code, r);                    // (quotient < tot + 1: far inside div_exact's reach; r >= 2^24 / 1020)
         if (q >= tot) err = 1;
         return q;
@@ -444,7 +388,7 @@ struct LaneDecQ {
         while (__any(range < RC_TOP)) {
             top_up();
             step();
-            if (++guard > 12) { err = 1; range = 0xFFFFFFFFu; break; }
+            if (++guard > RC_GUARD) { err = 1; range = 0xFFFFFFFFu; break; }
         }
     }
 };

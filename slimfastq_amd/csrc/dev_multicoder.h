@@ -5,14 +5,8 @@
 #include "dev_coder.h"
 #include "dev_wave.h"
 
-#define NEUTRAL_TRIPLE make_uint4(0u, 1u, 1u, 0xFFFFFFFFu)     // range /= 1, low += 0, range *= 1: a no-op step
+#define NEUTRAL_TRIPLE make_uint4(0u, 1u, 1u, 0xFFFFFFFFu)     // range /= 1, low += 0, range *= 1: a no-op step (rc_recip(1) = 2^32 - 1)
 
-// reciprocal for the multiply-high divide: m = floor(2^32 / tot) (estimate at most 1 below); tot = 1 (only the
-// neutral step) keeps 2^32 - 1, which the same single fix-up handles
-__device__ __forceinline__ u32 recip_exact(u32 tot) {
-    const u32 m0 = 0xFFFFFFFFu / tot;
-    return (tot != 1 && (0xFFFFFFFFu - m0 * tot) == tot - 1) ? m0 + 1 : m0;
-}
 // per-chain scalars live one per lane (lane j = chain j): read with readlane, written with a select
 #define CGET(reg, j) rl(reg, j)
 #define CSET(reg, j, val) do { const u32 v_ = (val); reg = (threadIdx.x == (j)) ? v_ : reg; } while (0)
@@ -39,10 +33,8 @@ struct MultiCoder {
     // compiler's version of the branchy form spent a third of its instructions moving loop-carried registers)
     __device__ __forceinline__ void renorm_step(bool lead) {
         const bool pred = vr < RC_TOP;
-        const u32 lo32 = (u32)lo, hi32 = (u32)(lo >> 32);
-        const u64 sum = lo + vr;
-        const bool clamp = ((((u32)(sum >> 32)) ^ hi32) >> 24) != 0;       // (low ^ (low + range)) >> 56
-        const u32 vrc = clamp ? (~lo32 & (RC_TOP - 1)) : vr;               // ((u32)low | (TOP-1)) - (u32)low
+        const u32 hi32 = (u32)(lo >> 32);
+        const u32 vrc = rc_clamped(lo, vr);
         const u32 nacc = __builtin_amdgcn_alignbit(hi32 >> 24, acc, 8);    // (acc >> 8) | (byte << 24)
         const u32 npos = pos + 1;
         if (pred && lead && (npos & 3) == 0 && npos <= cap) *reinterpret_cast<u32*>(outp + npos - 4) = nacc;
@@ -56,9 +48,7 @@ struct MultiCoder {
 #pragma nounroll
         for (u32 k = 0; k < nmax; k++) {
             const uint4 t = trip[h][k];
-            u32 r = __umulhi(vr, t.w);                                       // r = range / tot (coder.hpp:68)
-            const u32 rem = vr - r * t.z;
-            r += rem >= t.z ? 1u : 0u;
+            const u32 r = rc_div(vr, t.z, t.w);                              // r = range / tot (coder.hpp:68)
             lo += (u64)t.x * r;                                              // coder.hpp:69 (cum * r < range: no wrap)
             vr = r * t.y;                                                    // coder.hpp:70
             int guard = 0;
@@ -66,7 +56,7 @@ struct MultiCoder {
             while (__any(vr < RC_TOP)) {
                 renorm_step(lead);
                 // the reference spins forever if the clamp yields range 0; every chain here must drain
-                if (++guard > 13) { err = 1; if (vr < RC_TOP) vr = 0xFFFFFFFFu; break; }
+                if (++guard > RC_GUARD_MULTI) { err = 1; if (vr < RC_TOP) vr = 0xFFFFFFFFu; break; }
             }
         }
     }

@@ -11,24 +11,7 @@ struct Sink0 {                 // uniform cursor; lane 0 stores
     u8* p; u32 pos, cap;
     __device__ __forceinline__ void put(u32 b) { if (threadIdx.x == 0 && pos < cap) p[pos] = (u8)b; pos++; }
 };
-struct RcEncU {                // RCoder (coder.hpp) on uniform values, one symbol at a time
-    u64 low; u32 range, err;
-    __device__ __forceinline__ void init() { low = 0; range = 0xFFFFFFFFu; err = 0; }
-    __device__ __forceinline__ void encode(Sink0& s, u32 cum, u32 freq, u32 tot) {      // coder.hpp:66-81
-        const u32 r = range / tot;
-        low += (u64)(u32)(cum * r);
-        range = r * freq;
-        int guard = 0;
-#pragma nounroll
-        while (range < RC_TOP) {
-            if ((low ^ (low + range)) >> 56) range = (((u32)low | (RC_TOP - 1)) - (u32)low);
-            s.put((u32)(low >> 56));
-            range <<= 8; low <<= 8;
-            if (++guard > 12) { err = 1; range = 0xFFFFFFFFu; break; }
-        }
-    }
-    __device__ __forceinline__ void done(Sink0& s) { for (int i = 0; i < 8; i++) { s.put((u32)(low >> 56)); low <<= 8; } }
-};
+using RcEncU = RcEncT<Sink0>;     // RCoder (coder.hpp) on uniform values, one symbol at a time
 
 // A block slot's PowerRanger rows with lane l holding slots 4l..4l+3 (power_ranger.hpp:36-131).
 struct WavePw {

@@ -101,7 +101,7 @@ __device__ __forceinline__ u32 gen_window(const ModelArgs& a, GenChains& g, u32 
             if (lane == i) { cum = cj; freq = fj; tot = tj; }
         }
     }
-    trip[j][lane] = in ? make_uint4(cum, freq, tot, recip_exact(tot)) : NEUTRAL_TRIPLE;
+    trip[j][lane] = in ? make_uint4(cum, freq, tot, rc_recip(tot)) : NEUTRAL_TRIPLE;
     // advance the chain
     const bool rec_done = base + 64 >= llen;
     CSET(g.base, j, rec_done ? 0u : base + 64);

@@ -984,7 +984,7 @@ __device__ __forceinline__ u32 qlt_window_k(const ModelArgs& a, QChain& c, u32* 
         }
         __syncthreads();
         const uint4 tr = strip[lane];
-        steps[spos] = valid ? make_uint4(tr.x, tr.y, tr.z, recip_exact(tr.z)) : NEUTRAL_TRIPLE;   // invalid keys sit at their own lane >= m
+        steps[spos] = valid ? make_uint4(tr.x, tr.y, tr.z, rc_recip(tr.z)) : NEUTRAL_TRIPLE;   // invalid keys sit at their own lane >= m
         cons = m; nsteps = m;
     } else {
         // escape symbols (quality >= 63: qlts.cpp:80-86) code two steps each: walk at most 32 symbols in order on lane 0
@@ -997,10 +997,10 @@ __device__ __forceinline__ u32 qlt_window_k(const ModelArgs& a, QChain& c, u32* 
                 const Triple t1 = l64_model_lane(qs + (size_t)ctx * L64_NSYM, qo + (size_t)ctx * 4, epoch_w,
                                                  a.prior_w ? a.prior_w + (size_t)ctx * L64_NSYM : nullptr, a.prior_wovf + (size_t)ctx * 4,
                                                  sym < LAST_QLT ? sym : LAST_QLT, perr);
-                steps[t] = make_uint4(t1.cum, t1.freq, t1.tot, recip_exact(t1.tot));
+                steps[t] = make_uint4(t1.cum, t1.freq, t1.tot, rc_recip(t1.tot));
                 if (sym >= LAST_QLT) {
                     const Triple t2 = Power::model(pw.slots + (size_t)PR_EXQ_ROW * PW_NSYM, pw.hdr + PR_EXQ_ROW, epoch, sym, perr);
-                    steps[t + 1] = make_uint4(t2.cum, t2.freq, t2.tot, recip_exact(t2.tot));
+                    steps[t + 1] = make_uint4(t2.cum, t2.freq, t2.tot, rc_recip(t2.tot));
                 }
             }
             t += sym >= LAST_QLT ? 2u : 1u;
