@@ -358,6 +358,37 @@ int sfq_ctx_set_quality_map(sfq_ctx* ctx, const uint8_t* lut);
 /* bytes changed by the last encode call's map (0 where none ran) */
 uint64_t sfq_get_quality_map_changed(const sfq_ctx* ctx);
 
+/* ---- paired files --------------------------------------------------------------------------------------------------------
+ * Two FASTQ texts whose record i are mates (R1 / R2) are coded as ONE text, A0 B0 A1 B1 ...: the header model then codes a mate's
+ * header as the one field that differs from its partner's.  Interleaving and splitting are text-to-text passes on the device
+ * (pair.hip), in front of an encode's framing and behind a decode's assembly; no stream, coder or block format knows of them.  A
+ * record is four lines; a text without a final '\n' ends in a line all the same.
+ * Every entry: SFQ_E_ARG for a null pointer or an empty text; SFQ_E_FORMAT for a text whose lines are no multiple of four, for
+ * A and B of different record counts (sfq_last_error gives both), for an odd number of records to split, and for an A that does
+ * not end in '\n' (its last record would run into its mate; B may lack the final '\n', the output then lacks it too and a split
+ * gives it back exactly); SFQ_E_UNSUPPORTED for a record of 4 GiB or more.  A refused call writes nothing to its output.  Each
+ * call runs on the context's stream and synchronises once.  Like sfq_crc32 the passes read the whole aligned 16-byte units of a
+ * text's first and last byte; they write nothing outside the output's bytes. */
+/* out = A0 B0 A1 B1 ...; *out_bytes = na + nb (on SFQ_E_OVERFLOW: the size needed); *n_pairs may be NULL; d_out overlaps neither text */
+int sfq_interleave(sfq_ctx* ctx, const uint8_t* d_a, uint64_t na, const uint8_t* d_b, uint64_t nb,
+                   uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* n_pairs);
+/* d_out[0, *split) = the even records in order, d_out[*split, n) = the odd ones; d_out must not overlap d_text; *n_pairs may be NULL */
+int sfq_split_pairs(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, uint8_t* d_out, uint64_t out_cap,
+                    uint64_t* split, uint64_t* n_pairs);
+/* sfq_encode_blocks_host of the interleaved text: both files staged, interleaved on the device, then the installed quality map,
+ * then the call as it is.  The host buffers are not touched.  The statistics, the checksums and the quality map of the call are
+ * those of the INTERLEAVED text (sfq_result.raw sizes too): that text is what the archive describes. */
+int sfq_encode_pairs_host(sfq_ctx* ctx, const uint8_t* h_a, uint64_t na, const uint8_t* h_b, uint64_t nb,
+                          const sfq_params* params, uint8_t* h_out, uint64_t out_cap, sfq_result* result);
+/* on != 0: sfq_decode_blocks_host hands back the split layout (sfq_split_pairs) instead of the interleaved text, split behind the
+ * checksum pass: the CRCs, installed ones included, are those of the interleaved text.  Costs one more device buffer of the
+ * text's size, held while the switch is on.  While it is on, sfq_decode_block_range and sfq_decode_block_range_host return
+ * SFQ_E_UNSUPPORTED (a window may start at a second mate).  sfq_decode_blocks writes into the caller's device buffer and is not
+ * affected: call sfq_split_pairs on its output.  Default off: nothing is launched or allocated. */
+int sfq_ctx_set_pair_split(sfq_ctx* ctx, int on);
+/* 1: the last decode call split its text, *first_bytes = where the second mates begin; 0: it did not (both set to 0) */
+int sfq_get_pair_split(const sfq_ctx* ctx, uint64_t* first_bytes, uint64_t* n_pairs);
+
 /* ---- the ".sfq" container (host only) ----------------------------------------------------------
  * Replaces FilerSave + the info page (filer.cpp:217-242, config.cpp:334-347) for hosts that assemble an archive
  * themselves: info_text is the info page ("key=value\n" lines), then n_streams named byte streams (names of at most

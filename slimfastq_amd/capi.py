@@ -32,6 +32,7 @@ EXPORTS = [
     "sfq_set_block_checksums", "sfq_decode_block_range", "sfq_decode_block_range_host",
     "sfq_ctx_set_stats", "sfq_get_text_stats", "sfq_text_stats_merge", "sfq_pack_text_stats", "sfq_unpack_text_stats",
     "sfq_quality_map_preset", "sfq_quality_map_check", "sfq_map_qualities", "sfq_ctx_set_quality_map", "sfq_get_quality_map_changed",
+    "sfq_interleave", "sfq_split_pairs", "sfq_encode_pairs_host", "sfq_ctx_set_pair_split", "sfq_get_pair_split",
 ]
 
 
@@ -193,6 +194,12 @@ def lib():
         L.sfq_ctx_set_quality_map.argtypes = [vp, C.c_char_p]
         L.sfq_get_quality_map_changed.argtypes = [vp]
         L.sfq_get_quality_map_changed.restype = u64
+        u64p = C.POINTER(u64)
+        L.sfq_interleave.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64p, u64p]
+        L.sfq_split_pairs.argtypes = [vp, vp, u64, vp, u64, u64p, u64p]
+        L.sfq_encode_pairs_host.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp]
+        L.sfq_ctx_set_pair_split.argtypes = [vp, C.c_int]
+        L.sfq_get_pair_split.argtypes = [vp, u64p, u64p]
         _lib = L
     return _lib
 
@@ -404,6 +411,40 @@ class Context:
         """Bytes changed by the last encode call's quality map (0 where none ran)."""
         return int(lib().sfq_get_quality_map_changed(self._h))
 
+    def interleave(self, d_a, na, d_b, nb, d_out, out_cap):
+        """The FASTQ texts in the device buffers at d_a and d_b record by record into the one at d_out (A0 B0 A1 B1 ...); returns
+        (bytes written, pairs).  An SfqError of code E_OVERFLOW carries the size needed as .needed."""
+        n, pairs = C.c_uint64(), C.c_uint64()
+        rc = lib().sfq_interleave(self._h, C.c_void_p(d_a), int(na), C.c_void_p(d_b), int(nb), C.c_void_p(d_out), int(out_cap),
+                                  C.byref(n), C.byref(pairs))
+        try:
+            self._check(rc)
+        except SfqError as e:
+            e.needed = int(n.value)
+            raise
+        return int(n.value), int(pairs.value)
+
+    def split_pairs(self, d_text, nbytes, d_out, out_cap):
+        """The interleaved FASTQ text in the device buffer at d_text into the one at d_out: its even records, then its odd ones;
+        returns (where the odd ones begin, pairs)."""
+        split, pairs = C.c_uint64(), C.c_uint64()
+        self._check(lib().sfq_split_pairs(self._h, C.c_void_p(d_text), int(nbytes), C.c_void_p(d_out), int(out_cap),
+                                          C.byref(split), C.byref(pairs)))
+        return int(split.value), int(pairs.value)
+
+    def set_pair_split(self, on=True):
+        """On: decode_host returns the first mates followed by the second mates (pair_split() says where) instead of the
+        interleaved text."""
+        self._check(lib().sfq_ctx_set_pair_split(self._h, 1 if on else 0))
+
+    def pair_split(self):
+        """(where the second mates begin, pairs) of the last decode call; None where it did not split its text."""
+        first, pairs = C.c_uint64(), C.c_uint64()
+        rc = lib().sfq_get_pair_split(self._h, C.byref(first), C.byref(pairs))
+        if rc < 0:
+            self._check(rc)
+        return (int(first.value), int(pairs.value)) if rc == 1 else None
+
     def set_block_checksums(self, crcs):
         """The expected CRCs of the next decode call's blocks (consumed by it)."""
         arr = (C.c_uint32 * max(len(crcs), 1))(*[c & 0xFFFFFFFF for c in crcs])
@@ -494,11 +535,28 @@ class Context:
         src = np.frombuffer(fastq, np.uint8)
         self._check(L.sfq_encode_blocks_host(self._h, src.ctypes.data_as(C.c_void_p), len(fastq), C.byref(p),
                                              out.ctypes.data_as(C.c_void_p), cap, C.byref(res)))
+        return self._encoded(res, out)
+
+    def _encoded(self, res, out) -> Encoded:
+        """What the last *_host encode call left in the context, with its streams in out."""
         blocks = self.index(res.n_blocks)
         crcs, text_crc = self.checksums()
         on = len(crcs) == res.n_blocks and res.n_blocks > 0
         return Encoded(res, blocks, self.first_headers(res.first_hdr_bytes), out[:res.total_bytes].copy(), self.prior(), self.chains(), self.rec_prior(),
                        crcs if on else None, text_crc if on else None, self.text_stats())
+
+    def encode_pairs_host(self, fastq_a: bytes, fastq_b: bytes, level=3, block_reads=0, gen_bits=0, models=0, kernel=0, prior_step=0,
+                          tables=0, chain_reads=0, lds_rows=0) -> Encoded:
+        """encode_host of the two texts interleaved record by record on the device (sfq_encode_pairs_host)."""
+        L = lib()
+        p = Params(level, block_reads, gen_bits, models, kernel, 0, prior_step, tables, chain_reads, lds_rows)
+        res = Result()
+        cap = L.sfq_encode_bound(len(fastq_a) + len(fastq_b))
+        out = np.empty(cap, np.uint8)
+        a, b = np.frombuffer(fastq_a, np.uint8), np.frombuffer(fastq_b, np.uint8)
+        self._check(L.sfq_encode_pairs_host(self._h, a.ctypes.data_as(C.c_void_p), len(fastq_a), b.ctypes.data_as(C.c_void_p), len(fastq_b),
+                                            C.byref(p), out.ctypes.data_as(C.c_void_p), cap, C.byref(res)))
+        return self._encoded(res, out)
 
     def encode_device(self, d_ptr, nbytes, d_out, out_cap, level=3, block_reads=0, gen_bits=0, models=0, kernel=0, qlt_only=False,
                       prior_step=0, tables=0, chain_reads=0, lds_rows=0):

@@ -188,6 +188,14 @@ struct sfq_ctx {
     DevBuf qmap_dev;                                  // [0, 256) the table, [256, 264) the changed bytes, from 512 on the pass's scratch
     void* qmap_pin = nullptr; size_t qmap_pin_cap = 0;        // the same two, page-locked: the table on its way in, the count on its way out
     u64 qmap_changed = 0;                             // the last encode call's
+    // paired files (pair.hip): like the checksums, nothing of this exists until a pairs entry is called or the split is switched on
+    DevBuf pair_work;                                 // a PairInfo, then the passes' working arrays (pair_run)
+    void* pair_pin = nullptr; size_t pair_pin_cap = 0;        // the PairInfo on its way out
+    u64 pair_cap = 0;                                 // records a start array is laid out for at least: what a call learned stays
+    DevBuf pair_in;                                   // sfq_encode_pairs_host: both files staged
+    DevBuf pair_out;                                  // the split layout of a decoded text (while the switch is on)
+    bool pair_split_on = false;                       // sfq_ctx_set_pair_split
+    bool pair_split_done = false; u64 pair_first = 0, pair_n = 0;     // the last decode call's
 };
 
 namespace {
@@ -949,7 +957,8 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
         &ctx->hcnt, &ctx->hfreq, &ctx->rrows, &ctx->rdec, &ctx->rmap, &ctx->rflags, &ctx->rtok, &ctx->ptmp, &ctx->qrows, &ctx->qdec, &ctx->qesc, &ctx->qw, &ctx->csz, &ctx->coff, &ctx->gcnt, &ctx->grows, &ctx->glog, &ctx->gcost, &ctx->gbins, &ctx->gfill, &ctx->gm_T, &ctx->gm_slen, &ctx->gm_boff, &ctx->gm_soff, &ctx->gm_scan, &ctx->gm_stage, &ctx->gm_tok, &ctx->gm_csz, &ctx->gm_idx, &ctx->excf, &ctx->cflags, &ctx->segn, &ctx->segoff, &ctx->segrec, &ctx->pslot, &ctx->plist, &ctx->chn_len, &ctx->chn_off, &ctx->chn_out,
         &ctx->oflags, &ctx->okbytes, &ctx->ofpos, &ctx->okoff, &ctx->ofilt, &ctx->orecmap, &ctx->olist, &ctx->line_off_o, &ctx->ono, &ctx->opiece,
         &ctx->otxt[0], &ctx->otxt[1], &ctx->otxt[2], &ctx->osize_all, &ctx->oroff_all, &ctx->oroff_k, &ctx->ocnt,
-        &ctx->crc_tab, &ctx->crc_tiles, &ctx->crc_grps, &ctx->crc_bounds, &ctx->crc_out, &ctx->stats_acc, &ctx->qmap_dev };
+        &ctx->crc_tab, &ctx->crc_tiles, &ctx->crc_grps, &ctx->crc_bounds, &ctx->crc_out, &ctx->stats_acc, &ctx->qmap_dev,
+        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out };
     for (DevBuf* b : all) release(*b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->pin2) (void)hipHostFree(ctx->pin2);
@@ -958,6 +967,7 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
     if (ctx->st_crc) (void)hipStreamDestroy(ctx->st_crc);
     if (ctx->stats_pin) (void)hipHostFree(ctx->stats_pin);
     if (ctx->qmap_pin) (void)hipHostFree(ctx->qmap_pin);
+    if (ctx->pair_pin) (void)hipHostFree(ctx->pair_pin);
     for (auto& e : ctx->stats_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->st_stats) (void)hipStreamDestroy(ctx->st_stats);
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
@@ -1907,16 +1917,13 @@ int sfq_set_prior_counts(sfq_ctx* ctx, int level, const uint32_t* d_qlt, const u
     ctx->counts.valid = true; ctx->counts.q_rows = (u32)(nq / 64); ctx->counts.rec = own_rec;
     return SFQ_OK;
 }
-int sfq_encode_blocks_host(sfq_ctx* ctx, const uint8_t* h_fastq, uint64_t nbytes, const sfq_params* params,
-                           uint8_t* h_out, uint64_t out_cap, sfq_result* result) {
-    if (!ctx || !h_fastq || !h_out) return fail(ctx, SFQ_E_ARG, "null argument");
-    HIPC(hipSetDevice(ctx->dev));
+// The *_host encode entries from the staged text on: ctx->in_stage holds nbytes of text, queued on the context's stream.  The staged
+// copy is the context's own: an installed quality map is applied where it lies.
+static int encode_staged(sfq_ctx* ctx, uint64_t nbytes, const sfq_params* params, uint8_t* h_out, uint64_t out_cap, sfq_result* result) {
     int rc;
-    if ((rc = reserve(ctx, ctx->in_stage, (size_t)nbytes + 16))) return rc;
     const u64 bound = sfq_encode_bound(nbytes);
     if ((rc = reserve(ctx, ctx->out_stage, (size_t)bound))) return rc;
-    HIPC(hipMemcpyAsync(ctx->in_stage.p, h_fastq, (size_t)nbytes, hipMemcpyHostToDevice, ctx->st));
-    const bool mapped = ctx->qmap_on && nbytes;            // the staged copy is the context's own: it can be mapped where it lies
+    const bool mapped = ctx->qmap_on && nbytes;
     ctx->qmap_changed = 0;
     if (mapped && (rc = qmap_queue(ctx, (u8*)ctx->in_stage.p, nbytes, ctx->qmap_lut))) return rc;
     rc = encode_impl(ctx, (const u8*)ctx->in_stage.p, nbytes, params, (u8*)ctx->out_stage.p, bound, result, 0);
@@ -1926,6 +1933,127 @@ int sfq_encode_blocks_host(sfq_ctx* ctx, const uint8_t* h_fastq, uint64_t nbytes
     HIPC(hipStreamSynchronize(ctx->st));
     if (mapped) memcpy(&ctx->qmap_changed, (const u8*)ctx->qmap_pin + 256, 8);
     return SFQ_OK;
+}
+int sfq_encode_blocks_host(sfq_ctx* ctx, const uint8_t* h_fastq, uint64_t nbytes, const sfq_params* params,
+                           uint8_t* h_out, uint64_t out_cap, sfq_result* result) {
+    if (!ctx || !h_fastq || !h_out) return fail(ctx, SFQ_E_ARG, "null argument");
+    HIPC(hipSetDevice(ctx->dev));
+    int rc;
+    if ((rc = reserve(ctx, ctx->in_stage, (size_t)nbytes + 16))) return rc;
+    HIPC(hipMemcpyAsync(ctx->in_stage.p, h_fastq, (size_t)nbytes, hipMemcpyHostToDevice, ctx->st));
+    return encode_staged(ctx, nbytes, params, h_out, out_cap, result);
+}
+
+// ---- paired files (pair.hip) -----------------------------------------------------------------------------------------------------
+// One pass on the context's stream, one synchronise: b null = split a into out, else interleave a and b into out (which holds
+// na + nb bytes and overlaps neither).  *got: what the device found.  Only a text with more records than the start arrays were laid
+// out for (one per 64 bytes, or what an earlier call learned) runs twice.
+static int pair_run(sfq_ctx* ctx, const u8* a, u64 na, const u8* b, u64 nb, u8* out, PairInfo* got) {
+    int rc;
+    if ((rc = reserve_pinned_buf(ctx, ctx->pair_pin, ctx->pair_pin_cap, sizeof(PairInfo)))) return rc;
+    for (int attempt = 0; ; attempt++) {
+        const u64 cap = std::max<u64>(ctx->pair_cap, std::max(na, nb) / 64 + 1024);
+        auto up = [](u64 v) { return (v + 15) & ~15ull; };
+        u64 at = up(sizeof(PairInfo));
+        const u64 sc_a = at; at += up(qmap_scratch(a, na).bytes);
+        const u64 sc_b = at; if (b) at += up(qmap_scratch(b, nb).bytes);
+        const u64 st_a = at; at += up((cap + 1) * 8);
+        const u64 st_b = at; if (b) at += up((cap + 1) * 8);
+        const u64 nlens = cap / 2 + 1;
+        const u64 lens = at; if (!b) at += up(nlens * 4);
+        const u64 offa = at; if (!b) at += up((nlens + 1) * 8);
+        const u64 tmp = at; if (!b) at += up((nlens / 1024 + 2) * 8);
+        if ((rc = reserve(ctx, ctx->pair_work, (size_t)at))) return rc;
+        u8* w = (u8*)ctx->pair_work.p;
+        PairInfo* info = (PairInfo*)w;
+        HIPC(hipMemsetAsync(info, 0, sizeof(PairInfo), ctx->st));
+        const PairText ta{ a, na, w + sc_a, (u64*)(w + st_a) };
+        if (b) launch_pair_interleave(ta, PairText{ b, nb, w + sc_b, (u64*)(w + st_b) }, cap, out, info, ctx->st);
+        else launch_pair_split(ta, cap, (u32*)(w + lens), (u64*)(w + offa), (u64*)(w + tmp), out, info, ctx->st);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(ctx->pair_pin, info, sizeof(PairInfo), hipMemcpyDeviceToHost, ctx->st));
+        HIPC(hipStreamSynchronize(ctx->st));
+        memcpy(got, ctx->pair_pin, sizeof(PairInfo));
+        if (got->status != PAIR_CAP) break;
+        if (attempt) return fail(ctx, SFQ_E_HIP, "paired files: the record starts did not fit twice");
+        ctx->pair_cap = std::max(got->recs[0], b ? got->recs[1] : 0);
+    }
+    const unsigned long long l0 = got->lines[0], l1 = got->lines[1], r0 = got->recs[0], r1 = got->recs[1];
+    switch (got->status) {
+    case PAIR_OK: return SFQ_OK;
+    case PAIR_LINES_A: return fail(ctx, SFQ_E_FORMAT, "paired files: the %s holds %llu lines, not a multiple of four", b ? "first text" : "text", l0);
+    case PAIR_LINES_B: return fail(ctx, SFQ_E_FORMAT, "paired files: the second text holds %llu lines, not a multiple of four", l1);
+    case PAIR_COUNTS: return fail(ctx, SFQ_E_FORMAT, "paired files: the first text holds %llu records, the second %llu", r0, r1);
+    case PAIR_A_END: return fail(ctx, SFQ_E_FORMAT, "paired files: the first text does not end in a line end: its last record would run into its mate");
+    case PAIR_ODD: return fail(ctx, SFQ_E_FORMAT, "paired files: the text holds %llu records, an odd number cannot be split into mates", r0);
+    case PAIR_LONG: return fail(ctx, SFQ_E_UNSUPPORTED, "paired files: a record of 4 GiB or more");
+    default: return fail(ctx, SFQ_E_HIP, "paired files: status %u", got->status);
+    }
+}
+int sfq_interleave(sfq_ctx* ctx, const uint8_t* d_a, uint64_t na, const uint8_t* d_b, uint64_t nb,
+                   uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* n_pairs) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!d_a || !d_b || !d_out || !out_bytes) return fail(ctx, SFQ_E_ARG, "null argument");
+    if (!na || !nb) return fail(ctx, SFQ_E_ARG, "paired files: an empty text (%llu and %llu bytes)", (unsigned long long)na, (unsigned long long)nb);
+    *out_bytes = na + nb;
+    if (n_pairs) *n_pairs = 0;
+    if (na + nb > out_cap) return fail(ctx, SFQ_E_OVERFLOW, "paired files: the interleaved text needs %llu bytes", (unsigned long long)(na + nb));
+    HIPC(hipSetDevice(ctx->dev));
+    Settle settle(ctx);
+    PairInfo got;
+    if (int rc = pair_run(ctx, d_a, na, d_b, nb, d_out, &got)) return rc;
+    if (n_pairs) *n_pairs = got.recs[0];
+    settle.ok = true;
+    return SFQ_OK;
+}
+int sfq_split_pairs(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, uint8_t* d_out, uint64_t out_cap, uint64_t* split, uint64_t* n_pairs) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!d_text || !d_out || !split) return fail(ctx, SFQ_E_ARG, "null argument");
+    if (!n) return fail(ctx, SFQ_E_ARG, "paired files: an empty text");
+    *split = 0;
+    if (n_pairs) *n_pairs = 0;
+    if (n > out_cap) return fail(ctx, SFQ_E_OVERFLOW, "paired files: the split text needs %llu bytes", (unsigned long long)n);
+    HIPC(hipSetDevice(ctx->dev));
+    Settle settle(ctx);
+    PairInfo got;
+    if (int rc = pair_run(ctx, d_text, n, nullptr, 0, d_out, &got)) return rc;
+    *split = got.split;
+    if (n_pairs) *n_pairs = got.recs[0] >> 1;
+    settle.ok = true;
+    return SFQ_OK;
+}
+int sfq_encode_pairs_host(sfq_ctx* ctx, const uint8_t* h_a, uint64_t na, const uint8_t* h_b, uint64_t nb, const sfq_params* params,
+                          uint8_t* h_out, uint64_t out_cap, sfq_result* result) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!h_a || !h_b || !h_out || !params || !result) return fail(ctx, SFQ_E_ARG, "null argument");
+    if (!na || !nb) return fail(ctx, SFQ_E_ARG, "paired files: an empty text (%llu and %llu bytes)", (unsigned long long)na, (unsigned long long)nb);
+    HIPC(hipSetDevice(ctx->dev));
+    int rc;
+    const u64 at_b = ((na + 15) & ~15ull) + 16;
+    if ((rc = reserve(ctx, ctx->pair_in, (size_t)(at_b + nb + 16)))) return rc;
+    if ((rc = reserve(ctx, ctx->in_stage, (size_t)(na + nb) + 16))) return rc;
+    u8* d_a = (u8*)ctx->pair_in.p;
+    HIPC(hipMemcpyAsync(d_a, h_a, (size_t)na, hipMemcpyHostToDevice, ctx->st));
+    HIPC(hipMemcpyAsync(d_a + at_b, h_b, (size_t)nb, hipMemcpyHostToDevice, ctx->st));
+    {
+        Settle settle(ctx);
+        PairInfo got;
+        if ((rc = pair_run(ctx, d_a, na, d_a + at_b, nb, (u8*)ctx->in_stage.p, &got))) return rc;
+        settle.ok = true;
+    }
+    return encode_staged(ctx, na + nb, params, h_out, out_cap, result);
+}
+int sfq_ctx_set_pair_split(sfq_ctx* ctx, int on) {
+    if (!ctx) return SFQ_E_ARG;
+    ctx->pair_split_on = on != 0;
+    if (!on) release(ctx->pair_out);
+    return SFQ_OK;
+}
+int sfq_get_pair_split(const sfq_ctx* ctx, uint64_t* first_bytes, uint64_t* n_pairs) {
+    if (!ctx) return SFQ_E_ARG;
+    if (first_bytes) *first_bytes = ctx->pair_split_done ? ctx->pair_first : 0;
+    if (n_pairs) *n_pairs = ctx->pair_split_done ? ctx->pair_n : 0;
+    return ctx->pair_split_done ? 1 : 0;
 }
 
 int sfq_get_block_index(sfq_ctx* ctx, sfq_block_info* h_blocks, uint32_t cap) {
@@ -2007,6 +2135,9 @@ static int decode_device(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_inf
     Settle settle(ctx);
     drop_encode_blobs(ctx);                             // whatever an encode left behind is not this archive's
     ctx->crcs.clear(); ctx->text_crc = 0;
+    ctx->pair_split_done = false;
+    if (w.ranged && ctx->pair_split_on)
+        return fail(ctx, SFQ_E_UNSUPPORTED, "a window of blocks may start at a second mate and is not split: sfq_ctx_set_pair_split(ctx, 0) comes first");
     const bool check = ex.set;
     const std::vector<u32>& expect = ex.crc;
     if (check && expect.size() != w.n) return fail(ctx, SFQ_E_ARG, "%zu block checksums installed for a call of %u blocks", expect.size(), w.n);
@@ -2776,7 +2907,18 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
     rc = decode_device(ctx, params, h_blocks, n_blocks, h_first_hdrs, first_hdr_bytes, (const u8*)ctx->in_stage.p,
                        stream_offset, (u8*)ctx->out_stage.p, out_cap, out_bytes, result, ex, w);
     if (rc) return rc;
-    HIPC(hipMemcpyAsync(h_out, ctx->out_stage.p, (size_t)*out_bytes, hipMemcpyDeviceToHost, ctx->st));
+    const u8* d_text = (const u8*)ctx->out_stage.p;
+    if (ctx->pair_split_on) {                              // behind the checksum pass: the archive describes the interleaved text
+        if (!*out_bytes) return fail(ctx, SFQ_E_FORMAT, "paired files: an empty text");
+        if ((rc = reserve(ctx, ctx->pair_out, (size_t)*out_bytes + 16))) return rc;
+        Settle settle(ctx);
+        PairInfo got;
+        if ((rc = pair_run(ctx, d_text, *out_bytes, nullptr, 0, (u8*)ctx->pair_out.p, &got))) return rc;
+        settle.ok = true;
+        d_text = (const u8*)ctx->pair_out.p;
+        ctx->pair_split_done = true; ctx->pair_first = got.split; ctx->pair_n = got.recs[0] >> 1;
+    }
+    HIPC(hipMemcpyAsync(h_out, d_text, (size_t)*out_bytes, hipMemcpyDeviceToHost, ctx->st));
     HIPC(hipStreamSynchronize(ctx->st));
     return SFQ_OK;
 }

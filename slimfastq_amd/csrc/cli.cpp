@@ -11,6 +11,8 @@
 //   -Q name   : LOSSY, encode only: bin the qualities on the GPU before they are coded (illumina8: 8 levels, novaseq4: 4 levels);
 //               info keys "qlt.map" / "qlt.map.changed"
 //   -R F:N    : with -d: records F .. F + N - 1 only (numbered from 0 over the archive) -- the blocks that hold them are decoded, no others
+//   -p fastq  : paired files: the mates of -u's records; both are interleaved on the GPU and coded as one text (info key "usr.pair");
+//               with -d: the second mates go here, the first to -u
 // All model / coder work happens in libslimfastq_amd.so on the GPU; this file parses arguments, reads and
 // writes files and fills the info page.
 #include <sys/stat.h>
@@ -96,6 +98,10 @@ static void usage() {
            "-R first:count   : with -d: write records first .. first+count-1 only (numbered from 0 over the whole archive; count is\n"
            "                   clipped at the end): only the blocks that hold them are decoded (and, under a base model, what the\n"
            "                   format makes them depend on); with -b: of every job\n"
+           "-p fastq         : paired files: record i of this file is the mate of record i of -u; the two are interleaved on the GPU\n"
+           "                   (R1 R2 R1 R2 ...) and coded as one text, so a mate's header costs the one field that differs; with -d:\n"
+           "                   the first mates are written to -u, the second mates here (the archive must have been written with -p;\n"
+           "                   without -p it decodes to interleaved FASTQ); needs -u, not with -b or -R\n"
            "-S mbytes        : input is compressed in slabs of this many MiB, one archive segment each (default 512 for a\n"
            "                   regular file, read ahead while the GPU codes the slab before; 2048 for a pipe)\n"
            "-t threads       : threads reading a slab (default 6)\n"
@@ -128,6 +134,7 @@ struct Opts {
     bool stats = false;                                                // -Y
     bool range = false; uint64_t r_first = 0, r_count = 0;             // -R first:count
     int qmap = 0; std::string qmap_name;                               // -Q: SFQ_QMAP_* (0 = none) and its name
+    std::string pair;                                                  // -p: the second file of a pair
 };
 // "FIRST:COUNT", both decimal, COUNT > 0
 static bool parse_range(const char* t, uint64_t& first, uint64_t& count) {
@@ -188,6 +195,16 @@ static size_t whole_records(const uint8_t* p, size_t n, uint64_t nl) {
     while (end > 0 && p[end - 1] != '\n') end--;
     while (drop && end > 0) { end--; while (end > 0 && p[end - 1] != '\n') end--; drop--; }
     return end;
+}
+
+// [0, n) ends at a line end or at the end of a file: the same without its last `drop` records (four lines each)
+static size_t drop_records(const uint8_t* p, size_t end, uint64_t drop) {
+    for (uint64_t l = 0; l < 4 * drop && end > 0; l++) { end--; while (end > 0 && p[end - 1] != '\n') end--; }
+    return end;
+}
+// the lines of [p, p + n): a text without a final '\n' ends in a line all the same
+static uint64_t count_lines(const uint8_t* p, size_t n) {
+    return (uint64_t)std::count(p, p + n, (uint8_t)'\n') + (n && p[n - 1] != '\n');
 }
 
 // One finished library call (a segment of raw bytes of text) into the archive's index.
@@ -262,6 +279,9 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         if (g_batch) croak("Can't read file '%s'", usr.c_str());
         fprintf(stderr, "Can't read file '%s'\n", usr.c_str()); exit(1);
     }
+    const bool paired = !o.pair.empty();
+    FILE* in2 = paired ? fopen(o.pair.c_str(), "rb") : nullptr;
+    if (paired && !in2) { fprintf(stderr, "Can't read file '%s'\n", o.pair.c_str()); exit(1); }
     const bool legacy = o.block_reads == 0;
     if (sfq_ctx_set_checksums(ctx, o.checksum ? 1 : 0)) croak("%s", sfq_last_error(ctx));
     if (sfq_ctx_set_stats(ctx, o.stats ? 1 : 0)) croak("%s", sfq_last_error(ctx));
@@ -284,6 +304,10 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     //  by one, 4-10x slower than reading into an ordinary buffer first.)
     size_t file_left = SIZE_MAX;                                       // bytes not yet read, when the input is a regular file
     if (in != stdin) { struct stat st; if (fstat(fileno(in), &st) == 0 && S_ISREG(st.st_mode)) file_left = (size_t)st.st_size; }
+    if (paired && file_left != SIZE_MAX) {                             // (the text that is coded: both files)
+        struct stat st;
+        if (fstat(fileno(in2), &st) == 0 && S_ISREG(st.st_mode)) file_left += (size_t)st.st_size; else file_left = SIZE_MAX;
+    }
     auto decide_tables = [&](uint64_t text_bytes) {
         if (tables_decided) return;
         tables_decided = true;
@@ -304,7 +328,7 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     // A regular file in the block format: slabs are read AHEAD -- several threads pread the next slab into one of two
     // page-locked buffers while the GPU codes the current one -- and the streams come back into a page-locked buffer too.
     // (File to file the time is the host's: one thread fread()s at ~5 GB/s, pageable H2D/D2H copies crawl.)
-    bool ahead = !legacy && in != stdin && file_left != SIZE_MAX;
+    bool ahead = !legacy && in != stdin && file_left != SIZE_MAX && !paired;      // (pairs: the plain loop below)
     size_t slab = (size_t)(o.slab_bytes ? o.slab_bytes : ahead ? (512ull << 20) : (2048ull << 20));
     // (a small file: buffers of its size, not of the slab's -- page-locking 1.5 GiB for a 1 MB file costs hundreds of
     //  milliseconds and may not fit a small memlock limit)
@@ -431,6 +455,68 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         streamed = true;
         eof = true;                                                     // nothing left for the loop below
     }
+    // -p: up to half a slab of each file, both cut to the same number of whole records and interleaved on the GPU; both tails are
+    // carried, so every archive segment holds whole pairs
+    if (paired) {
+        Bytes fb;
+        bool eof2 = false;
+        uint64_t done = 0;                                              // pairs coded so far
+        // the records of a file from its carried tail on, read to its end (only to name both counts where they differ)
+        auto count_rest = [&](FILE* f, Bytes& buf, bool& at_end) {
+            uint64_t lines = 0;
+            for (;;) {
+                lines += (uint64_t)std::count(buf.p, buf.p + buf.n, (uint8_t)'\n');
+                const bool open_line = buf.n && buf.p[buf.n - 1] != '\n';
+                if (at_end) return (lines + open_line + 3) / 4;
+                buf.n = 0;
+                if (!fill(f, buf, (size_t)64 << 20, at_end)) croak("read error");
+            }
+        };
+        auto unequal = [&](uint64_t na, uint64_t nb) {
+            croak("-p: the files do not pair up: '%s' holds %llu records, '%s' holds %llu", usr.c_str(), (unsigned long long)na, o.pair.c_str(), (unsigned long long)nb);
+        };
+        for (;;) {
+            auto want_of = [&](const Bytes& b) {
+                size_t want = legacy ? std::max<size_t>(b.n * 2, 64u << 20) : slab / 2;
+                return want <= b.n ? b.n * 2 : want;                    // a record longer than half a slab: grow
+            };
+            if (!eof && !fill(in, fq, want_of(fq), eof)) croak("read error");
+            if (!eof2 && !fill(in2, fb, want_of(fb), eof2)) croak("read error");
+            tick("read slab");
+            if (eof && eof2 && fq.n == 0 && fb.n == 0) break;
+            if (legacy && !(eof && eof2)) continue;                     // (one adaptive state cannot be cut: one slab holds both files)
+            // whole records of each, then the same number of them
+            size_t ua = fq.n, ub = fb.n;
+            if (!eof) ua = whole_records(fq.p, fq.n, (uint64_t)std::count(fq.p, fq.p + fq.n, (uint8_t)'\n'));
+            if (!eof2) ub = whole_records(fb.p, fb.n, (uint64_t)std::count(fb.p, fb.p + fb.n, (uint8_t)'\n'));
+            const uint64_t la = count_lines(fq.p, ua), lb = count_lines(fb.p, ub);
+            if (la & 3) croak("'%s': %llu lines at the end of the file, not a multiple of four", usr.c_str(), (unsigned long long)la);
+            if (lb & 3) croak("'%s': %llu lines at the end of the file, not a multiple of four", o.pair.c_str(), (unsigned long long)lb);
+            const uint64_t ra = la / 4, rb = lb / 4, r = std::min(ra, rb);
+            if (eof && eof2 && ra != rb) unequal(done + ra, done + rb);
+            if (!r) {
+                if ((eof && !ra) || (eof2 && !rb)) unequal(done + count_rest(in, fq, eof), done + count_rest(in2, fb, eof2));
+                continue;                                               // not one whole record of a file yet: read on
+            }
+            ua = drop_records(fq.p, ua, ra - r); ub = drop_records(fb.p, ub, rb - r);
+            decide_tables(eof && eof2 ? ua + ub : (64ull << 20));
+            const size_t bound = (size_t)sfq_encode_bound(ua + ub);
+            if (!out.reserve(bound)) croak("out of memory");
+            out.touch((ua + ub) / 3 + (1 << 20));
+            sfq_result res;
+            if (sfq_encode_pairs_host(ctx, fq.p, ua, fb.p, ub, &p, out.p, bound, &res)) croak("%s", sfq_last_error(ctx));
+            tick("sfq_encode_pairs_host");
+            qmap_changed += sfq_get_quality_map_changed(ctx);
+            collect(ctx, res, ua + ub, idx, o.checksum, o.stats);
+            for (int s = 0; s < SFQ_NSTREAMS; s++)
+                streams[s].insert(streams[s].end(), out.p + res.stream_offset[s], out.p + res.stream_offset[s] + res.stream_bytes[s]);
+            memmove(fq.p, fq.p + ua, fq.n - ua); fq.n -= ua;
+            memmove(fb.p, fb.p + ub, fb.n - ub); fb.n -= ub;
+            done += r;
+        }
+        fclose(in2);
+        eof = true; fq.n = 0;                                           // nothing left for the loop below
+    }
     for (;;) {
         if (eof && fq.n == 0) break;
         // the reference's single adaptive state (format 6) cannot be cut: one slab holds the whole file
@@ -482,6 +568,7 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         a.set("num_records", (long long)idx.records);
         if (!o.quiet && b.extra_hi) a.set("qlt.extra.hi", b.extra_hi);
     } else a.info = idx.info(o.level, orig_name, frozen, false);
+    if (paired) a.set("usr.pair", 1);                                  // R1 R2 R1 R2 ...: a decode with -p splits them again
     if (o.qmap) {                                                      // (the reference reads its info page into a map: keys it does not know are no harm)
         a.set("qlt.map", o.qmap_name);
         a.set("qlt.map.changed", (long long)qmap_changed);
@@ -562,7 +649,16 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         if (o.r_first >= total) croak("-R %llu:%llu: the archive holds %llu records", (unsigned long long)o.r_first, (unsigned long long)o.r_count, (unsigned long long)total);
         r_lo = o.r_first; r_hi = o.r_count > total - r_lo ? total : r_lo + o.r_count;
     }
+    const bool paired = !o.pair.empty();
+    if (paired && a.get_long("usr.pair", 0) != 1) croak("-p: %s was not written from paired files (no usr.pair in its info): decode it without -p", fil.c_str());
     FILE* of = stdout;
+    FILE* of2 = nullptr;
+    if (paired) {
+        if (!o.overwrite && access(o.pair.c_str(), F_OK) == 0) { fprintf(stderr, "Can't write file '%s': File exists\n", o.pair.c_str()); exit(1); }
+        if (!o.overwrite && access(usr.c_str(), F_OK) == 0) { fprintf(stderr, "Can't write file '%s': File exists\n", usr.c_str()); exit(1); }
+        of2 = fopen(o.pair.c_str(), "wb");
+        if (!of2) { fprintf(stderr, "Can't write file '%s'\n", o.pair.c_str()); exit(1); }
+    }
     if (!usr.empty()) {
         if (!o.overwrite && access(usr.c_str(), F_OK) == 0) {
             if (g_batch) croak("Can't write file '%s': File exists", usr.c_str());
@@ -578,6 +674,7 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     p.level = level; p.version = version >= kBlockVersionMin ? kInternalVersion : (uint32_t)version;
     // (a -b worker keeps its context from job to job: a -K encode before this job left the pass on; installed checksums run it)
     if (sfq_ctx_set_checksums(ctx, 0)) croak("%s", sfq_last_error(ctx));
+    if (sfq_ctx_set_pair_split(ctx, paired ? 1 : 0)) croak("%s", sfq_last_error(ctx));
     // walk the segments: each one's blocks, its slice of every stream (streams are segment-major), its prior
     size_t b0 = 0, pri_off = 0, chn_off = 0, rpr_off = 0;
     uint64_t spos[SFQ_NSTREAMS] = {0};
@@ -677,11 +774,17 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             const size_t to = from + records_end(dst + from, (size_t)got - from, hi - lo);
             dst += from; got = to - from;
         }
+        // -p: the call handed back the first mates, then (from `first` on) the second mates
+        uint64_t first = got;
+        if (paired && sfq_get_pair_split(ctx, &first, nullptr) != 1) croak("-p: the library did not split the text");
+        auto write_out = [dst, got, first, of, of2]() {
+            return fwrite(dst, 1, (size_t)first, of) == first && (got == first || fwrite(dst + first, 1, (size_t)(got - first), of2) == got - first);
+        };
         writer.join();
         if (wbad) croak("USR: Error writing output");
-        if (in_out) { if (fwrite(dst, 1, (size_t)got, of) != got) croak("USR: Error writing output"); }
+        if (in_out) { if (!write_out()) croak("USR: Error writing output"); }
         else {
-            writer.start([dst, got, of, &wbad]() { if (fwrite(dst, 1, (size_t)got, of) != got) wbad = 1; });
+            writer.start([write_out, &wbad]() { if (!write_out()) wbad = 1; });
             ob ^= 1;
         }
         tick("write output");
@@ -690,6 +793,7 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     writer.join();
     if (wbad) croak("USR: Error writing output");
     if (of != stdout) fclose(of); else fflush(stdout);
+    if (of2) fclose(of2);
 }
 
 int main(int argc, char** argv) {
@@ -697,7 +801,7 @@ int main(int argc, char** argv) {
     Opts o;
     bool statistics = false;
     if (argc == 1) usage();
-    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKY1234u:f:l:B:g:S:T:C:t:R:Q:")) != -1;) {
+    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKY1234u:f:l:B:g:S:T:C:t:R:Q:p:")) != -1;) {
         switch (opt) {
         case 'u': g_usr = optarg; break;
         case 'f': fil = optarg; break;
@@ -721,6 +825,7 @@ int main(int argc, char** argv) {
             o.qmap_name = optarg;
             o.qmap = o.qmap_name == "illumina8" ? SFQ_QMAP_ILLUMINA8 : o.qmap_name == "novaseq4" ? SFQ_QMAP_NOVASEQ4 : -1;
             break;
+        case 'p': o.pair = optarg; break;
         case 'R': if (!parse_range(optarg, o.r_first, o.r_count)) usage(); o.range = true; break;
         case 'C': o.chain_reads = strtol(optarg, 0, 0); break;
         case 't': o.io_threads = std::min(64, std::max(1, atoi(optarg))); break;
@@ -747,6 +852,15 @@ int main(int argc, char** argv) {
 
     if (o.range && g_encode) {
         fprintf(stderr, "slimfastq: -R (a range of records) goes with -d: it picks what a decode writes\n");
+        return 1;
+    }
+
+    if (!o.pair.empty() && g_batch) {
+        fprintf(stderr, "slimfastq: -p (paired files) names one file: it does not go with -b, whose jobs name theirs\n");
+        return 1;
+    }
+    if (!o.pair.empty() && o.range) {
+        fprintf(stderr, "slimfastq: -p (paired files) does not go with -R: a range may start at a second mate\n");
         return 1;
     }
 
@@ -793,6 +907,10 @@ int main(int argc, char** argv) {
         else if (!g_encode && g_usr.empty()) g_usr = file;
         else if (g_encode && fil.empty()) fil = file;
         else { fprintf(stderr, "What am I suppose to do with '%s'?\n (please specify explicitly with -f/-u prefix)\n", file); exit(1); }
+    }
+    if (!o.pair.empty() && !statistics && g_usr.empty()) {
+        fprintf(stderr, "slimfastq: -p (paired files) needs -u: the first mates are a file, not %s\n", g_encode ? "stdin" : "stdout");
+        return 1;
     }
     if (fil.empty()) { fprintf(stderr, "Missing essential argument: -f\n"); exit(1); }
 

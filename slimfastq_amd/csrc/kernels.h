@@ -279,3 +279,26 @@ void launch_text_stats(const u8* fq, u64 n, const u64* line_off, u64 nrec, void*
 struct QmapScratch { u64 nspans = 0, cnt_off = 0, before_off = 0, tmp_off = 0, bytes = 0; };
 QmapScratch qmap_scratch(const u8* d, u64 n);
 void launch_quality_map(u8* d, u64 n, const u8* d_lut, u8* scratch, u64* d_changed, hipStream_t st);
+// its first step alone: the '\n' bytes of every span of [d, d + n) into cnt[qmap_scratch(d, n).nspans]
+void launch_newline_counts(const u8* d, u64 n, u32* cnt, hipStream_t st);
+
+// Paired files (pair.hip): two texts record by record into one (A0 B0 A1 B1 ...), and such a text back into its even records followed
+// by its odd ones.  Both passes find the records themselves -- the line ends per span, their scan, then the offset of every fourth
+// line end -- check what they found and copy only where it holds: *info tells the host, which synchronises once.
+enum PairStatus : u32 {
+    PAIR_OK = 0,
+    PAIR_LINES_A,           // the (first) text's lines are no multiple of four
+    PAIR_LINES_B,
+    PAIR_COUNTS,            // A and B hold different record counts
+    PAIR_A_END,             // A does not end in '\n'
+    PAIR_ODD,               // an odd number of records to split
+    PAIR_LONG,              // a record of 4 GiB or more
+    PAIR_CAP                // more records than the start arrays hold: info->recs says how many, nothing else was done
+};
+struct PairInfo { u64 lines[2], recs[2], split; u32 status, pad; };
+// a text and what the passes over it need: scratch = qmap_scratch(d, n).bytes bytes, 16-byte aligned; starts: cap + 1 entries
+struct PairText { const u8* d; u64 n; u8* scratch; u64* starts; };
+// info: zeroed by the caller.  out: a.n + b.n bytes; nothing outside them is written, and nothing at all unless info->status stays 0
+void launch_pair_interleave(const PairText& a, const PairText& b, u64 cap /* records a start array holds */, u8* out, PairInfo* info, hipStream_t st);
+// out: t.n bytes, the even records then (from info->split on) the odd ones; lens[cap / 2 + 1], offa[cap / 2 + 2], scan_tmp as launch_scan_u32 wants it for cap / 2 + 1
+void launch_pair_split(const PairText& t, u64 cap, u32* lens, u64* offa, u64* scan_tmp, u8* out, PairInfo* info, hipStream_t st);

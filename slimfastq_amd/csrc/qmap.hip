@@ -16,65 +16,18 @@
 // nothing outside [text, text + n): interior units are stored whole, the (at most two) ragged units byte by byte.
 // The table never moves a '\n' and never makes one (sfq_quality_map_check), so the counts of step 1 hold while step 3 writes.
 #include "kernels.h"
+#include "dev_lines.h"
 
 namespace {
 
-constexpr u32 ROW = 1024;                      // bytes a wavefront reads with one load instruction (64 lanes x 16)
-constexpr u32 SPAN_ROWS = 16;
-constexpr u32 SPAN = ROW * SPAN_ROWS;          // 16 KiB: the text a wavefront takes at a time
-constexpr u32 BATCH = 4;                       // rows a wavefront loads before it looks at the first
-constexpr u32 MAX_WG = 2048;                   // workgroups of a launch; each strides over the tiles of 4 spans
+using namespace textspan;          // dev_lines.h: ROW, SPAN, the unit loads, newline_mask, the wave sums
 
-__device__ __forceinline__ u32 wave_incl_add(u32 v, u32 lane) {
-#pragma unroll
-    for (u32 o = 1; o < 64; o <<= 1) { const u32 t = (u32)__shfl_up((int)v, o, 64); if (lane >= o) v += t; }
-    return v;
-}
-__device__ __forceinline__ u32 wave_sum(u32 v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v += (u32)__shfl_xor((int)v, o, 64);
-    return v;
-}
-// bit 7 of every byte of x that is not zero (exact: no carry leaves a byte)
-__device__ __forceinline__ u32 nonzero_bytes(u32 x) { return (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u; }
-// bits 7, 15, 23, 31 -> bits 0 .. 3 (the four partial products land on bits 21 .. 24, no two on one bit)
-__device__ __forceinline__ u32 gather_bit7(u32 t) { return (((t >> 7) * 0x00204081u) >> 21) & 0xFu; }
-// bit j: byte j of the unit is '\n'
-__device__ __forceinline__ u32 newline_mask(uint4 v) {
-    const u32 w[4] = { v.x, v.y, v.z, v.w };
-    u32 m = 0;
-#pragma unroll
-    for (u32 i = 0; i < 4; i++) m |= gather_bit7(~nonzero_bytes(w[i] ^ 0x0A0A0A0Au) & 0x80808080u) << (4 * i);
-    return m;
-}
 // bit j: the parity of the bits below j of a 16-bit mask
 __device__ __forceinline__ u32 parity_below(u32 m) {
     u32 x = m << 1;
     x ^= x << 1; x ^= x << 2; x ^= x << 4; x ^= x << 8;
     return x & 0xFFFFu;
 }
-// The unit of `lane` in the row that starts at text offset rb: *ub = its offset (negative in front of the text), the result
-// the mask of its bytes that are text.  EDGE = false: the span lies inside the text, every byte of every unit is text.
-template <bool EDGE>
-__device__ __forceinline__ u32 unit_mask(i64 rb, i64 n, u32 lane, i64* ub) {
-    *ub = rb + 16 * (i64)lane;
-    if (!EDGE) return 0xFFFFu;
-    if (*ub >= n || *ub + 16 <= 0) return 0u;
-    const u32 jlo = *ub < 0 ? (u32)(-*ub) : 0u;
-    const u32 jhi = n - *ub < 16 ? (u32)(n - *ub) : 16u;
-    return ((1u << jhi) - 1u) & ~((1u << jlo) - 1u);
-}
-template <bool EDGE>
-__device__ __forceinline__ void load_batch(const u8* fq, i64 n, i64 rb0, u32 lane, uint4 (&v)[BATCH], u32 (&vm)[BATCH]) {
-#pragma unroll
-    for (u32 k = 0; k < BATCH; k++) {
-        i64 ub;
-        vm[k] = unit_mask<EDGE>(rb0 + (i64)k * ROW, n, lane, &ub);
-        v[k] = make_uint4(0, 0, 0, 0);
-        if (vm[k]) v[k] = *reinterpret_cast<const uint4*>(fq + ub);
-    }
-}
-
 // ---- 1. line ends per span ---------------------------------------------------------------------------------------------------
 template <bool EDGE>
 __device__ __forceinline__ u32 count_span(const u8* fq, i64 n, i64 s0, u32 lane) {
@@ -180,6 +133,13 @@ QmapScratch qmap_scratch(const u8* d, u64 n) {
     return q;
 }
 
+void launch_newline_counts(const u8* d, u64 n, u32* cnt, hipStream_t st) {
+    if (!n) return;
+    const u32 mis = (u32)((uintptr_t)d & 15);
+    const u64 nspans = (mis + n + SPAN - 1) / SPAN, tiles = (nspans + 3) / 4;
+    hipLaunchKernelGGL(k_qmap_count, dim3((u32)(tiles < MAX_WG ? tiles : MAX_WG)), dim3(256), 0, st, d - mis, mis, n, nspans, cnt);
+}
+
 void launch_quality_map(u8* d, u64 n, const u8* d_lut, u8* scratch, u64* d_changed, hipStream_t st) {
     if (!n) return;
     const QmapScratch q = qmap_scratch(d, n);
@@ -189,7 +149,7 @@ void launch_quality_map(u8* d, u64 n, const u8* d_lut, u8* scratch, u64* d_chang
     u64* tmp = reinterpret_cast<u64*>(scratch + q.tmp_off);
     const u64 tiles = (q.nspans + 3) / 4;
     const u32 wg = (u32)(tiles < MAX_WG ? tiles : MAX_WG);
-    hipLaunchKernelGGL(k_qmap_count, dim3(wg), dim3(256), 0, st, (const u8*)(d - mis), mis, n, q.nspans, cnt);
+    launch_newline_counts(d, n, cnt, st);
     launch_scan_u32(cnt, before, q.nspans, tmp, st);
     hipLaunchKernelGGL(k_qmap_apply, dim3(wg), dim3(256), 0, st, d - mis, mis, n, q.nspans, (const u64*)before, d_lut, d_changed);
 }
