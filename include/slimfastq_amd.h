@@ -196,7 +196,18 @@ void  sfq_host_free(sfq_ctx* ctx, void* p);
  * of FASTQ text resident on the device.  d_out receives, stream after stream, the concatenation of
  * every block's bytes for that stream; sfq_get_block_index() tells the per-block sizes.
  * Worst-case d_out size: sfq_encode_bound(nbytes). Asynchronous errors are reported at return
- * (the call synchronizes the context's stream once, at the end). */
+ * (the call synchronizes the context's stream once, at the end).
+ * PLACEMENT (sfq_encode_blocks, sfq_encode_qlt_blocks, sfq_build_priors, sfq_count_priors; sfq_decode_blocks and
+ * sfq_decode_block_range below): d_fastq, d_streams and either output may lie at ANY address, whatever its alignment, inside a
+ * larger buffer with live data on both sides.  No byte outside [d_fastq, d_fastq + nbytes) influences a result, and none outside
+ * the extents of the streams -- [d_streams + stream_offset[s], + the sum of the blocks' size[s]) for every stream s -- does; an
+ * input is never written.  Nothing outside [d_out, d_out + out_cap) / [d_fastq_out, d_fastq_out + out_cap) is written (inside it,
+ * bytes behind the result may be).  Unlike sfq_crc32 and the other side passes, which read the whole aligned 16-byte units of their
+ * text's first and last byte, these entries READ no byte outside those extents either: every wide load of the text and of a
+ * stream is bounded by the extent's end and falls back to single bytes there, and the few loads that run past a LINE's end (a
+ * header's last dword) stay inside the text, which goes on behind every header.  tests/test_placement.py holds the first three
+ * statements at every kind of offset from a 16-byte boundary, between guard bytes that would show; the last is by reading the
+ * kernels. */
 uint64_t sfq_encode_bound(uint64_t fastq_bytes);
 int sfq_encode_blocks(sfq_ctx* ctx, const uint8_t* d_fastq, uint64_t nbytes, const sfq_params* params,
                       uint8_t* d_out, uint64_t out_cap, sfq_result* result);

@@ -28,6 +28,15 @@ def gm_table_bits(nbytes):
     return tb
 
 
+def gm_chain_reads(nbytes, nrec, br, cr):
+    """Records per BASE chain of a call that takes the match model: such chains are cut shorter than the quality chains (api.cpp): 2 KiB of text each
+    or more (about 819 200 a call), of equal length inside a block"""
+    per = max(1, nbytes // max(1, nrec))
+    gcpb = -(-br // min(max(-(-2048 // per), -(-nrec // 819200)), cr))
+    gcr = max(1, -(-min(br, nrec) // gcpb))
+    return cr if gcr >= cr else gcr
+
+
 def base_chains_oracle(fq, goff, glen, ci, br, cr, seg=0, other=None, quads=False):
     """The base chains as the oracle's restatement of the generation MATCH model (gm.hip; sfq_oracle.c sfqo_gm_*) writes them, and
     its verdict; "chn.idx" must say the same (flag bit 0: the model is on; bit 5 + the index's bits: it is the match model)."""
@@ -36,14 +45,8 @@ def base_chains_oracle(fq, goff, glen, ci, br, cr, seg=0, other=None, quads=Fals
         want, sizes, on = O.gm_encode_segs(fq, goff, glen, other, tb, br, seg)
         gcr = 1
     else:
-        # the base chains of a call that takes the model are cut shorter than the quality chains (api.cpp): 2 KiB of text each or more (about 819 200 a call), of equal
-        # length inside a block; a call that does not take it keeps the quality chains' records
-        nrec = len(goff)
-        per = max(1, len(fq) // max(1, nrec))
-        gcpb = -(-br // min(max(-(-2048 // per), -(-nrec // 819200)), cr))
-        gcr = max(1, -(-min(br, nrec) // gcpb))
-        if gcr >= cr:
-            gcr = cr
+        # (a call that does not take the model keeps the quality chains' records)
+        gcr = gm_chain_reads(len(fq), len(goff), br, cr)
         want, sizes, on = O.gm_encode_chains(fq, goff, glen, tb, br, gcr)
         if not on:
             want, sizes, on = O.gm_encode_chains(fq, goff, glen, tb, br, cr)
@@ -56,8 +59,11 @@ def base_chains_oracle(fq, goff, glen, ci, br, cr, seg=0, other=None, quads=Fals
     return want, sizes, on
 
 
-def check_against_oracle(ctx, fq, level, br, cr, step, what="", quads=False):
-    enc = ctx.encode_host(fq, level=level, block_reads=br, prior_step=step, tables=capi.TABLES_FROZEN, chain_reads=cr)
+def check_against_oracle(ctx, fq, level, br, cr, step, what="", quads=False, enc=None):
+    """enc: the Encoded of a call with these parameters that the caller has made itself (Context._encoded of an encode_device result: a text
+    placed in the caller's own device memory); without it the text is coded here, through encode_host.  Either way every assertion below runs."""
+    if enc is None:
+        enc = ctx.encode_host(fq, level=level, block_reads=br, prior_step=step, tables=capi.TABLES_FROZEN, chain_reads=cr)
     starts, lens = util.line_table(fq)
     nrec = len(starts) // 4
     solid = enc.blocks[0].solid

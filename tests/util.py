@@ -193,6 +193,72 @@ def unpack_rec_prior(blob: bytes):
     return f
 
 
+# ---- device buffers placed at any address, between guards that would show (tests/test_placement.py) -------------------------------
+GUARD = 256                                                # bytes on either side of a placed buffer
+# (offset of the text or the streams, offset of the output) behind a 16-byte boundary: the control first
+PLACEMENTS = ((0, 0), (1, 15), (4, 4), (7, 2), (8, 0), (13, 8), (15, 1))
+FILLS = ("fastq", "ff")
+_GUARD_PIECE = b"\n@g 1\nNnACGT.\n+\n!!II!"                # plausible FASTQ: line ends, '@' / '+', '!', N-like and lower-case bytes
+
+
+def guard_fill(fill: str, before: int, after: int):
+    """The guard bytes (before, after) a placed buffer lies between.  "fastq": a repeating piece of FASTQ that continues a text -- the
+    guard in front ends in a line end, the one behind starts with an '@' --; "ff": 0xFF throughout."""
+    if fill == "ff":
+        return b"\xff" * before, b"\xff" * after
+    assert fill == "fastq"
+    p = _GUARD_PIECE
+    front = (p[1:] + p[:1]) * (before // len(p) + 1)       # ... "!!II!\n"
+    back = (p[1:] + p[:1]) * (after // len(p) + 1)         # "@g 1\n" ...
+    return front[len(front) - before:], back[:after]
+
+
+class Placed:
+    """n bytes on the device that start off bytes behind a 16-byte boundary, GUARD bytes or more of `fill` on either side (guard_fill):
+    bytes that would change a result if a kernel used them, and that must come back as they were."""
+
+    def __init__(self, n, off, fill, data=None):
+        import torch
+        assert 0 <= off < 16
+        self.n, self.off, self.fill = n, off, fill
+        self.t = torch.empty(n + 2 * GUARD + 32, dtype=torch.uint8, device="cuda")
+        self.base = (-self.t.data_ptr()) % 16 + GUARD + off
+        self.ptr = self.t.data_ptr() + self.base
+        assert self.ptr % 16 == off
+        front, back = guard_fill(fill, self.base, self.t.numel() - self.base - n)
+        body = bytes(data) if data is not None else b"\xa5" * n
+        assert len(body) == n
+        self._front = torch.frombuffer(bytearray(front), dtype=torch.uint8).cuda()
+        self._back = torch.frombuffer(bytearray(back), dtype=torch.uint8).cuda()
+        self.t.copy_(torch.frombuffer(bytearray(front + body + back), dtype=torch.uint8))
+        torch.cuda.synchronize()                           # (the library runs on a stream of its own)
+
+    def guards_intact(self):
+        import torch
+        torch.cuda.synchronize()
+        return torch.equal(self.t[:self.base], self._front) and torch.equal(self.t[self.base + self.n:], self._back)
+
+    def head(self, k):
+        """the first k of the n bytes"""
+        assert k <= self.n
+        return self.t[self.base:self.base + k].cpu().numpy().tobytes()
+
+    def back(self, what):
+        """the n bytes; the guards must come back untouched"""
+        assert self.guards_intact(), "a guard byte of %s was written" % what
+        return self.head(self.n)
+
+
+def first_difference(got: bytes, want: bytes, what: str):
+    """got == want, or an AssertionError that names the first byte that differs"""
+    if got != want:
+        m = min(len(got), len(want))
+        a, b = np.frombuffer(got, np.uint8, m), np.frombuffer(want, np.uint8, m)
+        bad = np.flatnonzero(a != b)
+        raise AssertionError("%s: got %d bytes, want %d; %d bytes differ, the first at %d" %
+                             (what, len(got), len(want), len(bad), bad[0] if len(bad) else m))
+
+
 def block_reference(chunk: bytes, level: int, gen_bits: int = 0):
     """The oracle's archive for ONE block of the block format: the reference run on a FASTQ holding only that block's
     records, with the block format's lossless rules (oracle sfqo_opts.lossless: where the reference would alter the text
