@@ -13,3 +13,5 @@ static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
 static inline uint32_t __umulhi(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) >> 32); }
 static inline uint32_t __builtin_amdgcn_alignbit(uint32_t hi, uint32_t lo, uint32_t sh) { return (uint32_t)((((uint64_t)hi << 32) | lo) >> (sh & 31)); }
 static inline int __any(int x) { return x; }
+static inline int __builtin_amdgcn_readfirstlane(int x) { return x; }
+static inline float __builtin_amdgcn_rcpf(float x) { return 1.0f / x; }

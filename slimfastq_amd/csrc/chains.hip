@@ -256,8 +256,24 @@ void launch_seg_fill(const u64* seg_off, u64 nrec, u32* seg_rec, hipStream_t st)
 #define QLT_STEP 2u      /* symbols whose row entries are looked up at a time, a step ahead of the coder (16 / QLT_STEP steps a piece) */
 #endif
 #define QLT_RING 8       // ring dwords per lane: 15 bytes may wait for their row of 16, four symbols add at most 4 x (2 + 2 escape)
+// The quality model's step, stated once for the encoder and the decoder: the context of the next symbol from the symbol b just seen.
+// HI = levels 3 and 4 (qlts.hpp:62-74: the last symbol, the larger of the two before it, whether those are equal, and how far the
+// qualities have fallen along the line); levels 1 and 2 (qlts.hpp:52-57) keep the last two or three symbols, mask12 says which.
+// The level is the same for a whole call, so the encoder takes HI as a template parameter: tested per symbol it was a scalar branch
+// pair and three register copies where the arms join, at every one of the kernel's 48 symbol sites.
+template <bool HI>
+__device__ __forceinline__ void qlt_model_step(u32 b, u32 mask12, u32& last, u32& p1, u32& p2, u32& delta) {
+    if constexpr (!HI) last = (b | (last << 6)) & mask12;
+    else {
+        delta += max(p1, b) - b;                                                     // if (p1 > b) delta += p1 - b
+        const u32 d3 = delta >> 3;
+        last = (b | ((p1 < p2 ? p2 : p1) << 6) | ((u32)(p1 == p2) << 12) | ((d3 < 7 ? d3 : 7) << 13)) & 0xFFFFu;
+        p2 = p1; p1 = b;
+    }
+}
 // MARK: the chains mark the records with a '!' for the exception pass (a.exc_flag; the framing does that where it can)
-template <int THREADS, bool LDS, bool MARK>
+// HI: the model of levels 3 and 4 (qlt_model_step above)
+template <int THREADS, bool LDS, bool MARK, bool HI>
 __global__ __launch_bounds__(THREADS) void k_qlt_encode_c(ChainArgs a) {
     __shared__ u32 ring[LaneEncB<THREADS, QLT_RING>::LDS_DWORDS];
     extern __shared__ u32 lds[];                              // the hot image: map, then rows
@@ -277,8 +293,7 @@ __global__ __launch_bounds__(THREADS) void k_qlt_encode_c(ChainArgs a) {
     LaneEncB<THREADS, QLT_RING> rc; u32 cap = 0;
     u8* outp = live ? chain_region(a, cp, SFQ_S_QLT, 2, 1, cap) : nullptr;
     rc.init(ring, threadIdx.x, outp, cap);
-    const int level = a.m.level;
-    const u32 mask12 = level == 1 ? 0xFFFu : 0xFFFFu;
+    const u32 mask12 = a.m.level == 1 ? 0xFFFu : 0xFFFFu;
     LineWalk lw; lw.init(a, cp.r0, cp.nrec, 3, live ? d->solid : 0u, cp.sub_lo, cp.sub_len);
     u32 last = 0, p1 = 0, p2 = 0, delta = 5;
     u32 extra = 0;
@@ -316,13 +331,7 @@ __global__ __launch_bounds__(THREADS) void k_qlt_encode_c(ChainArgs a) {
                 const u32 g = (u32)__builtin_amdgcn_raw_buffer_load_b32(qtab, (int)(((last << 8) | (sym << 2)) | hm), 0, 0);
                 e[jj] = (c0 | ((c1 - c0) << 16)) & hm; eg[jj] = g;                 // (ORed where the entry is used: the table's answer need not be there before)
             } else { e[jj] = a.qrows[(size_t)last * 64 + sym]; eg[jj] = 0; }
-            if (level <= 2) last = (b | (last << 6)) & mask12;                           // qlts.hpp:52-57
-            else {                                                                       // qlts.hpp:62-74
-                delta += max(p1, b) - b;                                                 // if (p1 > b) delta += p1 - b
-                const u32 d3 = delta >> 3;
-                last = (b | ((p1 < p2 ? p2 : p1) << 6) | ((u32)(p1 == p2) << 12) | ((d3 < 7 ? d3 : 7) << 13)) & 0xFFFFu;
-                p2 = p1; p1 = b;
-            }
+            qlt_model_step<HI>(b, mask12, last, p1, p2, delta);
         }
     };
     // (b) the serial part: the range coder, eight symbols
@@ -396,21 +405,26 @@ __global__ __launch_bounds__(THREADS) void k_qlt_encode_c(ChainArgs a) {
         else if (rc.err) atomicMax(&a.m.blocks[cp.b].status, (u32)(-SFQ_E_CORRUPT));
     }
 }
-template <int T>
+// (a function per level class: each instantiation has its own `allowed`, so the attribute is set on the kernel that is launched)
+template <int T, bool HI>
 static void launch_qlt_lds(const ChainArgs& a, u32 dyn, hipStream_t st) {
     static u32 allowed = 0;
-    if (dyn > allowed) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_qlt_encode_c<T, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); allowed = dyn; }
-    hipLaunchKernelGGL((k_qlt_encode_c<T, true, false>), dim3((a.geo.nchains + T - 1) / T), dim3(T), dyn, st, a);
+    if (dyn > allowed) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_qlt_encode_c<T, true, false, HI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); allowed = dyn; }
+    hipLaunchKernelGGL((k_qlt_encode_c<T, true, false, HI>), dim3((a.geo.nchains + T - 1) / T), dim3(T), dyn, st, a);
 }
-void launch_qlt_encode_c(const ChainArgs& a, hipStream_t st) {
-    if (a.exc_flag) { hipLaunchKernelGGL((k_qlt_encode_c<256, false, true>), dim3((a.geo.nchains + 255) / 256), dim3(256), 0, st, a); return; }   // (chains that mark: no caller does)
+template <bool HI>
+static void launch_qlt_encode_lv(const ChainArgs& a, hipStream_t st) {
+    if (a.exc_flag) { hipLaunchKernelGGL((k_qlt_encode_c<256, false, true, HI>), dim3((a.geo.nchains + 255) / 256), dim3(256), 0, st, a); return; }   // (chains that mark: no caller does)
     if (a.q_hot) {
         // One workgroup of 1024 lanes per CU shares the image (a table per 256 lanes would hold a quarter of the rows).  The default
         // geometry aims at as many chains as 256 such workgroups hold, one per CU (api.cpp SFQ_CHAINS_WANT; DESIGN.md 4.5 on why
         // not the 200 of rounds 4 and 5a).  With workgroups of 832 lanes the quality chains took as long and the header coder 6.1 ms instead of 2.5.
         const u32 dyn = QH_MAP_BYTES(a.q_rows) + a.q_hot * QH_ROW_U16 * 2u;
-        launch_qlt_lds<1024>(a, dyn, st);
-    } else hipLaunchKernelGGL((k_qlt_encode_c<256, false, false>), dim3((a.geo.nchains + 255) / 256), dim3(256), 0, st, a);
+        launch_qlt_lds<1024, HI>(a, dyn, st);
+    } else hipLaunchKernelGGL((k_qlt_encode_c<256, false, false, HI>), dim3((a.geo.nchains + 255) / 256), dim3(256), 0, st, a);
+}
+void launch_qlt_encode_c(const ChainArgs& a, hipStream_t st) {
+    if (a.m.level <= 2) launch_qlt_encode_lv<false>(a, st); else launch_qlt_encode_lv<true>(a, st);      // the level's class is a constant of the kernel
 }
 
 // =========================================================================================================
@@ -509,13 +523,9 @@ __global__ __launch_bounds__(THREADS) void k_qlt_decode_c(ChainArgs a, DecodeArg
                 rc.decode(re, b << 8, 256u);
             }
             out.put(('!' + b) & 0xffu);
-            if (level <= 2) last = (b | (last << 6)) & mask12;
-            else {
-                delta += max(p1, b) - b;                                    // if (p1 > b) delta += p1 - b
-                const u32 d3 = delta >> 3;
-                last = (b | ((p1 < p2 ? p2 : p1) << 6) | ((u32)(p1 == p2) << 12) | ((d3 < 7 ? d3 : 7) << 13)) & 0xFFFFu;
-                p2 = p1; p1 = b;
-            }
+            // (the level stays a run-time test here: as a template parameter it left the decode leg where it was)
+            if (level <= 2) qlt_model_step<false>(b, mask12, last, p1, p2, delta);
+            else qlt_model_step<true>(b, mask12, last, p1, p2, delta);
         }
         out.end();
     }

@@ -108,11 +108,17 @@ struct LaneEncB {
     }
     __device__ __forceinline__ void renorm() {
         step();
-        int guard = 0;
+        // Rare: a symbol of probability < 2^-8.  The second and later rounds are a block of their own behind one scalar test, and their
+        // guard is a scalar that lives in that block alone.  (As `while (__any(..)) { step(); if (++guard > ..) .. }` the counter was a
+        // vector register set to zero in front of every symbol, and err and the counter were copied on the path that skips the loop.)
+        if (__builtin_expect(__any(range < RC_TOP), 0)) {
+            u32 guard = 0;
 #pragma nounroll
-        while (__any(range < RC_TOP)) {                                       // rare: a symbol of probability < 2^-8
-            step();
-            if (++guard > RC_GUARD) { err = 1; range = 0xFFFFFFFFu; break; }
+            do {
+                step();
+                guard = (u32)__builtin_amdgcn_readfirstlane((int)(guard + 1u));
+                if (guard > RC_GUARD) { err = 1; range = 0xFFFFFFFFu; break; }
+            } while (__any(range < RC_TOP));
         }
     }
     // the arithmetic of encode() for the lanes whose mask vm is all ones; the others keep their state
