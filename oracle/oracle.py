@@ -477,6 +477,37 @@ def gm_encode_segs(buf: bytes, goff, glen, other_len, table_bits, block_reads, s
     return _take(out, n), sizes, on.value
 
 
+# the event bits of the walk's trace (sfq_oracle.c GMT_*)
+GMT_LOOKUP, GMT_EMPTY, GMT_CHECK, GMT_LIM, GMT_FOUND, GMT_REFUSED, GMT_DROP_MISS, GMT_DROP_END = (1 << k for k in range(8))
+
+
+def gm_trace(buf: bytes, goff, glen, table_bits, block_reads, chain_reads=1, seg_len=0, other_len=None):
+    """What the oracle's walk did at every staged base while it wrote the chains of gm_encode_chains (seg_len: of gm_encode_segs) ->
+    dict(on, soff, tok, ev, m, dist, ptr): arrays over the stage's positions, soff[r] + i = base i of record r (sfq_oracle.c gmtrace)."""
+    L = lib()
+    goff, po = _arr(goff, np.uint64); glen, pl = _arr(glen, np.uint32)
+    soff = np.zeros(len(glen) + 1, np.int64)
+    np.cumsum(glen.astype(np.int64) + 1, out=soff[1:])
+    n = int(soff[-1])
+    t = dict(soff=soff, tok=np.zeros(n, np.uint8), ev=np.zeros(n, np.uint8), m=np.zeros(n, np.uint8), dist=np.zeros(n, np.uint16),
+             ptr=np.zeros(n, np.uint64))
+    arrays = [t[k].ctypes.data_as(C.c_void_p) for k in ("tok", "ev", "m", "dist", "ptr")]
+    on = C.c_int()
+    if seg_len:
+        other_len, pt = _arr(other_len, np.uint32)
+        L.sfqo_gm_trace_segs.restype = C.c_longlong
+        L.sfqo_gm_trace_segs.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_uint32] + [C.c_void_p] * 5 + [C.POINTER(C.c_int)]
+        got = L.sfqo_gm_trace_segs(buf, po, pl, pt, len(goff), table_bits, block_reads, seg_len, *arrays, C.byref(on))
+    else:
+        L.sfqo_gm_trace_chains.restype = C.c_longlong
+        L.sfqo_gm_trace_chains.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t] + [C.c_void_p] * 5 + [C.POINTER(C.c_int)]
+        got = L.sfqo_gm_trace_chains(buf, po, pl, len(goff), table_bits, block_reads, chain_reads, *arrays, C.byref(on))
+    if got < 0:
+        raise _err()
+    t["on"] = on.value
+    return t
+
+
 REC_ROWS = 66 * 16
 
 

@@ -1958,24 +1958,48 @@ long long sfqo_gen_encode_segs(const u8* base, const u64* goff, const u32* glen,
 #define GM_MCAP 31
 #define GM_EMPTY (~0ull)
 static u32 gm_fo(u32 m) { return m < 4 ? 64u : m < 8 ? 40u : m < 16 ? 24u : 16u; }
-typedef struct { const u8* st; const u64* T; int tb; u64 lim; chenc* c; u64 cost, nbases; } gmw;
+/* the walk's TRACE (tests only; sfqo_gm_trace_chains / _segs): what the walk that CODES did at every staged base -- arrays over the stage's
+   positions (soff[r] + i = base i of record r; a sentinel's entry stays zero), filled by gm_walk itself where a sink is given:
+     tok   the token k_gm_plan writes: 0 = coded flat, 0x80 | level << 2 | e = predicted base e at Fo level `level`;
+     ev    GMT_* bits: what happened at / behind this base;
+     m     with a pointer: the bases matched in a row when the base was predicted;
+     dist  with a pointer: its distance from the position p it was found at (GM_D at its first base; the window's offset is dist mod 16,
+           the window has shifted dist / 16 times);
+     ptr   with a pointer: its stage position; behind a base whose lookup met an entry (GMT_CHECK, GMT_LIM, GMT_FOUND): the position it held. */
+#define GMT_LOOKUP 1u        /* behind this base an entry was read (no pointer, none pending, a k-mer of the sampled quarter) */
+#define GMT_EMPTY 2u         /*   ... it was empty */
+#define GMT_CHECK 4u         /*   ... its check bits differ */
+#define GMT_LIM 8u           /*   ... its position is not below the generation's first */
+#define GMT_FOUND 16u        /*   ... taken: a pointer is pending */
+#define GMT_REFUSED 32u      /* the pointer due at this base was refused: a sentinel in [p, p + GM_D] */
+#define GMT_DROP_MISS 64u    /* this base missed with m < GM_DROP: the pointer is dropped */
+#define GMT_DROP_END 128u    /* the pointer stood at a sentinel: dropped before this base */
+typedef struct { u8* tok; u8* ev; u8* m; u16* dist; u64* ptr; } gmtrace;
+typedef struct { const u8* st; const u64* T; int tb; u64 lim; chenc* c; u64 cost, nbases; const gmtrace* tr; } gmw;
 static void gm_walk(gmw* w, u64 q0, size_t n) {
-    u32 kmer = 0, seen = 0, m = 0; int have = 0; u64 ptr = 0; long long pend_at = -1; u64 pend_p = 0;
+    u32 kmer = 0, seen = 0, m = 0; int have = 0; u64 ptr = 0, from = 0; long long pend_at = -1; u64 pend_p = 0;
     const u8* st = w->st;
+    const gmtrace* tr = w->tr;
     for (size_t i = 0; i < n; i++) {
         const u32 b = st[q0 + i];
+        u32 ev = 0;
         if (pend_at == (long long)i) {
             pend_at = -1;
             int ok = 1; for (int d = 0; d <= GM_D; d++) if (st[pend_p + d] == 0xFF) { ok = 0; break; }
-            if (ok) { have = 1; m = GM_K; ptr = pend_p + GM_D; }
+            if (ok) { have = 1; m = GM_K; ptr = pend_p + GM_D; from = pend_p; }
+            else ev |= GMT_REFUSED;
         }
-        if (have && st[ptr] == 0xFF) have = 0;
+        if (have && st[ptr] == 0xFF) { have = 0; ev |= GMT_DROP_END; }
         if (have) {
             const u32 e = st[ptr], fo = gm_fo(m), fm = 4096u - 3u * fo;
+            if (tr) {
+                tr->tok[q0 + i] = (u8)(0x80u | ((m < 4 ? 0u : m < 8 ? 1u : m < 16 ? 2u : 3u) << 2) | e);
+                tr->m[q0 + i] = (u8)m; tr->dist[q0 + i] = (u16)(ptr - from > 0xFFFF ? 0xFFFF : ptr - from); tr->ptr[q0 + i] = ptr;
+            }
             if (w->c) ch_encode(w->c, b * fo + (b > e ? fm - fo : 0u), b == e ? fm : fo, 4096);
             else w->cost += 12 * 1024 - log2fp(b == e ? fm : fo);
             if (b == e) { if (m < GM_MCAP) m++; ptr++; }
-            else if (m < GM_DROP) have = 0;
+            else if (m < GM_DROP) { have = 0; ev |= GMT_DROP_MISS; }
             else { m = 0; ptr++; }
         } else {
             if (w->c) ch_encode(w->c, b * 1024u, 1024u, 4096);
@@ -1988,8 +2012,13 @@ static void gm_walk(gmw* w, u64 q0, size_t n) {
             if ((h >> 62) == 0) {
                 const u64 e = w->T[(h >> (62 - w->tb)) & ((1ull << w->tb) - 1)];
                 if (e != GM_EMPTY && (e & 0xFFFFFF) == ((h >> (38 - w->tb)) & 0xFFFFFF) && (e >> 24) < w->lim) { pend_at = (long long)(i + 1 + GM_D); pend_p = e >> 24; }
+                if (tr) {
+                    ev |= GMT_LOOKUP | (pend_at >= 0 ? GMT_FOUND : e == GM_EMPTY ? GMT_EMPTY : (e & 0xFFFFFF) != ((h >> (38 - w->tb)) & 0xFFFFFF) ? GMT_CHECK : GMT_LIM);
+                    if (e != GM_EMPTY) tr->ptr[q0 + i] = e >> 24;
+                }
             }
         }
+        if (tr) tr->ev[q0 + i] = (u8)ev;
     }
 }
 static void gm_insert(const u8* st, const u64* soff, const u32* glen, size_t r0, size_t r1, size_t stride, u64* T, int tb) {
@@ -2009,7 +2038,7 @@ static void gm_insert(const u8* st, const u64* soff, const u32* glen, size_t r0,
     }
 }
 static long long gm_encode_x(const u8* base, const u64* goff, const u32* glen, size_t nrec, int tb, size_t block_reads, size_t chain_reads,
-                             u8** out, size_t* out_len, u32* sizes, int* gen_on, u32 seg_len, const u32* other_len) {
+                             u8** out, size_t* out_len, u32* sizes, int* gen_on, u32 seg_len, const u32* other_len, const gmtrace* tr) {
     g_failed = 0; g_err[0] = 0;
     if (tb < 8 || tb > 26) { fail("gm: table bits %d", tb); return -1; }
     const size_t nblocks = (nrec + block_reads - 1) / block_reads;
@@ -2031,7 +2060,7 @@ static long long gm_encode_x(const u8* base, const u64* goff, const u32* glen, s
         soff[nrec] = sp; memset(st + sp, 0xFF, 64);
         T = xmalloc(sizeof(u64) << tb); memset(T, 0xFF, sizeof(u64) << tb);
         gm_insert(st, soff, glen, REC_OF(bound[0]), REC_OF(bound[1]), GSTRIDE(0), T, tb);
-        gmw w = { st, T, tb, soff[REC_OF(bound[1])], NULL, 0, 0 };
+        gmw w = { st, T, tb, soff[REC_OF(bound[1])], NULL, 0, 0, NULL };                          /* (the verdict's walk leaves no trace) */
         for (size_t r = REC_OF(bound[1]); r < REC_OF(bound[2]); r += GSTRIDE(1) * 8)                       /* (in stretches of 256 bases, each walked as a line) */
             for (u32 lo = 0; lo < glen[r]; lo += 256) gm_walk(&w, soff[r] + lo, glen[r] - lo < 256 ? glen[r] - lo : 256);
         on = w.nbases && w.cost * 100 < w.nbases * 2048 * 99;
@@ -2058,7 +2087,7 @@ static long long gm_encode_x(const u8* base, const u64* goff, const u32* glen, s
                     const size_t lo = sg * L < glen[r] ? sg * L : glen[r];
                     const size_t cnt = glen[r] - lo < L ? glen[r] - lo : L;
                     chenc c; ch_init(&c);
-                    gmw w = { st, T, tb, lim, &c, 0, 0 };
+                    gmw w = { st, T, tb, lim, &c, 0, 0, tr };
                     gm_walk(&w, soff[r] + lo, cnt);                              /* (a segment starts as a line does) */
                     const size_t nb = ch_finish(&c);
                     ob_write(&o, c.out, nb);
@@ -2071,7 +2100,7 @@ static long long gm_encode_x(const u8* base, const u64* goff, const u32* glen, s
         for (size_t r0 = b0; r0 < b1; r0 += chain_reads, nc++) {
             const size_t r1 = r0 + chain_reads < b1 ? r0 + chain_reads : b1;
             chenc c; ch_init(&c);
-            gmw w = { st, T, tb, lim, &c, 0, 0 };
+            gmw w = { st, T, tb, lim, &c, 0, 0, tr };
             for (size_t r = r0; r < r1; r++) gm_walk(&w, soff[r], glen[r]);
             const size_t n = ch_finish(&c);
             ob_write(&o, c.out, n);
@@ -2193,11 +2222,29 @@ int sfqo_gm_steer_chains(const u8* streams, const u32* sizes, const u32* glen, s
 
 long long sfqo_gm_encode_chains(const u8* base, const u64* goff, const u32* glen, size_t nrec, int table_bits, size_t block_reads,
                                 size_t chain_reads, u8** out, size_t* out_len, u32* sizes, int* gen_on) {
-    return gm_encode_x(base, goff, glen, nrec, table_bits, block_reads, chain_reads, out, out_len, sizes, gen_on, 0, NULL);
+    return gm_encode_x(base, goff, glen, nrec, table_bits, block_reads, chain_reads, out, out_len, sizes, gen_on, 0, NULL, NULL);
 }
 long long sfqo_gm_encode_segs(const u8* base, const u64* goff, const u32* glen, const u32* other_len, size_t nrec, int table_bits, size_t block_reads,
                               u32 seg_len, u8** out, size_t* out_len, u32* sizes, int* gen_on) {
-    return gm_encode_x(base, goff, glen, nrec, table_bits, block_reads, 1, out, out_len, sizes, gen_on, seg_len, other_len);
+    return gm_encode_x(base, goff, glen, nrec, table_bits, block_reads, 1, out, out_len, sizes, gen_on, seg_len, other_len, NULL);
+}
+/* The walk's trace (tests only): the same calls, and what gm_walk did while it wrote their chains -- five arrays of sum(glen) + nrec entries each,
+   zeroed by the caller (see gmtrace).  Nothing is traced where the verdict leaves the model off (*gen_on = 0).  Returns the chains' number, or -1. */
+long long sfqo_gm_trace_chains(const u8* base, const u64* goff, const u32* glen, size_t nrec, int table_bits, size_t block_reads, size_t chain_reads,
+                               u8* tok, u8* ev, u8* m, uint16_t* dist, u64* ptr, int* gen_on) {
+    const gmtrace tr = { tok, ev, m, dist, ptr };
+    u8* out = NULL; size_t out_len = 0;
+    const long long rc = gm_encode_x(base, goff, glen, nrec, table_bits, block_reads, chain_reads, &out, &out_len, NULL, gen_on, 0, NULL, &tr);
+    free(out);
+    return rc;
+}
+long long sfqo_gm_trace_segs(const u8* base, const u64* goff, const u32* glen, const u32* other_len, size_t nrec, int table_bits, size_t block_reads, u32 seg_len,
+                             u8* tok, u8* ev, u8* m, uint16_t* dist, u64* ptr, int* gen_on) {
+    const gmtrace tr = { tok, ev, m, dist, ptr };
+    u8* out = NULL; size_t out_len = 0;
+    const long long rc = gm_encode_x(base, goff, glen, nrec, table_bits, block_reads, 1, &out, &out_len, NULL, gen_on, seg_len, other_len, &tr);
+    free(out);
+    return rc;
 }
 
 /* ---- the way back for the quality chains and the generation tables' base chains, and MINTING (tests only) -----------------------------

@@ -121,6 +121,13 @@ long long sfqo_gm_encode_chains(const uint8_t* base, const uint64_t* goff, const
                                 size_t chain_reads, uint8_t** out, size_t* out_len, uint32_t* sizes, int* gen_on);
 long long sfqo_gm_encode_segs(const uint8_t* base, const uint64_t* goff, const uint32_t* glen, const uint32_t* other_len, size_t nrec, int table_bits, size_t block_reads,
                               uint32_t seg_len, uint8_t** out, size_t* out_len, uint32_t* sizes, int* gen_on);
+/* the walk's trace (tests only): what the walk did at every staged base while it wrote those chains -- five arrays of sum(glen) + nrec entries
+   each (stage position soff[r] + i = base i of record r, soff[r + 1] = soff[r] + glen[r] + 1), zeroed by the caller: the token k_gm_plan would
+   write, event bits (sfq_oracle.c GMT_*), m, the pointer's distance from where it was found, the pointer.  Returns the chains' number, or -1. */
+long long sfqo_gm_trace_chains(const uint8_t* base, const uint64_t* goff, const uint32_t* glen, size_t nrec, int table_bits, size_t block_reads, size_t chain_reads,
+                               uint8_t* tok, uint8_t* ev, uint8_t* m, uint16_t* dist, uint64_t* ptr, int* gen_on);
+long long sfqo_gm_trace_segs(const uint8_t* base, const uint64_t* goff, const uint32_t* glen, const uint32_t* other_len, size_t nrec, int table_bits, size_t block_reads,
+                             uint32_t seg_len, uint8_t* tok, uint8_t* ev, uint8_t* m, uint16_t* dist, uint64_t* ptr, int* gen_on);
 /* the way back on the CPU (whole-record chains of a call that took the model): the bases' codes 0..3, codes[sum glen]; 0 or -1 */
 int sfqo_gm_decode_chains(const uint8_t* streams, const uint32_t* sizes, const uint32_t* glen, size_t nrec, int table_bits, size_t block_reads, size_t chain_reads, uint8_t* codes);
 /* the way back on the CPU for the quality chains (adm = NULL) and for base chains under the generation tables; with adm (64 flags: the
