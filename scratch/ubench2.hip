@@ -66,6 +66,13 @@ template <int OP> __global__ __launch_bounds__(64) void k(u32* out, Stamp* st, u
         if (OP == 25) { ASM8("v_lshlrev_b32 %0, 1, %0") }
         if (OP == 26) { ASM8("v_add_co_u32 %0, vcc, %0, %1\n\tv_addc_co_u32 %0, vcc, %0, %1, vcc") }
         if (OP == 27) { ASM8("v_ffbh_u32 %0, %0") }
+        if (OP == 28) { ASM8("v_dot4_u32_u8 %0, %0, %1, %0") }
+        if (OP == 29) { ASM8("v_bitop3_b32 %0, %0, %1, %1 bitop3:0x96") }
+        if (OP == 30) { ASM8("v_xad_u32 %0, %0, %1, %1") }
+        if (OP == 31) { ASM8("v_and_or_b32 %0, %0, %1, %1") }
+        if (OP == 32) { ASM8("v_lshl_or_b32 %0, %0, 1, %1") }
+        if (OP == 33) { ASM8("v_lshrrev_b32 %0, 7, %0") }
+        if (OP == 34) { ASM8("v_alignbit_b32 %0, %0, %1, 8") }
     }
     const u64 c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
     u32 s = (u32)w + (u32)(w >> 32); for (int i = 0; i < NCH; i++) s += a[i] + sa[i];
@@ -90,12 +97,17 @@ template <typename F> static void run(const char* name, F launch, int wps, u32* 
     printf("%-34s waves/SIMD %d  wall %8.3f ms  clock %5.0f MHz  cycles/inst: one wave's view %6.2f  per SIMD (wall) %5.2f\n",
            name, wps, ms, mhz, cyc[grid / 2] / inst, per_simd_wall);
 }
-int main() {
+int main(int argc, char** argv) {
+    const bool frame_only = argc > 1 && argv[1][0] == 'f';          // "f": the instructions of k_frame's mask gather alone
     u32* d; Stamp* dst;
     (void)hipMalloc(&d, 256 * 4 * 8 * 64 * 4); (void)hipMalloc(&dst, sizeof(Stamp) * 256 * 4 * 8);
     int clk = 0; (void)hipDeviceGetAttribute(&clk, hipDeviceAttributeClockRate, 0);
     printf("hipDeviceAttributeClockRate %d kHz; REP %d x %d instructions per wave\n", clk, REP, NCH);
 #define V(OP, NAME, NI) for (int w : {1, 2, 4, 8}) run(NAME, [](int g, u32* p, Stamp* s) { hipLaunchKernelGGL(k<OP>, dim3(g), dim3(64), 0, 0, p, s, 12345u); }, w, d, dst, NI)
+    // what k_frame's byte tests and mask gather are made of (frame_masks.h), beside the multiply and shifts they replace
+    V(28, "v_dot4_u32_u8", 1); V(29, "v_bitop3_b32", 1); V(30, "v_xad_u32", 1); V(31, "v_and_or_b32", 1); V(32, "v_lshl_or_b32", 1);
+    V(33, "v_lshrrev_b32", 1); V(34, "v_alignbit_b32", 1);
+    if (frame_only) { V(1, "v_mul_lo_u32", 1); V(0, "v_add_u32", 1); V(4, "v_and_b32", 1); return 0; }
     V(0, "v_add_u32", 1); V(1, "v_mul_lo_u32", 1); V(2, "v_mul_hi_u32", 1); V(3, "v_mul_u32_u24", 1); V(4, "v_and_b32", 1);
     V(5, "v_cndmask_b32", 1); V(25, "v_lshlrev_b32", 1); V(27, "v_ffbh_u32", 1); V(26, "v_add_co + v_addc_co (64-bit add)", 2);
     V(23, "v_mad_u64_u32 (dependent)", 1); V(24, "v_lshlrev_b64 (dependent)", 1);

@@ -1,4 +1,4 @@
-// dev_wave.h -- wave-level building blocks shared by the wave-per-block kernels (models_w.hip, models_k.hip).
+// dev_wave.h -- wave-level building blocks shared by the wave-per-block kernels (models_w.hip, models_k.hip) and the framing (frame.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dev_common.h"
@@ -6,6 +6,7 @@
 
 // ---- wave primitives (gfx950 = wave64, GFX9 DPP controls) --------------------------------------------
 #define DPP_ROW_SHR(n)  (0x110 + (n))
+#define DPP_WAVE_SHL1   0x130
 #define DPP_WAVE_SHR1   0x138
 #define DPP_ROW_BCAST15 0x142
 #define DPP_ROW_BCAST31 0x143
@@ -30,6 +31,11 @@ __device__ __forceinline__ u32 wave_incl_scan(u32 x) {
 // value of the previous lane; lane 0 receives `first`
 __device__ __forceinline__ u32 wave_shr1(u32 x, u32 first) {
     return (u32)__builtin_amdgcn_update_dpp((int)first, (int)x, DPP_WAVE_SHR1, 0xf, 0xf, false);
+}
+
+// value of the next lane; lane 63 receives `last`
+__device__ __forceinline__ u32 wave_shl1(u32 x, u32 last) {
+    return (u32)__builtin_amdgcn_update_dpp((int)last, (int)x, DPP_WAVE_SHL1, 0xf, 0xf, false);
 }
 
 // Persistent launch: a workgroup (= one wave = one table slot) takes blocks off a shared ticket counter until

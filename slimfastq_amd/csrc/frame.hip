@@ -6,6 +6,8 @@
 // then the per-record line limits (usrs.hpp:34-36) from the index alone and one descriptor per record block (the
 // first-record analysis of UsrSave::determine_record, usrs.cpp:186-267).  All of it is streaming, HBM-bound work.
 #include "kernels.h"
+#include "dev_wave.h"
+#include "frame_masks.h"
 
 #define HIP_KCHECK() do { } while (0)
 
@@ -38,27 +40,23 @@ __device__ __forceinline__ u32 block_excl_scan_256(u32 v, u32* lds /* >= 8 u32 *
 //   * a thread owns 64 CONTIGUOUS bytes (four 16-byte loads): one newline count, one block scan per 16 KiB tile;
 //   * a tile's place in the file comes from a decoupled look-back over the tiles before it (tstat: flag | value in one 64-bit
 //     word, so no fence is needed) instead of a counting pass and a scan kernel;
-//   * newlines, '!' candidates and odd-base candidates are 64-bit masks per thread (a SWAR test per dword, four flag bits gathered
-//     with one multiply), so offsets and marks are a few bit operations per LINE END in the window, not per byte;
+//   * newlines, '!' candidates and odd-base candidates are 64-bit masks per thread (a SWAR test per dword, the flag bits gathered
+//     by dot products: frame_masks.h), so offsets and marks are a few bit operations per LINE END in the window, not per byte;
 //   * the '@' / '+' checks of UsrSave::get_record (usrs.cpp:311, 346) ride on the line ends: the byte behind a newline is in cache.
 // The line index must be sized before the number of lines is known: the caller guesses (cap entries), the kernel never writes
 // past it and reports the count; a text of shorter lines than guessed is framed again with the exact size.
 // =========================================================================================================
 struct FrameOut { u64 nlines; u32 guard_tripped; u32 ticket; };      // (zeroed by the caller: ticket = the tile number a starting workgroup takes)
-__device__ __forceinline__ u32 flags4(u32 m) { return (m * 0x00204081u) >> 28; }      // the 0x80 flags of four bytes as four bits
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 #define TS_AGG  (1ull << 62)
 #define TS_PFX  (2ull << 62)
 #define TS_VAL  ((1ull << 62) - 1)
 // A workgroup takes a TILE of FRAME_TILE bytes in FRAME_WIN sub-tiles of 16 KiB.  Round one LOADS the text -- coalesced, 16 bytes a
-// lane, a wave's 64 lanes one KiB -- and keeps of every 64-byte window five 64-bit masks in LDS: newlines, '@', '+', '!' candidates,
-// odd-base candidates (40 bytes per 64 of text: 40 KiB a tile); its newline count is what the tiles behind it wait for.  Round two --
-// the tile's place in the file known from the look-back -- runs FROM THE MASKS: a thread takes a window, writes offsets and marks per
-// line end, and checks the '@' / '+' behind a line end in the masks too.  The text is read ONCE (round 5).
+// lane, a wave's 64 lanes one KiB -- and keeps of every 64-byte window four 64-bit masks in LDS: newlines, '@' and '+' folded into
+// one (frame_masks.h: only a byte behind a line end is asked for either), '!' candidates, odd-base candidates (32 bytes per 64 of
+// text: 32 KiB a tile, FOUR workgroups a CU -- the kernel's time follows the workgroups a CU holds); its
+// newline count is what the tiles behind it wait for.  Round two -- the tile's place in the file known from the look-back -- runs
+// FROM THE MASKS: a thread takes a window, writes offsets and marks per line end, and checks the '@' / '+' behind a line end in the
+// masks too.  The text is read ONCE (round 5).
 // (Round 4 read it twice -- the second time "out of L2", which the counters did not bear out: TCC_MISS 6.1e7 of 7.1e7 requests, 7.4 GB
 //  fetched per 3.7 GB of text after the guide's gfx950 correction: 256 workgroups x 128 KiB in flight are four times the L2s.  Measured
 //  on the way, per 3.7 GB: a thread loading its own 64 contiguous bytes straight from memory 1.9-2.0 ms; one round with every window's
@@ -71,19 +69,14 @@ __device__ __forceinline__ u64 wave_sum_u64(u64 v) {
 #define FRAME_SUB 16384u
 #define FRAME_TILE (FRAME_SUB * FRAME_WIN)
 #define FRAME_NW (FRAME_TILE / 64u)      /* windows of a tile */
-__device__ __forceinline__ u32 eq_flags(u32 x, u32 c4) {    // 0x80 where the byte equals the one c4 repeats four times
-    const u32 y = x ^ c4;
-    return ~(((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y | 0x7f7f7f7fu);
-}
-__device__ __forceinline__ u32 nl_flags(u32 x) { return eq_flags(x, 0x0a0a0a0au); }
-__device__ __forceinline__ u32 mask16(u32 fx, u32 fy, u32 fz, u32 fw) { return flags4(fx) | (flags4(fy) << 4) | (flags4(fz) << 8) | (flags4(fw) << 12); }
 template <bool MARKS>
 __global__ __launch_bounds__(256) void k_frame(const u8* __restrict__ fq, u64 n, u64* __restrict__ tstat, u64* __restrict__ line_off, u64 cap,
                                                u32* __restrict__ status, u8* __restrict__ exc_flag, u64 ecap, FrameOut* __restrict__ fo) {
-    constexpr u32 NM = MARKS ? 5u : 3u;
-    __shared__ u64 mk[NM][FRAME_NW];                         // [newline, '@', '+', '!' candidate, odd-base candidate][window]
+    constexpr u32 NM = MARKS ? 4u : 2u;
+    __shared__ u64 mk[NM][FRAME_NW];                         // [newline, '@' and '+' folded, '!' candidate, odd-base candidate][window]; all but the last COMPLEMENTED (frame_masks.h)
     __shared__ u32 wtot[4];
     __shared__ u32 s_last[4];
+    __shared__ u32 s_npl0[4];                                // per wave of round 1, bit 4 wi + j: the first byte of its KiB j of sub-tile wi is no '+'
     __shared__ u64 s_base;
     __shared__ u32 s_tile;
     const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -106,7 +99,9 @@ __global__ __launch_bounds__(256) void k_frame(const u8* __restrict__ fq, u64 n,
         }
     };
     // ---- round 1: the text, once -- the windows' masks into LDS, the tile's newlines counted -------------------------------------------
-    u32 cnt = 0;
+    u16* const m16 = reinterpret_cast<u16*>(&mk[0][0]);      // a tile's mask, sixteen bits a piece
+    u32 npl0 = 0;                                            // bit 4 wi + j: the thread's piece j of sub-tile wi does not start with a '+'
+    u32 ncnt = 0;                                            // the thread's bytes that are NO newline
     {
         uint4 nx[4];
         fetch(tb, nx);
@@ -118,30 +113,25 @@ __global__ __launch_bounds__(256) void k_frame(const u8* __restrict__ fq, u64 n,
             if (wi + 1 < FRAME_WIN) fetch(tb + (u64)FRAME_SUB * (wi + 1), nx);
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                // piece j of thread tid lies in window 64 j + tid / 4 of the sub-tile, at bytes 16 (tid % 4)
-                const u32 W = wi * 256u + 64u * j + (tid >> 2), q = tid & 3u;
-                const uint4 x = v[j];
-                const u32 nl = mask16(nl_flags(x.x), nl_flags(x.y), nl_flags(x.z), nl_flags(x.w));
-                cnt += (u32)__popc(nl);
-                reinterpret_cast<u16*>(&mk[0][W])[q] = (u16)nl;
-                reinterpret_cast<u16*>(&mk[1][W])[q] = (u16)mask16(eq_flags(x.x, 0x40404040u), eq_flags(x.y, 0x40404040u), eq_flags(x.z, 0x40404040u), eq_flags(x.w, 0x40404040u));
-                reinterpret_cast<u16*>(&mk[2][W])[q] = (u16)mask16(eq_flags(x.x, 0x2b2b2b2bu), eq_flags(x.y, 0x2b2b2b2bu), eq_flags(x.z, 0x2b2b2b2bu), eq_flags(x.w, 0x2b2b2b2bu));
+                // piece j of thread tid lies in window 64 j + tid / 4 of the sub-tile, at bytes 16 (tid % 4): sixteen bits P of a mask
+                const u32 P = wi * 1024u + 256u * j + tid;
+                const PieceMasks m = piece_masks<MARKS>(v[j].x, v[j].y, v[j].z, v[j].w);
+                ncnt += (u32)__popc(m.nnl);
+                m16[0u * FRAME_NW * 4u + P] = (u16)m.nnl;
+                // the byte behind the piece is the next lane's first; behind the wave's last piece another wave's, which leaves its
+                // "no '+'" in s_npl0 (npl0) for round 2 (the fold's bit 15 of that piece is not read: see there)
+                m16[1u * FRAME_NW * 4u + P] = (u16)fold_prefix16(m.nnl, m.nat, m.npl, wave_shl1(m.npl, 0u));
+                npl0 |= (m.npl & 1u) << (4u * wi + j);
                 if constexpr (MARKS) {
-                    // '!' candidates: a byte b with (b & 0x5e) == 0 -- in a quality line (0x21 .. 0x7e) that is '!' alone   (no carry between bytes: 0x5e + 0x7f < 0x100)
-                    // odd-base candidates: bit 3 (N, '.') or bits 5 and 6 (lowercase) -- every N-like or lowercase base, and no A C G T 0 1 2 3
-#define FR_BANG(w) (~(((w) & 0x5e5e5e5eu) + 0x7f7f7f7fu) & 0x80808080u)
-#define FR_ODD(w) ((((w) << 4) | (((w) << 1) & ((w) << 2))) & 0x80808080u)
-                    reinterpret_cast<u16*>(&mk[3][W])[q] = (u16)mask16(FR_BANG(x.x), FR_BANG(x.y), FR_BANG(x.z), FR_BANG(x.w));
-                    reinterpret_cast<u16*>(&mk[4][W])[q] = (u16)mask16(FR_ODD(x.x), FR_ODD(x.y), FR_ODD(x.z), FR_ODD(x.w));
-#undef FR_BANG
-#undef FR_ODD
+                    m16[2u * FRAME_NW * 4u + P] = (u16)m.nbang;
+                    m16[3u * FRAME_NW * 4u + P] = (u16)m.odd;
                 }
             }
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) cnt += (u32)__shfl_xor((int)cnt, d, 64);
-    if (lane == 0) wtot[wave] = cnt;
+    ncnt = wave_incl_scan(ncnt);                             // (the wave's sum in its last lane: DPP, no LDS crossbar)
+    if (lane == 63) wtot[wave] = 64u * (FRAME_TILE / 256u) - ncnt;
+    if (lane == 0) s_npl0[wave] = npl0;
     __syncthreads();
     const u32 total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
     // ---- the tile among the file's (decoupled look-back) ------------------------------------------------------------------------------
@@ -160,13 +150,15 @@ __global__ __launch_bounds__(256) void k_frame(const u8* __restrict__ fq, u64 n,
                     __builtin_amdgcn_s_sleep(1);
                     continue;
                 }
+                // the tiles' own counts (an aggregate is at most FRAME_TILE: 64 of them fit 32 bits) add up by DPP; the one prefix
+                // taken, of the nearest tile that knows its own, is 64 bits wide and comes by readlane
                 const u64 pm = __ballot((word >> 62) == 2);
+                const u32 first = pm ? (u32)__ffsll((long long)pm) - 1u : 64u;
+                excl += rl(wave_incl_scan(lane < first ? (u32)word : 0u), 63);
                 if (pm) {
-                    const u32 first = (u32)__ffsll((long long)pm) - 1u;             // the nearest tile that knows its prefix
-                    excl += wave_sum_u64(lane <= first ? (word & TS_VAL) : 0ull);
+                    excl += ((u64)rl((u32)((word & TS_VAL) >> 32), first) << 32) | rl((u32)word, first);
                     break;
                 }
-                excl += wave_sum_u64(word & TS_VAL);
                 j -= 64;
             }
             if (tripped && lane == 0) fo->guard_tripped = 1;
@@ -190,17 +182,15 @@ __global__ __launch_bounds__(256) void k_frame(const u8* __restrict__ fq, u64 n,
         if (sb >= n) break;                                  // (the same for every thread)
         const u32 W = wi * 256u + tid;
         const u64 w0 = sb + 64u * tid;
-        const u64 nlm = mk[0][W], atm = mk[1][W], plm = mk[2][W];
+        const u64 nlm = ~mk[0][W], nfold = mk[1][W];         // (frame_masks.h: prefix_no_at, prefix_no_plus)
         u64 bang = 0, odd = 0;
         if constexpr (MARKS) {
             const u64 live = w0 >= n ? 0ull : (n - w0) >= 64 ? ~0ull : ((1ull << (n - w0)) - 1);      // (bytes past the end read as 0: a '!' candidate)
-            bang = mk[3][W] & live; odd = mk[4][W] & live;
+            bang = ~mk[2][W] & live; odd = mk[3][W] & live;
         }
         // this window's newlines among its sub-tile's
         const u32 c = (u32)__popcll(nlm);
-        u32 incl = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const u32 o = (u32)__shfl_up((int)incl, d, 64); if (lane >= (u32)d) incl += o; }
+        const u32 incl = wave_incl_scan(c);
         if (lane == 63) { wtot[wave] = incl; s_last[wave] = (u32)(nlm >> 63); }
         __syncthreads();
         u32 bw = 0, tw = 0;
@@ -210,10 +200,14 @@ __global__ __launch_bounds__(256) void k_frame(const u8* __restrict__ fq, u64 n,
         run += tw;
         // usrs.cpp:311, 346: a record's first line starts with '@', its third with '+'.  A line that starts WITH the window (the
         // byte before it, the window before's last, is a newline -- handed over from lane to lane, wave to wave, sub-tile to sub-tile):
-        u32 prev_nl = (u32)__shfl_up((int)(u32)(nlm >> 63), 1, 64);
+        // ... and whether the window's first byte is no '+': the fold keeps that in the bit of the line end before it, the window
+        // before's last; behind a wave's KiB of round 1 -- every sixteenth window -- it is in s_npl0
+        u32 no_plus0 = wave_shr1((u32)(nfold >> 63), 0u);
+        if ((tid & 15u) == 0u) no_plus0 = (s_npl0[(tid >> 4) & 3u] >> (4u * wi + (tid >> 6))) & 1u;      // (window tid = 64 j + 16 wave)
+        u32 prev_nl = wave_shr1((u32)(nlm >> 63), 0u);
         if (lane == 0) prev_nl = wave ? s_last[wave - 1] : carry_nl;
         if (tid == 0) carry_nl = s_last[3];
-        if (prev_nl && w0 < n && ((u32)k & 1u) == 0u && !((((u32)k & 2u) ? plm : atm) & 1ull)) atomicMax(status, (u32)(-SFQ_E_FORMAT));
+        if (prev_nl && w0 < n && ((u32)k & 1u) == 0u && (((u32)k & 2u) ? no_plus0 : prefix_no_at(nlm, nfold, 0u))) atomicMax(status, (u32)(-SFQ_E_FORMAT));
         if (w0 < n) {
             u64 m = nlm;
             u64 below = 0;                                   // the window's bytes up to the line end looked at last
@@ -233,7 +227,7 @@ __global__ __launch_bounds__(256) void k_frame(const u8* __restrict__ fq, u64 n,
                 // ... and a line that starts inside it: the byte behind the line end, in the '@' / '+' masks
                 if (i < 63u && start < n) {
                     const u32 type = (u32)k & 3u;
-                    if ((type & 1u) == 0u && !(((type ? plm : atm) >> (i + 1u)) & 1ull)) atomicMax(status, (u32)(-SFQ_E_FORMAT));
+                    if ((type & 1u) == 0u && (type ? prefix_no_plus(nfold, i) : prefix_no_at(nlm, nfold, i + 1u))) atomicMax(status, (u32)(-SFQ_E_FORMAT));
                 }
             }
             if constexpr (MARKS) {                           // what lies behind the window's last line end (or the whole window)
