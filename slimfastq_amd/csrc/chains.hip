@@ -17,6 +17,8 @@
 #include "kernels.h"
 #include "dev_chain.h"
 #include "dev_walk.h"
+#include "dev_wave.h"
+#include "gen_pack_place.h"
 // a dword of text at any address: vector global loads need no alignment on gfx9, SCALAR loads drop the address's low bits -- and a plain u32 pointer lets the
 // compiler take one where the address is wave-uniform (the record that lane 0 of a wave stages alone)
 typedef u32 __attribute__((aligned(1))) u32_any;
@@ -1050,23 +1052,12 @@ __global__ __launch_bounds__(THREADS) void k_gen_encode_c(ChainArgs a, u32 c0, u
 }
 // ---- bases without a model, packed by a wavefront per chain (block format 10, "chn.idx" flag CHN_FLAT_RAW) ----------------------------
 // The chain's bases two bits each, four a byte (the first in the low bits), across its records' ends; the last byte padded with
-// zeros; N-like, illegal and lowercase characters code as gen_code_of(c) & 3.  Lane i of the wave owns output dword t = i + 64 j:
-// bases 16 t .. 16 t + 15 of the concatenation.  It finds the record of its first base in the prefix of the line lengths, takes its
-// sixteen bytes from that record and the ones behind it (one, or two where a line ends inside the dword), and the wave stores 256
-// contiguous bytes.  Records come 64 at a time; a dword that straddles two such chunks is carried over in a register.
-// A byte position j of a dword's sixteen as a byte mask over a uint4: the bytes [0, n), n in [0, 16]
-__device__ __forceinline__ uint4 gp_below(u32 n) {
-    const u64 lo = n >= 8u ? ~0ull : (1ull << (8u * n)) - 1ull;
-    const u64 hi = n >= 16u ? ~0ull : n <= 8u ? 0ull : (1ull << (8u * (n - 8u))) - 1ull;
-    return make_uint4((u32)lo, (u32)(lo >> 32), (u32)hi, (u32)(hi >> 32));
-}
-// 16 bytes at any offset, those outside [0, nbytes) read as zero
-__device__ __forceinline__ uint4 gp_load16(const u8* buf, u64 nbytes, long long at) {
-    if (at >= 0 && (u64)at + 16u <= nbytes) return load16(buf, nbytes, (u64)at);
-    u32 w[4] = {0, 0, 0, 0};
-    for (u32 i = 0; i < 16; i++) { const long long p = at + (long long)i; if (p >= 0 && (u64)p < nbytes) w[i >> 2] |= (u32)buf[p] << ((i & 3) * 8); }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
+// zeros; N-like, illegal and lowercase characters code as gen_code_of(c) & 3.  A group of lanes owns a record, a lane sixteen
+// bases of its line (gen_pack_place.h): it knows its record by construction, loads its sixteen bytes, codes them and ORs the
+// thirty-two bits into the wavefront's ring in LDS at their place in the chain; the wavefront stores the ring's complete rows, 256
+// contiguous bytes each.  Records come 64 at a time: their bounds a lane each, one scan of the lengths, and a table in LDS from
+// which a lane reads its record in one go.  A ring and a table are their wavefront's own: no workgroup barrier, the order
+// between a wavefront's LDS writes and its reads is stated to the compiler by wavefront-scope fences (the LDS keeps it anyway).
 // four bytes -> their codes (a byte each), the bytes of `valid` that are not an upper-case ACGT in `odd` (bit 7 of the byte), illegal ones in `ill`
 __device__ __forceinline__ u32 gp_codes(u32 w, u32 valid, u32& odd, u32& ill) {
     const u32 s1 = w >> 1;
@@ -1089,13 +1080,16 @@ __device__ __forceinline__ u32 gp_codes(u32 w, u32 valid, u32& odd, u32& ill) {
 }
 // codes of bases 4 d .. 4 d + 3 (a byte each) -> bits 0-3 and 16-19
 __device__ __forceinline__ u32 gp_fold(u32 cd) { return cd | (cd >> 6); }
-// bit 7 of each byte of four dwords -> a bit per byte of the sixteen
-__device__ __forceinline__ u32 gp_nib(u32 t) { return ((t >> 7) * 0x01020408u) >> 24; }
-__device__ __forceinline__ u32 gp_bits16(u32 o0, u32 o1, u32 o2, u32 o3) { return gp_nib(o0) | gp_nib(o1) << 4 | gp_nib(o2) << 8 | gp_nib(o3) << 12; }
+__device__ __forceinline__ void gp_wave_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
 __global__ __launch_bounds__(256) void k_gen_pack_raw(ChainArgs a, u32 c0, u32 c1) {
+    __shared__ uint4 tabs[4][64];                                                         // a chunk's records: {b0 low, b0 high, first base in the chain, bases}
+    __shared__ u32 rings[4][GP_RING];
     const u32 lane = threadIdx.x & 63u;
-    const u32 c = c0 + blockIdx.x * 4u + (threadIdx.x >> 6);
+    const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));         // (uniform: the chain's geometry stays in scalar registers)
+    const u32 c = c0 + blockIdx.x * 4u + wv;
     if (c >= c1) return;                                                                  // (the whole wave)
+    uint4* tab = tabs[wv]; u32* ring = rings[wv];
+    ring[lane] = 0; ring[lane + 64u] = 0;
     ChainPos cp = chain_pos(a, c); chain_seg_encode(a, cp);
     const u32 solid = a.m.blocks[cp.b].solid;
     u32 cap = 0;
@@ -1103,7 +1097,7 @@ __global__ __launch_bounds__(256) void k_gen_pack_raw(ChainArgs a, u32 c0, u32 c
     const u8* buf = a.st_off ? a.st_buf : a.m.fq;
     const u64 nbytes = a.st_off ? a.st_bytes : a.nbytes;
     u32 done = 0;          // bases of the chunks before this one
-    u32 carry = 0;         // the codes of the dword the previous chunk ended inside
+    u32 row = 0;           // the first dword of the chain not stored yet
     u32 illegal = 0;
     for (u32 k0 = 0; k0 < cp.nrec; k0 += 64u) {
         // the chunk's base lines (LineWalk::bounds)
@@ -1122,73 +1116,59 @@ __global__ __launch_bounds__(256) void k_gen_pack_raw(ChainArgs a, u32 c0, u32 c
             if (b1 < b0) b1 = b0;
         }
         const u32 len = (u32)(b1 - b0);
-        u32 inc = len;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const u32 o = (u32)__shfl_up((int)inc, d, 64); if (lane >= (u32)d) inc += o; }
-        const u32 st = inc - len;                                                         // the record's first base in the chunk
-        const u32 tot = (u32)__shfl((int)inc, 63, 64);
-        const u32 end = done + tot;
-        const bool last_chunk = k0 + 64u >= cp.nrec;
-        const u32 t0 = done >> 4, t1 = (end + 15u) >> 4;                                  // the dwords the chunk touches
-        for (u32 tb = t0; tb < t1; tb += 64u) {
-            const u32 t = tb + lane;
-            const u32 d0 = 16u * t;
-            const u32 lo = d0 > done ? d0 : done, hi = d0 + 16u < end ? d0 + 16u : end;   // this lane's bases [lo, hi) (lo >= hi: none)
-            // the record of base lo: the last one that starts at or before it (a record of no bases starts where the next one does)
-            u32 kr = 0;
-#pragma unroll
-            for (u32 s = 32; s > 0; s >>= 1) { const u32 sk = (u32)__shfl((int)st, (int)(kr + s), 64); if (sk + done <= lo) kr += s; }
-            uint4 w = make_uint4(0, 0, 0, 0);
-            u32 pos = lo;
-            while (__any(pos < hi)) {                                                     // one record a round: one round, two where a line ends inside the dword
-                const u32 ks = kr & 63u;
-                const u32 sk = (u32)__shfl((int)st, (int)ks, 64) + done, lk = (u32)__shfl((int)len, (int)ks, 64);
-                const u64 bk = (u64)__shfl((unsigned long long)b0, (int)ks, 64);
-                const u32 e = sk + lk < hi ? sk + lk : hi;
-                if (pos < hi && e > pos) {
-                    const u32 j = pos - d0;                                               // the piece is bytes [j, j + e - pos) of the dword
-                    const uint4 v = gp_load16(buf, nbytes, (long long)(bk + (pos - sk)) - (long long)j);
-                    const uint4 m0 = gp_below(j), m1 = gp_below(j + (e - pos));
-                    w.x = (w.x & ~(m1.x & ~m0.x)) | (v.x & m1.x & ~m0.x);
-                    w.y = (w.y & ~(m1.y & ~m0.y)) | (v.y & m1.y & ~m0.y);
-                    w.z = (w.z & ~(m1.z & ~m0.z)) | (v.z & m1.z & ~m0.z);
-                    w.w = (w.w & ~(m1.w & ~m0.w)) | (v.w & m1.w & ~m0.w);
-                    pos = e;
+        const u32 inc = wave_incl_scan(len);
+        const u32 n = cp.nrec - k0 < 64u ? cp.nrec - k0 : 64u;
+        const u32 lanes = gp_group_lanes(rl(wave_incl_scan_max(len), 63u));                // of a group: a record's
+        const u32 per = rfl(gp_div_lanes(64u, lanes));                                    // records a step
+        const u32 sub = gp_div_lanes(lane, lanes);
+        const u32 piece = gp_lane_piece(lane, sub, lanes, per);
+        gp_wave_fence();                                                                  // (the chunk before has read its table)
+        tab[lane] = make_uint4((u32)b0, (u32)(b0 >> 32), done + inc - len, len);
+        gp_wave_fence();
+        for (u32 s0 = 0; s0 < n; s0 += per) {
+            const u32 rec = s0 + sub;
+            uint4 e = tab[rec & 63u];
+            if (rec >= n) e.w = 0;                                                        // (a group past the chunk's last record)
+            const u32 last = gp_step_last(s0, n, per);
+            const u32 rec_end = done + rl(inc, last), last_len = rl(len, last);
+            u32 q0 = 0;
+            do {                                                                          // one turn; a line of more than 1024 bases: one per 1024 bases
+                const u32 off = q0 + piece;
+                if (off < e.w) {
+                    const uint4 w = load16(buf, nbytes, ((u64)e.y << 32 | e.x) + off);
+                    const uint4 vm = gp_valid4(e.w - off);
+                    u32 o0, o1, o2, o3, i0, i1, i2, i3;
+                    const u32 f0 = gp_fold(gp_codes(w.x, vm.x, o0, i0)), f1 = gp_fold(gp_codes(w.y, vm.y, o1, i1));
+                    const u32 f2 = gp_fold(gp_codes(w.z, vm.z, o2, i2)), f3 = gp_fold(gp_codes(w.w, vm.w, o3, i3));
+                    illegal |= i0 | i1 | i2 | i3;
+                    // bytes (c0 | c1 << 2, c2 | c3 << 2) of two dwords side by side, then the high nibbles folded down: a byte per four bases
+                    u32 p01 = __builtin_amdgcn_perm(f1, f0, 0x06020400u), p23 = __builtin_amdgcn_perm(f3, f2, 0x06020400u);
+                    p01 |= p01 >> 12; p23 |= p23 >> 12;
+                    const u32 code = __builtin_amdgcn_perm(p23, p01, 0x05040100u);
+                    // an N, a lowercase base or an illegal character marks its record for the pass over the exceptions (k_gen_exc_w)
+                    if (a.exc_flag && (o0 | o1 | o2 | o3)) a.exc_flag[cp.r0 + k0 + rec] = 1;
+                    const GpPlace g = gp_place(e.z + off, code);
+                    __hip_atomic_fetch_or(&ring[gp_ring_slot(g.d)], g.lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    __hip_atomic_fetch_or(&ring[gp_ring_slot(g.d + 1u)], g.hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);      // (nothing, often: cheaper than asking)
                 }
-                kr++;
-            }
-            const bool any = lo < hi;
-            const uint4 va = gp_below(any ? hi - d0 : 0u), vb = gp_below(any ? lo - d0 : 0u);
-            const uint4 vm = make_uint4(va.x & ~vb.x, va.y & ~vb.y, va.z & ~vb.z, va.w & ~vb.w);
-            u32 o0, o1, o2, o3, i0, i1, i2, i3;
-            const u32 f0 = gp_fold(gp_codes(w.x, vm.x, o0, i0)), f1 = gp_fold(gp_codes(w.y, vm.y, o1, i1));
-            const u32 f2 = gp_fold(gp_codes(w.z, vm.z, o2, i2)), f3 = gp_fold(gp_codes(w.w, vm.w, o3, i3));
-            illegal |= i0 | i1 | i2 | i3;
-            // bytes (c0 | c1 << 2, c2 | c3 << 2) of two dwords side by side, then the high nibbles folded down: a byte per four bases
-            u32 p01 = __builtin_amdgcn_perm(f1, f0, 0x06020400u), p23 = __builtin_amdgcn_perm(f3, f2, 0x06020400u);
-            p01 |= p01 >> 12; p23 |= p23 >> 12;
-            u32 code = __builtin_amdgcn_perm(p23, p01, 0x05040100u);
-            if (t == t0) code |= carry;                                                   // (the bases of the chunk before, below `done`)
-            // an N, a lowercase base or an illegal character marks its record for the pass over the exceptions (k_gen_exc_w)
-            u32 odd = gp_bits16(o0, o1, o2, o3);
-            if (a.exc_flag) {
-                while (__any(odd != 0u)) {
-                    const u32 jb = odd ? (u32)__builtin_ctz(odd) : 0u;
-                    u32 ko = 0;
-#pragma unroll
-                    for (u32 s = 32; s > 0; s >>= 1) { const u32 sk = (u32)__shfl((int)st, (int)(ko + s), 64); if (sk + done <= d0 + jb) ko += s; }
-                    const u32 ke = (u32)__shfl((int)inc, (int)ko, 64) + done;              // the record's end
-                    if (odd) {
-                        a.exc_flag[cp.r0 + k0 + ko] = 1;
-                        odd &= ke - d0 >= 16u ? 0u : ~((1u << (ke - d0)) - 1u);
-                    }
+                const u32 next = gp_turn_end(rec_end, last_len, q0);
+                gp_wave_fence();
+                if (gp_row_ready(row, next)) {                                            // every base of the row is in: store it, zero it for the row 128 dwords on
+                    const u32 t = row + lane, slot = gp_ring_slot(t);
+                    const u32 v = ring[slot];
+                    ring[slot] = 0;
+                    if (4u * t < cap) out[t] = v;
+                    row += GP_ROW;
                 }
-            }
-            const bool held = t == t1 - 1u && (end & 15u) && !last_chunk;               // finished by the next chunk
-            if (t < t1 && !held && 4u * t < cap) out[t] = code;
-            if (!last_chunk) carry = (end & 15u) ? (u32)__shfl((int)code, (int)((t1 - 1u - tb) & 63u), 64) : 0u;
+                gp_wave_fence();
+                q0 += 1024u;
+            } while (q0 < last_len);
         }
-        done = end;
+        done += rl(inc, 63u);
+    }
+    {   // the dwords behind the last full row, the last one padded with zeros
+        const u32 t = row + lane;
+        if (lane < gp_tail_dwords(row, done) && 4u * t < cap) out[t] = ring[gp_ring_slot(t)];
     }
     if (lane == 0) {
         const u32 n = (done + 3u) >> 2;
