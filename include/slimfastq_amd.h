@@ -400,6 +400,54 @@ int sfq_ctx_set_pair_split(sfq_ctx* ctx, int on);
 /* 1: the last decode call split its text, *first_bytes = where the second mates begin; 0: it did not (both set to 0) */
 int sfq_get_pair_split(const sfq_ctx* ctx, uint64_t* first_bytes, uint64_t* n_pairs);
 
+/* Records [first_record, first_record + n_records) of d_text, split: d_out[0, *split) = the window's records 0, 2, 4, ... (counted from
+ * first_record), d_out[*split, *out_bytes) = its records 1, 3, 5, ...  *out_bytes = the bytes of those records (on SFQ_E_OVERFLOW: the
+ * size needed).  first_record may be odd or even; n_records must be even and > 0 (SFQ_E_FORMAT otherwise); a range that ends behind the
+ * text's last record: SFQ_E_ARG.  The text's own record count may be odd.  Everything else as sfq_split_pairs: one copy cuts and
+ * splits, a refused call writes nothing, and with first_record = 0 and all records the output is sfq_split_pairs' byte for byte. */
+int sfq_split_pairs_range(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, uint64_t first_record, uint64_t n_records,
+                          uint8_t* d_out, uint64_t out_cap, uint64_t* split, uint64_t* out_bytes);
+
+/* Mates by name.  A record's NAME is the bytes of its first line behind the line's first byte (the '@'), up to but not including the
+ * first ' ', '\t' or the line end; if what remains is two bytes or longer and ends in "/1" or "/2", those two bytes are dropped.  Two
+ * records are mates by name if their names have the same length and the same bytes: "@r/1" and "@r/2", "@r 1:N:0:ACGT" and
+ * "@r 2:N:0:ACGT", "@r/1" and "@r", two empty names are; "@r1" and "@r10", "@ra" and "@rb" are not. */
+typedef struct sfq_mate_report {
+    uint64_t n_pairs, n_mismatch;
+    uint64_t first_mismatch;               /* pair index, the smallest; valid where n_mismatch                         */
+    uint64_t first_off_a, first_off_b;     /* byte offsets of that pair's header lines in their texts                   */
+} sfq_mate_report;
+/* d_b != NULL: record i of d_a against record i of d_b (the refusals of sfq_interleave: line counts, record counts, an A without its
+ * final line end).  d_b == NULL: d_a is an interleaved text, record 2k against record 2k + 1 (the refusals of sfq_split_pairs; both
+ * offsets are d_a's).  Mismatches are REPORTED, not refused: SFQ_OK with n_mismatch > 0.  Writes nothing to either text; reads them
+ * like the other passes; synchronises once. */
+int sfq_check_mates(sfq_ctx* ctx, const uint8_t* d_a, uint64_t na, const uint8_t* d_b, uint64_t nb, sfq_mate_report* report);
+/* on != 0: sfq_encode_pairs_host compares the names before it codes (between the record starts and the copy: no second counting pass,
+ * no second synchronise) and returns SFQ_E_FORMAT where a pair differs -- sfq_last_error gives the count, the first pair's index and
+ * both names (each cut at 64 bytes) -- with nothing written to h_out.  Default off: nothing is launched, allocated or copied that is
+ * not today. */
+int sfq_ctx_set_mate_check(sfq_ctx* ctx, int on);
+/* 1: the last sfq_encode_pairs_host ran the check, *out = what it found; 0: it did not (*out zeroed) */
+int sfq_get_mate_report(const sfq_ctx* ctx, sfq_mate_report* out);
+
+/* host only: the blocks that hold records [2*first_pair, 2*(first_pair + n_pairs)) of a call's block index (by the blocks' n_records);
+ * SFQ_E_ARG where the range ends behind the last record or n_pairs == 0 */
+int sfq_pair_window_blocks(const sfq_block_info* h_blocks, uint32_t n_blocks, uint64_t first_pair, uint64_t n_pairs,
+                           uint32_t* first_block, uint32_t* n_window);
+/* Pairs [first_pair, first_pair + n_pairs) of a call written from paired files, split: h_out[0, *split) the first mates,
+ * h_out[*split, *out_bytes) the second.  Decodes the blocks sfq_pair_window_blocks names exactly as sfq_decode_block_range_host does
+ * (same arguments, same partial upload, same dependence on what lies in front), then cuts to the records and splits ON THE DEVICE
+ * (sfq_split_pairs_range); only the result crosses the link.  out_cap sizes the decoded window of blocks (SFQ_E_OVERFLOW: *out_bytes =
+ * the size needed); h_out holds out_cap bytes.  Works whatever sfq_ctx_set_pair_split says and answers sfq_get_pair_split afterwards.
+ * Installed block checksums are those of the window's blocks (of the interleaved text), checked before the cut.  A call whose record
+ * count is odd: SFQ_E_FORMAT; n_pairs == 0 or a window past the end: SFQ_E_ARG.  There is no device-pointer variant: a caller with
+ * device buffers composes sfq_decode_block_range and sfq_split_pairs_range. */
+int sfq_decode_pair_range_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_info* h_blocks, uint32_t n_blocks,
+                               const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
+                               const uint8_t* h_streams, uint64_t streams_bytes, const uint64_t stream_offset[SFQ_NSTREAMS],
+                               uint64_t first_pair, uint64_t n_pairs,
+                               uint8_t* h_out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* split, sfq_result* result);
+
 /* ---- the ".sfq" container (host only) ----------------------------------------------------------
  * Replaces FilerSave + the info page (filer.cpp:217-242, config.cpp:334-347) for hosts that assemble an archive
  * themselves: info_text is the info page ("key=value\n" lines), then n_streams named byte streams (names of at most

@@ -33,6 +33,8 @@ EXPORTS = [
     "sfq_ctx_set_stats", "sfq_get_text_stats", "sfq_text_stats_merge", "sfq_pack_text_stats", "sfq_unpack_text_stats",
     "sfq_quality_map_preset", "sfq_quality_map_check", "sfq_map_qualities", "sfq_ctx_set_quality_map", "sfq_get_quality_map_changed",
     "sfq_interleave", "sfq_split_pairs", "sfq_encode_pairs_host", "sfq_ctx_set_pair_split", "sfq_get_pair_split",
+    "sfq_split_pairs_range", "sfq_check_mates", "sfq_ctx_set_mate_check", "sfq_get_mate_report", "sfq_pair_window_blocks",
+    "sfq_decode_pair_range_host",
 ]
 
 
@@ -86,6 +88,12 @@ class TextStats(C.Structure):
         t = TextStats()
         C.memmove(C.byref(t), C.byref(self), C.sizeof(TextStats))
         return t
+
+
+class MateReport(C.Structure):
+    """sfq_mate_report: what the name pass found (pair.hip k_pair_names)."""
+    _fields_ = [("n_pairs", C.c_uint64), ("n_mismatch", C.c_uint64), ("first_mismatch", C.c_uint64),
+                ("first_off_a", C.c_uint64), ("first_off_b", C.c_uint64)]
 
 
 class SfqError(RuntimeError):
@@ -200,6 +208,13 @@ def lib():
         L.sfq_encode_pairs_host.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp]
         L.sfq_ctx_set_pair_split.argtypes = [vp, C.c_int]
         L.sfq_get_pair_split.argtypes = [vp, u64p, u64p]
+        L.sfq_split_pairs_range.argtypes = [vp, vp, u64, u64, u64, vp, u64, u64p, u64p]
+        L.sfq_check_mates.argtypes = [vp, vp, u64, vp, u64, C.POINTER(MateReport)]
+        L.sfq_ctx_set_mate_check.argtypes = [vp, C.c_int]
+        L.sfq_get_mate_report.argtypes = [vp, C.POINTER(MateReport)]
+        L.sfq_pair_window_blocks.argtypes = [C.POINTER(BlockInfo), C.c_uint32, u64, u64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.sfq_decode_pair_range_host.argtypes = [vp, C.POINTER(Params), C.POINTER(BlockInfo), C.c_uint32, u8p, u64, u8p, u64, C.POINTER(u64),
+                                                 u64, u64, u8p, u64, u64p, u64p, C.POINTER(Result)]
         _lib = L
     return _lib
 
@@ -431,6 +446,39 @@ class Context:
         self._check(lib().sfq_split_pairs(self._h, C.c_void_p(d_text), int(nbytes), C.c_void_p(d_out), int(out_cap),
                                           C.byref(split), C.byref(pairs)))
         return int(split.value), int(pairs.value)
+
+    def split_pairs_range(self, d_text, nbytes, first_record, n_records, d_out, out_cap):
+        """Records [first_record, first_record + n_records) of the FASTQ text in the device buffer at d_text into the one at d_out:
+        the window's even records, then its odd ones (sfq_split_pairs_range); returns (where the odd ones begin, bytes written).  An
+        SfqError of code E_OVERFLOW carries the size needed as .needed."""
+        split, n = C.c_uint64(), C.c_uint64()
+        rc = lib().sfq_split_pairs_range(self._h, C.c_void_p(d_text), int(nbytes), int(first_record), int(n_records),
+                                         C.c_void_p(d_out), int(out_cap), C.byref(split), C.byref(n))
+        try:
+            self._check(rc)
+        except SfqError as e:
+            e.needed = int(n.value)
+            raise
+        return int(split.value), int(n.value)
+
+    def check_mates(self, d_a, na, d_b=None, nb=0) -> MateReport:
+        """The names of record i of the device text at d_a against those of record i of the one at d_b; d_b None: d_a is an interleaved
+        text, record 2k against record 2k + 1 (sfq_check_mates).  Mismatches are reported, not raised."""
+        r = MateReport()
+        self._check(lib().sfq_check_mates(self._h, C.c_void_p(d_a), int(na), C.c_void_p(d_b) if d_b is not None else None, int(nb), C.byref(r)))
+        return r
+
+    def set_mate_check(self, on=True):
+        """On: encode_pairs_host compares the mates' names before it codes and raises an SfqError of code E_FORMAT where a pair differs."""
+        self._check(lib().sfq_ctx_set_mate_check(self._h, 1 if on else 0))
+
+    def mate_report(self):
+        """What the last encode_pairs_host's name check found (a MateReport); None where it did not run."""
+        r = MateReport()
+        rc = lib().sfq_get_mate_report(self._h, C.byref(r))
+        if rc < 0:
+            self._check(rc)
+        return r if rc == 1 else None
 
     def set_pair_split(self, on=True):
         """On: decode_host returns the first mates followed by the second mates (pair_split() says where) instead of the
@@ -665,3 +713,49 @@ class Context:
                                                   data.ctypes.data_as(C.c_void_p), len(data), soff, first_block, n_window,
                                                   out.ctypes.data_as(C.c_void_p), out_cap, C.byref(n), C.byref(res)))
         return out[:n.value].tobytes(), res
+
+    def decode_pair_range_host(self, enc: Encoded, first_pair, n_pairs, level=3, version=0, out_cap=None, kernel=0, lds_rows=0, crcs=None):
+        """Pairs [first_pair, first_pair + n_pairs) of an Encoded written from paired files (sfq_decode_pair_range_host); crcs: the
+        expected CRCs of the blocks pair_window_blocks names (default: their share of enc.crcs, where the encode computed them).
+        Returns (the first mates, the second mates, Result)."""
+        L = lib()
+        self._check(L.sfq_set_qlt_prior(self._h, enc.prior if enc.prior else None, len(enc.prior)))
+        self._check(L.sfq_set_chain_index(self._h, enc.chains if enc.chains else None, len(enc.chains)))
+        self._check(L.sfq_set_rec_prior(self._h, enc.rec_prior if enc.rec_prior else None, len(enc.rec_prior)))
+        data = enc.data if isinstance(enc.data, np.ndarray) else np.ascontiguousarray(np.frombuffer(bytes(enc.data), np.uint8))
+        if crcs is None and enc.crcs is not None:
+            w = pair_window_blocks(enc.blocks, first_pair, n_pairs)
+            crcs = enc.crcs[w[0]:w[0] + w[1]] if w is not None else None
+        if crcs:                                               # (an empty list: none are installed)
+            self.set_block_checksums(crcs)
+        p = Params(level, 0, 0, 0, kernel, version, 0, 0, 0, lds_rows)
+        res = Result()
+        if out_cap is None:
+            out_cap = 64 * len(data) + (1 << 20)
+        out = np.empty(out_cap, np.uint8)
+        n, split = C.c_uint64(), C.c_uint64()
+        fb = np.frombuffer(enc.first_hdrs if len(enc.first_hdrs) else b"\0", np.uint8)
+        soff = (C.c_uint64 * NSTREAMS)(*list(enc.res.stream_offset))
+        rc = L.sfq_decode_pair_range_host(self._h, C.byref(p), enc.blocks, len(enc.blocks), fb.ctypes.data_as(C.c_void_p), len(enc.first_hdrs),
+                                          data.ctypes.data_as(C.c_void_p), len(data), soff, int(first_pair), int(n_pairs),
+                                          out.ctypes.data_as(C.c_void_p), out_cap, C.byref(n), C.byref(split), C.byref(res))
+        try:
+            self._check(rc)
+        except SfqError as e:
+            e.needed = int(n.value)
+            raise
+        return out[:split.value].tobytes(), out[split.value:n.value].tobytes(), res
+
+    @staticmethod
+    def pair_window_blocks(blocks, first_pair, n_pairs):
+        return pair_window_blocks(blocks, first_pair, n_pairs)
+
+
+def pair_window_blocks(blocks, first_pair, n_pairs):
+    """(first block, blocks) that hold pairs [first_pair, first_pair + n_pairs) of a call's block index (sfq_pair_window_blocks, no
+    GPU); None where there is no such window."""
+    if not isinstance(blocks, C.Array):
+        blocks = (BlockInfo * max(len(blocks), 1))(*blocks)
+    b0, nw = C.c_uint32(), C.c_uint32()
+    rc = lib().sfq_pair_window_blocks(blocks, len(blocks), int(first_pair), int(n_pairs), C.byref(b0), C.byref(nw))
+    return (int(b0.value), int(nw.value)) if rc == 0 else None

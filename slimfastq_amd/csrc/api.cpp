@@ -196,6 +196,8 @@ struct sfq_ctx {
     DevBuf pair_out;                                  // the split layout of a decoded text (while the switch is on)
     bool pair_split_on = false;                       // sfq_ctx_set_pair_split
     bool pair_split_done = false; u64 pair_first = 0, pair_n = 0;     // the last decode call's
+    bool mate_check_on = false;                       // sfq_ctx_set_mate_check
+    bool mate_report_valid = false; sfq_mate_report mate_report{};    // the last sfq_encode_pairs_host's
 };
 
 namespace {
@@ -1948,7 +1950,10 @@ int sfq_encode_blocks_host(sfq_ctx* ctx, const uint8_t* h_fastq, uint64_t nbytes
 // One pass on the context's stream, one synchronise: b null = split a into out, else interleave a and b into out (which holds
 // na + nb bytes and overlaps neither).  *got: what the device found.  Only a text with more records than the start arrays were laid
 // out for (one per 64 bytes, or what an earlier call learned) runs twice.
-static int pair_run(sfq_ctx* ctx, const u8* a, u64 na, const u8* b, u64 nb, u8* out, PairInfo* got) {
+// what: PAIR_COPY = the pass as it is; PAIR_COPY_NAMES = an interleave with the name pass in front of its copy; PAIR_NAMES = the record
+// starts, the rules and the name pass alone (out is not used).  win: a split's window of records, null = the whole text.
+enum PairWhat { PAIR_COPY, PAIR_COPY_NAMES, PAIR_NAMES };
+static int pair_run(sfq_ctx* ctx, const u8* a, u64 na, const u8* b, u64 nb, u8* out, PairInfo* got, PairWhat what = PAIR_COPY, const PairWindow* win = nullptr) {
     int rc;
     if ((rc = reserve_pinned_buf(ctx, ctx->pair_pin, ctx->pair_pin_cap, sizeof(PairInfo)))) return rc;
     for (int attempt = 0; ; attempt++) {
@@ -1968,8 +1973,10 @@ static int pair_run(sfq_ctx* ctx, const u8* a, u64 na, const u8* b, u64 nb, u8* 
         PairInfo* info = (PairInfo*)w;
         HIPC(hipMemsetAsync(info, 0, sizeof(PairInfo), ctx->st));
         const PairText ta{ a, na, w + sc_a, (u64*)(w + st_a) };
-        if (b) launch_pair_interleave(ta, PairText{ b, nb, w + sc_b, (u64*)(w + st_b) }, cap, out, info, ctx->st);
-        else launch_pair_split(ta, cap, (u32*)(w + lens), (u64*)(w + offa), (u64*)(w + tmp), out, info, ctx->st);
+        const PairText tb{ b, nb, w + sc_b, (u64*)(w + st_b) };
+        if (what == PAIR_NAMES) launch_pair_names(ta, tb, cap, info, ctx->st);
+        else if (b) launch_pair_interleave(ta, tb, cap, what == PAIR_COPY_NAMES, out, info, ctx->st);
+        else launch_pair_split(ta, cap, win ? *win : PairWindow{ 0, 0, 0, 0, 0 }, (u32*)(w + lens), (u64*)(w + offa), (u64*)(w + tmp), out, info, ctx->st);
         HIPC(hipGetLastError());
         HIPC(hipMemcpyAsync(ctx->pair_pin, info, sizeof(PairInfo), hipMemcpyDeviceToHost, ctx->st));
         HIPC(hipStreamSynchronize(ctx->st));
@@ -1987,6 +1994,8 @@ static int pair_run(sfq_ctx* ctx, const u8* a, u64 na, const u8* b, u64 nb, u8* 
     case PAIR_A_END: return fail(ctx, SFQ_E_FORMAT, "paired files: the first text does not end in a line end: its last record would run into its mate");
     case PAIR_ODD: return fail(ctx, SFQ_E_FORMAT, "paired files: the text holds %llu records, an odd number cannot be split into mates", r0);
     case PAIR_LONG: return fail(ctx, SFQ_E_UNSUPPORTED, "paired files: a record of 4 GiB or more");
+    case PAIR_RANGE: return fail(ctx, SFQ_E_ARG, "paired files: records %llu..+%llu end behind the text's %llu records", (unsigned long long)win->r0, (unsigned long long)win->nr, r0);
+    case PAIR_ROOM: return fail(ctx, SFQ_E_OVERFLOW, "paired files: the window's records need %llu bytes", (unsigned long long)got->nout);
     default: return fail(ctx, SFQ_E_HIP, "paired files: status %u", got->status);
     }
 }
@@ -2022,12 +2031,61 @@ int sfq_split_pairs(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, uint8_t* d_
     settle.ok = true;
     return SFQ_OK;
 }
+int sfq_split_pairs_range(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, uint64_t first_record, uint64_t n_records,
+                          uint8_t* d_out, uint64_t out_cap, uint64_t* split, uint64_t* out_bytes) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!d_text || !d_out || !split || !out_bytes) return fail(ctx, SFQ_E_ARG, "null argument");
+    if (!n) return fail(ctx, SFQ_E_ARG, "paired files: an empty text");
+    *split = 0; *out_bytes = 0;
+    if (!n_records || (n_records & 1))
+        return fail(ctx, SFQ_E_FORMAT, "paired files: a window of %llu records cannot be split into mates", (unsigned long long)n_records);
+    HIPC(hipSetDevice(ctx->dev));
+    Settle settle(ctx);
+    PairInfo got;
+    const PairWindow win{ 1, 0, first_record, n_records, out_cap };
+    const int rc = pair_run(ctx, d_text, n, nullptr, 0, d_out, &got, PAIR_COPY, &win);
+    if (rc == SFQ_E_OVERFLOW) *out_bytes = got.nout;
+    if (rc) return rc;
+    *split = got.split; *out_bytes = got.nout;
+    settle.ok = true;
+    return SFQ_OK;
+}
+static void mate_report_of(const PairInfo& got, sfq_mate_report* r) {
+    r->n_pairs = got.pieces; r->n_mismatch = got.mm_count;
+    r->first_mismatch = got.mm_count ? got.mm_first : 0;
+    r->first_off_a = got.mm_count ? got.mm_off[0] : 0; r->first_off_b = got.mm_count ? got.mm_off[1] : 0;
+}
+int sfq_check_mates(sfq_ctx* ctx, const uint8_t* d_a, uint64_t na, const uint8_t* d_b, uint64_t nb, sfq_mate_report* report) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!d_a || !report) return fail(ctx, SFQ_E_ARG, "null argument");
+    if (!na || (d_b && !nb)) return fail(ctx, SFQ_E_ARG, "paired files: an empty text (%llu and %llu bytes)", (unsigned long long)na, (unsigned long long)nb);
+    memset(report, 0, sizeof *report);
+    HIPC(hipSetDevice(ctx->dev));
+    Settle settle(ctx);
+    PairInfo got;
+    if (int rc = pair_run(ctx, d_a, na, d_b, d_b ? nb : 0, nullptr, &got, PAIR_NAMES)) return rc;
+    mate_report_of(got, report);
+    settle.ok = true;
+    return SFQ_OK;
+}
+// the name of the record whose header line begins at h[off] (slimfastq_amd.h), cut at 64 bytes, for a message
+static std::string mate_name(const u8* h, u64 n, u64 off) {
+    u64 e = off < n ? off + 1 : n;
+    if (off < n && h[off] == '\n') e = off;
+    const u64 b = e;
+    while (e < n && h[e] != '\n' && h[e] != ' ' && h[e] != '\t') e++;
+    if (e - b >= 2 && h[e - 2] == '/' && (h[e - 1] == '1' || h[e - 1] == '2')) e -= 2;
+    std::string s((const char*)h + b, (size_t)std::min<u64>(e - b, 64));
+    for (char& c : s) if ((unsigned char)c < 32 || (unsigned char)c > 126) c = '?';
+    return s;
+}
 int sfq_encode_pairs_host(sfq_ctx* ctx, const uint8_t* h_a, uint64_t na, const uint8_t* h_b, uint64_t nb, const sfq_params* params,
                           uint8_t* h_out, uint64_t out_cap, sfq_result* result) {
     if (!ctx) return SFQ_E_ARG;
     if (!h_a || !h_b || !h_out || !params || !result) return fail(ctx, SFQ_E_ARG, "null argument");
     if (!na || !nb) return fail(ctx, SFQ_E_ARG, "paired files: an empty text (%llu and %llu bytes)", (unsigned long long)na, (unsigned long long)nb);
     HIPC(hipSetDevice(ctx->dev));
+    ctx->mate_report_valid = false;
     int rc;
     const u64 at_b = ((na + 15) & ~15ull) + 16;
     if ((rc = reserve(ctx, ctx->pair_in, (size_t)(at_b + nb + 16)))) return rc;
@@ -2038,8 +2096,16 @@ int sfq_encode_pairs_host(sfq_ctx* ctx, const uint8_t* h_a, uint64_t na, const u
     {
         Settle settle(ctx);
         PairInfo got;
-        if ((rc = pair_run(ctx, d_a, na, d_a + at_b, nb, (u8*)ctx->in_stage.p, &got))) return rc;
+        if ((rc = pair_run(ctx, d_a, na, d_a + at_b, nb, (u8*)ctx->in_stage.p, &got, ctx->mate_check_on ? PAIR_COPY_NAMES : PAIR_COPY))) return rc;
         settle.ok = true;
+        if (ctx->mate_check_on) {
+            mate_report_of(got, &ctx->mate_report);
+            ctx->mate_report_valid = true;
+            if (got.mm_count)
+                return fail(ctx, SFQ_E_FORMAT, "paired files: the names of %llu of %llu pairs differ, the first pair %llu: \"%s\" and \"%s\"",
+                            (unsigned long long)got.mm_count, (unsigned long long)got.pieces, (unsigned long long)got.mm_first,
+                            mate_name(h_a, na, got.mm_off[0]).c_str(), mate_name(h_b, nb, got.mm_off[1]).c_str());
+        }
     }
     return encode_staged(ctx, na + nb, params, h_out, out_cap, result);
 }
@@ -2048,6 +2114,17 @@ int sfq_ctx_set_pair_split(sfq_ctx* ctx, int on) {
     ctx->pair_split_on = on != 0;
     if (!on) release(ctx->pair_out);
     return SFQ_OK;
+}
+int sfq_ctx_set_mate_check(sfq_ctx* ctx, int on) {
+    if (!ctx) return SFQ_E_ARG;
+    ctx->mate_check_on = on != 0;
+    return SFQ_OK;
+}
+int sfq_get_mate_report(const sfq_ctx* ctx, sfq_mate_report* out) {
+    if (!ctx || !out) return SFQ_E_ARG;
+    if (!ctx->mate_report_valid) { memset(out, 0, sizeof *out); return 0; }
+    *out = ctx->mate_report;
+    return 1;
 }
 int sfq_get_pair_split(const sfq_ctx* ctx, uint64_t* first_bytes, uint64_t* n_pairs) {
     if (!ctx) return SFQ_E_ARG;
@@ -2117,7 +2194,8 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
                        uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* res, const u32* expect, const struct Window& w);
 // The blocks [b0, b0 + n) of the call that one decode produces: all of them (sfq_decode_blocks), or a window (sfq_decode_block_range:
 // ranged -- what is outside the window is decoded only where the format forces it, decode_body)
-struct Window { u32 b0, n; bool ranged; };
+// pairs: a window of pairs (sfq_decode_pair_range_host): decode_host finds b0 and n itself and cuts and splits what was decoded
+struct Window { u32 b0, n; bool ranged; bool pairs = false; u64 first_pair = 0, n_pairs = 0; };
 // The checksums installed with sfq_set_block_checksums belong to the decode call that follows, whatever it returns: both entry
 // points take them before anything else, so that no early return leaves them for the call after.
 struct Expected {
@@ -2136,7 +2214,7 @@ static int decode_device(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_inf
     drop_encode_blobs(ctx);                             // whatever an encode left behind is not this archive's
     ctx->crcs.clear(); ctx->text_crc = 0;
     ctx->pair_split_done = false;
-    if (w.ranged && ctx->pair_split_on)
+    if (w.ranged && ctx->pair_split_on && !w.pairs)
         return fail(ctx, SFQ_E_UNSUPPORTED, "a window of blocks may start at a second mate and is not split: sfq_ctx_set_pair_split(ctx, 0) comes first");
     const bool check = ex.set;
     const std::vector<u32>& expect = ex.crc;
@@ -2858,9 +2936,22 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
 static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_info* h_blocks, uint32_t n_blocks,
                        const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
                        const uint8_t* h_streams, uint64_t streams_bytes, const uint64_t stream_offset[SFQ_NSTREAMS],
-                       uint8_t* h_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* result, const Window& w) {
+                       uint8_t* h_out, uint64_t out_cap, uint64_t* out_bytes, sfq_result* result, const Window& w_in, uint64_t* split = nullptr) {
     const Expected ex(ctx);
     if (!h_streams || !h_out || !h_blocks || !stream_offset) return fail(ctx, SFQ_E_ARG, "null argument");
+    Window w = w_in;
+    u64 rec0 = 0;                                          // a window of pairs: its first record, counted from the window's first block
+    if (w.pairs) {
+        if (!split || !out_bytes) return fail(ctx, SFQ_E_ARG, "null argument");
+        *split = 0;
+        u64 recs = 0;
+        for (u32 b = 0; b < n_blocks; b++) recs += h_blocks[b].n_records;
+        if (recs & 1) return fail(ctx, SFQ_E_FORMAT, "paired files: the call holds %llu records, an odd number was not written from paired files", (unsigned long long)recs);
+        if (sfq_pair_window_blocks(h_blocks, n_blocks, w.first_pair, w.n_pairs, &w.b0, &w.n))
+            return fail(ctx, SFQ_E_ARG, "pairs %llu..+%llu: not a window of the call's %llu pairs", (unsigned long long)w.first_pair, (unsigned long long)w.n_pairs, (unsigned long long)(recs >> 1));
+        rec0 = 2 * w.first_pair;
+        for (u32 b = 0; b < w.b0; b++) rec0 -= h_blocks[b].n_records;
+    }
     if (w.n == 0 || w.b0 >= n_blocks || w.n > n_blocks - w.b0) return fail(ctx, SFQ_E_ARG, "blocks %u..+%u: not a window of the call's %u blocks", w.b0, w.n, n_blocks);
     HIPC(hipSetDevice(ctx->dev));
     int rc;
@@ -2908,7 +2999,18 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
                        stream_offset, (u8*)ctx->out_stage.p, out_cap, out_bytes, result, ex, w);
     if (rc) return rc;
     const u8* d_text = (const u8*)ctx->out_stage.p;
-    if (ctx->pair_split_on) {                              // behind the checksum pass: the archive describes the interleaved text
+    if (w.pairs) {                                         // behind the checksum pass too: cut to the pairs and split in one copy
+        if (!*out_bytes) return fail(ctx, SFQ_E_FORMAT, "paired files: an empty text");
+        if ((rc = reserve(ctx, ctx->pair_out, (size_t)*out_bytes + 16))) return rc;
+        Settle settle(ctx);
+        PairInfo got;
+        const PairWindow win{ 1, 0, rec0, 2 * w.n_pairs, *out_bytes };
+        if ((rc = pair_run(ctx, d_text, *out_bytes, nullptr, 0, (u8*)ctx->pair_out.p, &got, PAIR_COPY, &win))) return rc;
+        settle.ok = true;
+        d_text = (const u8*)ctx->pair_out.p;
+        *out_bytes = got.nout; *split = got.split;
+        ctx->pair_split_done = true; ctx->pair_first = got.split; ctx->pair_n = w.n_pairs;
+    } else if (ctx->pair_split_on) {                       // behind the checksum pass: the archive describes the interleaved text
         if (!*out_bytes) return fail(ctx, SFQ_E_FORMAT, "paired files: an empty text");
         if ((rc = reserve(ctx, ctx->pair_out, (size_t)*out_bytes + 16))) return rc;
         Settle settle(ctx);
@@ -2938,6 +3040,34 @@ int sfq_decode_block_range_host(sfq_ctx* ctx, const sfq_params* params, const sf
     if (!ctx) return SFQ_E_ARG;
     return decode_host(ctx, params, h_blocks, n_blocks, h_first_hdrs, first_hdr_bytes, h_streams, streams_bytes, stream_offset, h_out, out_cap, out_bytes, result,
                        Window{ first_block, n_window, true });
+}
+
+int sfq_pair_window_blocks(const sfq_block_info* h_blocks, uint32_t n_blocks, uint64_t first_pair, uint64_t n_pairs,
+                           uint32_t* first_block, uint32_t* n_window) {
+    if (!h_blocks || !first_block || !n_window || !n_pairs) return SFQ_E_ARG;
+    if (first_pair > (~0ull >> 2) || n_pairs > (~0ull >> 2)) return SFQ_E_ARG;
+    const u64 r0 = 2 * first_pair, r1 = r0 + 2 * n_pairs;                       // records [r0, r1)
+    u64 at = 0;
+    u32 b0 = n_blocks, b1 = n_blocks;                      // the block of record r0, the block of record r1 - 1
+    for (u32 b = 0; b < n_blocks; b++) {
+        const u64 end = at + h_blocks[b].n_records;
+        if (b0 == n_blocks && r0 < end) b0 = b;
+        if (r1 <= end && r1 > at) { b1 = b; break; }
+        at = end;
+    }
+    if (b0 == n_blocks || b1 == n_blocks) return SFQ_E_ARG;
+    *first_block = b0; *n_window = b1 - b0 + 1;
+    return SFQ_OK;
+}
+int sfq_decode_pair_range_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_info* h_blocks, uint32_t n_blocks,
+                               const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
+                               const uint8_t* h_streams, uint64_t streams_bytes, const uint64_t stream_offset[SFQ_NSTREAMS],
+                               uint64_t first_pair, uint64_t n_pairs,
+                               uint8_t* h_out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* split, sfq_result* result) {
+    if (!ctx) return SFQ_E_ARG;
+    Window w{ 0, 0, true };
+    w.pairs = true; w.first_pair = first_pair; w.n_pairs = n_pairs;
+    return decode_host(ctx, params, h_blocks, n_blocks, h_first_hdrs, first_hdr_bytes, h_streams, streams_bytes, stream_offset, h_out, out_cap, out_bytes, result, w, split);
 }
 
 int sfq_crc32(sfq_ctx* ctx, const uint8_t* d_data, const uint64_t* h_bounds, uint32_t n_ranges, uint32_t* h_crc) {

@@ -13,6 +13,8 @@
 //   -R F:N    : with -d: records F .. F + N - 1 only (numbered from 0 over the archive) -- the blocks that hold them are decoded, no others
 //   -p fastq  : paired files: the mates of -u's records; both are interleaved on the GPU and coded as one text (info key "usr.pair");
 //               with -d: the second mates go here, the first to -u
+//   -W F:N    : with -d and -p: pairs F .. F + N - 1 only (numbered from 0 over the archive), cut and split on the GPU
+//   -M        : with -p on encode: the mates' names are compared on the GPU before a slab is coded; a mismatch ends the run
 // All model / coder work happens in libslimfastq_amd.so on the GPU; this file parses arguments, reads and
 // writes files and fills the info page.
 #include <sys/stat.h>
@@ -102,6 +104,12 @@ static void usage() {
            "                   (R1 R2 R1 R2 ...) and coded as one text, so a mate's header costs the one field that differs; with -d:\n"
            "                   the first mates are written to -u, the second mates here (the archive must have been written with -p;\n"
            "                   without -p it decodes to interleaved FASTQ); needs -u, not with -b or -R\n"
+           "-W first:count   : with -d and -p: write pairs first .. first+count-1 only (numbered from 0 over the whole archive; count is\n"
+           "                   clipped at the end): first mates to -u, second mates to -p; only the blocks that hold them are decoded,\n"
+           "                   and they are cut to the pairs and split on the GPU; needs -d, -u and -p, not with -R or -b\n"
+           "-M               : with -p on a compress run: compare the names of every pair of mates on the GPU before it is coded (the\n"
+           "                   header's first word, without a final /1 or /2); a pair that differs ends the run with its index and both\n"
+           "                   names, and no archive is written\n"
            "-S mbytes        : input is compressed in slabs of this many MiB, one archive segment each (default 512 for a\n"
            "                   regular file, read ahead while the GPU codes the slab before; 2048 for a pipe)\n"
            "-t threads       : threads reading a slab (default 6)\n"
@@ -135,6 +143,8 @@ struct Opts {
     bool range = false; uint64_t r_first = 0, r_count = 0;             // -R first:count
     int qmap = 0; std::string qmap_name;                               // -Q: SFQ_QMAP_* (0 = none) and its name
     std::string pair;                                                  // -p: the second file of a pair
+    bool window = false; uint64_t w_first = 0, w_count = 0;            // -W first:count (pairs)
+    bool mates = false;                                                // -M
 };
 // "FIRST:COUNT", both decimal, COUNT > 0
 static bool parse_range(const char* t, uint64_t& first, uint64_t& count) {
@@ -148,6 +158,16 @@ static bool parse_range(const char* t, uint64_t& first, uint64_t& count) {
     if (errno || !e2 || *e2 || !c) return false;
     first = f; count = c;
     return true;
+}
+// the name of the record whose header line begins at t[off] (slimfastq_amd.h: mates by name), cut at 64 bytes, for a message
+static std::string mate_name(const uint8_t* t, size_t n, uint64_t off) {
+    if (off >= n || t[off] == '\n') return "";
+    size_t b = (size_t)off + 1, e = b;
+    while (e < n && t[e] != '\n' && t[e] != ' ' && t[e] != '\t') e++;
+    if (e - b >= 2 && t[e - 2] == '/' && (t[e - 1] == '1' || t[e - 1] == '2')) e -= 2;
+    std::string s((const char*)t + b, std::min<size_t>(e - b, 64));
+    for (char& c : s) if ((unsigned char)c < 32 || (unsigned char)c > 126) c = '?';
+    return s;
 }
 // where the first `skip` records (four lines each) of a text end, or n where it has fewer
 static size_t records_end(const uint8_t* t, size_t n, uint64_t skip) {
@@ -285,6 +305,7 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     const bool legacy = o.block_reads == 0;
     if (sfq_ctx_set_checksums(ctx, o.checksum ? 1 : 0)) croak("%s", sfq_last_error(ctx));
     if (sfq_ctx_set_stats(ctx, o.stats ? 1 : 0)) croak("%s", sfq_last_error(ctx));
+    if (sfq_ctx_set_mate_check(ctx, o.mates ? 1 : 0)) croak("%s", sfq_last_error(ctx));
     uint8_t qlut[256];
     if (o.qmap && sfq_quality_map_preset(o.qmap, qlut)) croak("-Q: no such preset");
     if (sfq_ctx_set_quality_map(ctx, o.qmap ? qlut : nullptr)) croak("%s", sfq_last_error(ctx));      // (a -b worker's context: set for every job)
@@ -504,7 +525,15 @@ static void encode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             if (!out.reserve(bound)) croak("out of memory");
             out.touch((ua + ub) / 3 + (1 << 20));
             sfq_result res;
-            if (sfq_encode_pairs_host(ctx, fq.p, ua, fb.p, ub, &p, out.p, bound, &res)) croak("%s", sfq_last_error(ctx));
+            if (sfq_encode_pairs_host(ctx, fq.p, ua, fb.p, ub, &p, out.p, bound, &res)) {
+                sfq_mate_report mr;                                     // -M: the report counts from the slab's first pair
+                if (o.mates && sfq_get_mate_report(ctx, &mr) == 1 && mr.n_mismatch)
+                    croak("-M: the files are out of step: pair %llu is \"%s\" in '%s' and \"%s\" in '%s' (%llu of the %llu pairs from pair %llu on differ)",
+                          (unsigned long long)(done + mr.first_mismatch), mate_name(fq.p, ua, mr.first_off_a).c_str(), usr.c_str(),
+                          mate_name(fb.p, ub, mr.first_off_b).c_str(), o.pair.c_str(), (unsigned long long)mr.n_mismatch,
+                          (unsigned long long)mr.n_pairs, (unsigned long long)done);
+                croak("%s", sfq_last_error(ctx));
+            }
             tick("sfq_encode_pairs_host");
             qmap_changed += sfq_get_quality_map_changed(ctx);
             collect(ctx, res, ua + ub, idx, o.checksum, o.stats);
@@ -649,6 +678,13 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         if (o.r_first >= total) croak("-R %llu:%llu: the archive holds %llu records", (unsigned long long)o.r_first, (unsigned long long)o.r_count, (unsigned long long)total);
         r_lo = o.r_first; r_hi = o.r_count > total - r_lo ? total : r_lo + o.r_count;
     }
+    // -W: pairs [w_first, w_first + w_count) are records [r_lo, r_hi) too; what -R does per segment holds with pairs for records
+    const bool ranged = o.range || o.window;
+    if (o.window) {
+        const uint64_t total = (blocks.back().first_record + blocks.back().n_records) / 2;
+        if (o.w_first >= total) croak("-W %llu:%llu: the archive holds %llu pairs", (unsigned long long)o.w_first, (unsigned long long)o.w_count, (unsigned long long)total);
+        r_lo = 2 * o.w_first; r_hi = o.w_count > total - o.w_first ? 2 * total : r_lo + 2 * o.w_count;
+    }
     const bool paired = !o.pair.empty();
     if (paired && a.get_long("usr.pair", 0) != 1) croak("-p: %s was not written from paired files (no usr.pair in its info): decode it without -p", fil.c_str());
     FILE* of = stdout;
@@ -683,7 +719,7 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     // several segments of known size: the text of one is written (a thread) while the next is decoded, out of two
     // page-locked buffers (kept for the life of the process, like the encoder's)
     static uint8_t* opin[2] = { nullptr, nullptr }; static size_t opin_cap = 0;
-    size_t max_raw = 0; bool sized = segs.size() > 1 && !o.range;
+    size_t max_raw = 0; bool sized = segs.size() > 1 && !ranged;
     for (const sfqc::Segment& g : segs) { max_raw = std::max<size_t>(max_raw, (size_t)g.raw_bytes); if (!g.raw_bytes) sized = false; }
     if (sized && opin_cap < max_raw + 64) {
         for (auto& q : opin) { if (q) sfq_host_free(ctx, q); q = nullptr; }
@@ -708,12 +744,18 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         // later segment that shares them)
         uint32_t w0 = 0, wn = (uint32_t)sb.size();
         bool touched = true;
-        if (o.range) {
+        uint64_t wp0 = 0, wpn = 0;                                      // -W: the segment's pairs of the window, counted from its first
+        if (ranged) {
             const uint64_t seg_end = rec0 + sb.back().first_record + sb.back().n_records, br = sb[0].n_records;
+            // (a -p encode takes the same number of records from both files per slab: a segment holds whole pairs)
+            if (o.window && ((rec0 | seg_end) & 1)) croak("-W: segment %zu holds records %llu..%llu, not whole pairs: %s was not written by -p",
+                                                          (size_t)(&g - segs.data()), (unsigned long long)rec0, (unsigned long long)seg_end, fil.c_str());
             touched = r_lo < seg_end && r_hi > rec0 && br;
             if (touched) {
                 const uint64_t lo = std::max(r_lo, rec0) - rec0, hi = std::min(r_hi, seg_end) - rec0;
                 w0 = (uint32_t)(lo / br); wn = (uint32_t)((hi - 1) / br) - w0 + 1;
+                wp0 = lo / 2; wpn = (hi - lo) / 2;
+                if (o.window && sfq_pair_window_blocks(sb.data(), (uint32_t)sb.size(), wp0, wpn, &w0, &wn)) croak("bad block index (a segment's records)");
             }
         }
         if (!touched) for (int s = 0; s < SFQ_NSTREAMS; s++) spos[s] += need[s];
@@ -739,11 +781,12 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         // (a window: its share of the segment's text and as much again; the call reports what it needs where that is too little --
         //  or, where the window's lines alone outgrow it, a damaged stream: then the segment's size is tried)
         const uint64_t cap_seg = cap;
-        if (o.range && wn < sb.size()) cap = std::min<uint64_t>(cap_seg, cap_seg / sb.size() * wn * 2 + (1 << 20));
+        if (ranged && wn < sb.size()) cap = std::min<uint64_t>(cap_seg, cap_seg / sb.size() * wn * 2 + (1 << 20));
         sfq_result res;
         int rc = 0;
         uint8_t* dst = nullptr;
-        for (int attempt = 0; attempt < (o.range ? 3 : 2); attempt++) {
+        uint64_t wsplit = 0;
+        for (int attempt = 0; attempt < (ranged ? 3 : 2); attempt++) {
             if (sized && cap + 16 <= opin_cap) dst = opin[ob];
             else {
                 if (!out.reserve((size_t)cap + 16)) croak("out of memory");
@@ -752,12 +795,14 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             }
             // (the expected checksums are consumed by the call they are installed for)
             if (!crcs.empty() && sfq_set_block_checksums(ctx, crcs.data() + b0 + w0, wn)) croak("%s", sfq_last_error(ctx));
-            if (o.range) rc = sfq_decode_block_range_host(ctx, &p, sb.data(), (uint32_t)sb.size(), first.data() + h0, hbytes,
+            if (o.window) rc = sfq_decode_pair_range_host(ctx, &p, sb.data(), (uint32_t)sb.size(), first.data() + h0, hbytes,
+                                                          data.data(), data.size(), soff, wp0, wpn, dst, cap, &got, &wsplit, &res);
+            else if (o.range) rc = sfq_decode_block_range_host(ctx, &p, sb.data(), (uint32_t)sb.size(), first.data() + h0, hbytes,
                                                           data.data(), data.size(), soff, w0, wn, dst, cap, &got, &res);
             else
             rc = sfq_decode_blocks_host(ctx, &p, sb.data(), (uint32_t)sb.size(), first.data() + h0, hbytes,
                                         data.data(), data.size(), soff, dst, cap, &got, &res);
-            if (o.range && rc == SFQ_E_CORRUPT && cap < cap_seg) { cap = cap_seg; continue; }
+            if (ranged && rc == SFQ_E_CORRUPT && cap < cap_seg) { cap = cap_seg; continue; }
             if (rc != SFQ_E_OVERFLOW || got <= cap) break;
             cap = got;                                                 // the call reports the size it needs
         }
@@ -801,7 +846,7 @@ int main(int argc, char** argv) {
     Opts o;
     bool statistics = false;
     if (argc == 1) usage();
-    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKY1234u:f:l:B:g:S:T:C:t:R:Q:p:")) != -1;) {
+    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKYM1234u:f:l:B:g:S:T:C:t:R:Q:p:W:")) != -1;) {
         switch (opt) {
         case 'u': g_usr = optarg; break;
         case 'f': fil = optarg; break;
@@ -827,6 +872,14 @@ int main(int argc, char** argv) {
             break;
         case 'p': o.pair = optarg; break;
         case 'R': if (!parse_range(optarg, o.r_first, o.r_count)) usage(); o.range = true; break;
+        case 'W':
+            if (!parse_range(optarg, o.w_first, o.w_count) || o.w_first > (~0ull >> 2) || o.w_count > (~0ull >> 2)) {
+                fprintf(stderr, "slimfastq: -W %s: a window of pairs is first:count, both decimal, count above 0\n", optarg);
+                return 1;
+            }
+            o.window = true;
+            break;
+        case 'M': o.mates = true; break;
         case 'C': o.chain_reads = strtol(optarg, 0, 0); break;
         case 't': o.io_threads = std::min(64, std::max(1, atoi(optarg))); break;
         case 'v': printf("Version %s\nInternal format version=%u (block format %u)\n", kUserVersion, kInternalVersion, kBlockVersion); exit(0);
@@ -852,6 +905,17 @@ int main(int argc, char** argv) {
 
     if (o.range && g_encode) {
         fprintf(stderr, "slimfastq: -R (a range of records) goes with -d: it picks what a decode writes\n");
+        return 1;
+    }
+
+    if (o.window && (g_encode || g_batch || o.range || o.pair.empty())) {
+        fprintf(stderr, "slimfastq: -W (a window of pairs) goes with -d and -p: it picks the pairs a decode writes to -u and -p%s\n",
+                o.range ? "; it does not go with -R, which counts records" : g_batch ? "; it does not go with -b" : "");
+        return 1;
+    }
+    if (o.mates && (!g_encode || o.pair.empty())) {
+        fprintf(stderr, "slimfastq: -M (the mates' names are compared) goes with -p on a compress run: %s\n",
+                !g_encode ? "a decode writes what the archive holds" : "it compares the records of -u with those of -p");
         return 1;
     }
 

@@ -293,12 +293,23 @@ enum PairStatus : u32 {
     PAIR_A_END,             // A does not end in '\n'
     PAIR_ODD,               // an odd number of records to split
     PAIR_LONG,              // a record of 4 GiB or more
-    PAIR_CAP                // more records than the start arrays hold: info->recs says how many, nothing else was done
+    PAIR_CAP,               // more records than the start arrays hold: info->recs says how many, nothing else was done
+    PAIR_RANGE,             // a window of records that ends behind the text's last record
+    PAIR_ROOM               // a window's records need more than the output holds: info->nout says how much
 };
-struct PairInfo { u64 lines[2], recs[2], split; u32 status, pad; };
+// pieces, win0, nout: what k_pair_check found the copy to be -- P of its 2 P pieces, the source offset of a split's first record, the
+// output's bytes (known to the host unless a window is cut).  mm_*: the name pass (k_pair_names), untouched where it does not run.
+struct PairInfo { u64 lines[2], recs[2], split; u32 status, pad; u64 pieces, win0, nout; u64 mm_count, mm_first, mm_off[2]; };
 // a text and what the passes over it need: scratch = qmap_scratch(d, n).bytes bytes, 16-byte aligned; starts: cap + 1 entries
 struct PairText { const u8* d; u64 n; u8* scratch; u64* starts; };
-// info: zeroed by the caller.  out: a.n + b.n bytes; nothing outside them is written, and nothing at all unless info->status stays 0
-void launch_pair_interleave(const PairText& a, const PairText& b, u64 cap /* records a start array holds */, u8* out, PairInfo* info, hipStream_t st);
-// out: t.n bytes, the even records then (from info->split on) the odd ones; lens[cap / 2 + 1], offa[cap / 2 + 2], scan_tmp as launch_scan_u32 wants it for cap / 2 + 1
-void launch_pair_split(const PairText& t, u64 cap, u32* lens, u64* offa, u64* scan_tmp, u8* out, PairInfo* info, hipStream_t st);
+// a split's window: records [r0, r0 + nr) alone, nr even and > 0, into an output of out_cap bytes; on = 0: the whole text
+struct PairWindow { u32 on, pad; u64 r0, nr, out_cap; };
+// info: zeroed by the caller.  out: a.n + b.n bytes; nothing outside them is written, and nothing at all unless info->status stays 0.
+// names: k_pair_names runs between the check and the copy (the copy does not wait for what it finds: info->mm_count tells the host)
+void launch_pair_interleave(const PairText& a, const PairText& b, u64 cap /* records a start array holds */, bool names, u8* out, PairInfo* info, hipStream_t st);
+// out: t.n bytes (a window: info->nout, at most win.out_cap), the even records then (from info->split on) the odd ones; lens[cap / 2 + 1],
+// offa[cap / 2 + 2], scan_tmp as launch_scan_u32 wants it for cap / 2 + 1
+void launch_pair_split(const PairText& t, u64 cap, const PairWindow& win, u32* lens, u64* offa, u64* scan_tmp, u8* out, PairInfo* info, hipStream_t st);
+// the record starts, the rules and the name pass, no copy: b.d null = t is interleaved (record 2k against 2k + 1, a split's rules),
+// else record i of a against record i of b (an interleave's rules).  Writes info alone.
+void launch_pair_names(const PairText& a, const PairText& b, u64 cap, PairInfo* info, hipStream_t st);

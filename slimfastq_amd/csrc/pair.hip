@@ -10,6 +10,11 @@
 //        interleave: piece 2i = A's record i to sA[i] + sB[i], piece 2i + 1 = B's record i to sA[i + 1] + sB[i]
 //        split:      piece k < P = record 2k to offa[k], piece P + k = record 2k + 1 to offa[P] + S[2k] - offa[k]
 //      none of them stored: a piece's destination and source are two loads from the start arrays.
+//      A window of records [r0, r0 + n) split (sfq_split_pairs_range) is the same copy over starts + r0: k_pair_check validates the range
+//      and leaves the window's first source byte, its size and its pairs in PairInfo, where the copy reads them (the size is known
+//      on the device alone; the host lays the grid over an upper bound).
+//   5. k_pair_names (sfq_check_mates, sfq_ctx_set_mate_check): a lane per pair compares the names of two header lines found through
+//      the start arrays, sixteen bytes a step.
 // The copy is laid out over the OUTPUT, not over the pieces: a wavefront takes a span of 16 KiB of the output (a workgroup four of
 // them), a lane an aligned 16-byte unit of it, so a record of 200 KB is copied by as many lanes as 600 records of 350 bytes, and no
 // lane or wave walks a long record.  Per span one 64-way search over the destinations (4 steps for 2^23 pieces) finds the piece of
@@ -22,6 +27,7 @@
 // Every kernel after the check returns at once where the status is set, so a refused call writes nothing to the output.
 #include "kernels.h"
 #include "dev_lines.h"
+#include "frame_masks.h"
 
 namespace {
 using namespace textspan;
@@ -63,7 +69,9 @@ __global__ __launch_bounds__(256) void k_pair_starts(const u8* __restrict__ base
 
 // ---- 3. the rules --------------------------------------------------------------------------------------------------------------
 struct CheckText { const u64* line_ends; const u8* last; u64 n; u64* starts; };       // line_ends: the scan's last entry; last: the text's last byte
-__global__ void k_pair_check(PairInfo* info, u32 split, CheckText a, CheckText b, u64 cap) {
+// Also what the copy and the name pass work on: P pairs (of pieces, of records), the source offset of the first record that is
+// copied, the output's bytes.  A window's (win.on, split only) are known here first; its range and its room are checked here.
+__global__ void k_pair_check(PairInfo* info, u32 split, CheckText a, CheckText b, u64 cap, PairWindow win) {
     if (threadIdx.x || blockIdx.x) return;
     u32 st = PAIR_OK;
     const CheckText t[2] = { a, b };
@@ -76,17 +84,27 @@ __global__ void k_pair_check(PairInfo* info, u32 split, CheckText a, CheckText b
         if ((lines & 3) && !st) st = i ? PAIR_LINES_B : PAIR_LINES_A;
         if (recs <= cap) { t[i].starts[0] = 0; t[i].starts[recs] = t[i].n; } else fits = false;
     }
-    if (!st && !split && info->recs[0] != info->recs[1]) st = PAIR_COUNTS;
+    const u64 recs = info->recs[0];
+    if (!st && !split && recs != info->recs[1]) st = PAIR_COUNTS;
     if (!st && !split && *a.last != '\n') st = PAIR_A_END;
-    if (!st && split && (info->recs[0] & 1)) st = PAIR_ODD;
+    if (!st && split && !win.on && (recs & 1)) st = PAIR_ODD;
+    if (!st && win.on && (win.r0 > recs || win.nr > recs - win.r0)) st = PAIR_RANGE;
     if (!st && !fits) st = PAIR_CAP;
+    u64 P = split ? recs >> 1 : recs, win0 = 0, nout = split ? a.n : a.n + b.n;
+    if (!st && win.on) {
+        win0 = a.starts[win.r0]; nout = a.starts[win.r0 + win.nr] - win0; P = win.nr >> 1;
+        if (nout > win.out_cap) st = PAIR_ROOM;
+    }
+    info->pieces = P; info->win0 = win0; info->nout = nout;
+    info->mm_first = ~0ull;
     info->status = st;
 }
-// interleave (lens null): s = A's starts, s2 = B's; split: s = the text's starts, lens[k] = the length of record 2k, 0 behind the last
+// interleave (lens null): s = A's starts, s2 = B's; split: s = the starts from the first record that is copied on, lens[k] = the
+// length of record 2k of those, 0 behind the last
 __global__ __launch_bounds__(256) void k_pair_lens(PairInfo* info, const u64* __restrict__ s, const u64* __restrict__ s2, u32* __restrict__ lens, u64 nlens) {
     if (info->status) return;
     const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
-    const u64 P = lens ? info->recs[0] >> 1 : info->recs[0];
+    const u64 P = info->pieces;
     u64 l0 = 0, l1 = 0;
     if (k < P) {
         if (lens) { l0 = s[2 * k + 1] - s[2 * k]; l1 = s[2 * k + 2] - s[2 * k + 1]; }
@@ -99,9 +117,10 @@ __global__ __launch_bounds__(256) void k_pair_lens(PairInfo* info, const u64* __
 // ---- 4. the copy ---------------------------------------------------------------------------------------------------------------
 struct PairJob {
     u32 split;
-    const u64* s0; const u64* s1;       // interleave: A's starts, B's starts; split: the text's starts, offa
+    const u64* s0; const u64* s1;       // interleave: A's starts, B's starts; split: the starts from the first record copied on, offa
     u64 src0, src1;                     // interleave: A, B; split: the text (addresses)
-    u64 nout;
+    u64 nout;                           // on the host an upper bound that sizes the grid; in the kernel what k_pair_check found
+    u64 base;                           // split: the source offset of the first record copied (k_pair_check; 0 unless a window is cut)
 };
 // piece k of 2 P: where it goes in the output and the address it comes from; k >= 2 P: the output's end
 __device__ __forceinline__ void piece(const PairJob& J, u64 P, u64 k, u64* dst, u64* src) {
@@ -111,7 +130,7 @@ __device__ __forceinline__ void piece(const PairJob& J, u64 P, u64 k, u64* dst, 
         if (k & 1) { *dst = J.s0[i + 1] + b; *src = J.src1 + b; }
         else { const u64 a = J.s0[i]; *dst = a + b; *src = J.src0 + a; }
     } else if (k < P) { *dst = J.s1[k]; *src = J.src0 + J.s0[2 * k]; }
-    else { const u64 j = k - P; *dst = J.s1[P] + J.s0[2 * j] - J.s1[j]; *src = J.src0 + J.s0[2 * j + 1]; }
+    else { const u64 j = k - P; *dst = J.s1[P] + (J.s0[2 * j] - J.base) - J.s1[j]; *src = J.src0 + J.s0[2 * j + 1]; }
 }
 // the piece that holds output byte key (< nout): 64 probes a step, one per lane
 __device__ __forceinline__ u64 find_piece(const PairJob& J, u64 P, u64 key, u32 lane) {
@@ -179,15 +198,19 @@ __device__ __forceinline__ void copy_units(u8* obase, u64 pos, u32 nun, u64 lo_o
         for (u64 x = lo_v; x < hi_v; x++) { const u32 i = (u32)(x - u); obase[x] = (u8)(o[i >> 2] >> (8 * (i & 3))); }
     }
 }
+// nspans: laid over J.nout as the host knows it, an upper bound where a window is cut; the real end is k_pair_check's
 __global__ __launch_bounds__(256) void k_pair_copy(PairJob J, PairInfo* info, u8* obase /* 16-byte aligned */, u32 mis /* the output starts at obase + mis */, u64 nspans) {
     if (info->status) return;
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u64 P = J.split ? info->recs[0] >> 1 : info->recs[0];
+    const u64 P = info->pieces;
+    J.nout = info->nout; J.base = info->win0;
     const u64 lo_out = mis, hi_out = (u64)mis + J.nout;
+    const u64 end_all = (hi_out + 15) & ~15ull;
     if (J.split && !blockIdx.x && !threadIdx.x) info->split = J.s1[P];
     for (u64 s = (u64)blockIdx.x * 4 + wave; s < nspans; s += (u64)gridDim.x * 4) {
         u64 pos = s * SPAN;
-        const u64 end_all = (hi_out + 15) & ~15ull, end = pos + SPAN < end_all ? pos + SPAN : end_all;
+        if (pos >= end_all) return;                             // (a window's output ends in front of its bound)
+        const u64 end = pos + SPAN < end_all ? pos + SPAN : end_all;
         u64 k0 = find_piece(J, P, (pos > lo_out ? pos : lo_out) - mis, lane);
         while (pos < end) {
             // the window: piece k0 holds pos
@@ -212,6 +235,112 @@ __global__ __launch_bounds__(256) void k_pair_copy(PairJob J, PairInfo* info, u8
     }
 }
 
+// ---- 5. mate names -------------------------------------------------------------------------------------------------------------
+// A lane takes a pair and walks its two header lines sixteen bytes at a time, both from the line's first byte on: a side's sixteen
+// bytes are two aligned units shifted into one (the upper unit stays for the next step, so a step is one load a side), their
+// delimiters -- ' ', '\t', '\n', the text's end -- one 16-bit mask (frame_masks.h), the bytes that differ between the sides another.
+// The walk keeps per side where its first delimiter is and the two bytes in front of it (a "/1" or "/2"), and for both where the first
+// event is: a byte that differs or a side's delimiter.  The rule (slimfastq_amd.h) is then arithmetic on those five numbers.  The
+// line's first byte is no part of a name: it counts as a delimiter only where it is a line end, and as equal otherwise.
+constexpr u32 NAMES_MAX_WG = 4096;
+struct NameSide {
+    u64 line, left;         // the address of the line's first byte, the text's bytes from there on (at least one)
+    uint4 carry;            // the aligned unit behind the one the last step began in
+    u32 prev;               // the last four bytes of the last step
+    u64 len; u32 tail; bool done;      // the first delimiter's offset in the line, the two bytes in front of it
+};
+// the sixteen bytes at pos of the line -> X, the mask of its delimiters -> the result.  Loads are aligned units that hold a byte of the text.
+__device__ __forceinline__ u32 name_step(NameSide& s, u64 pos, u32 (&X)[4]) {
+    const u64 S = s.line + pos, rem = s.left - pos;            // rem > 0: a text's end is a delimiter, and the walk ends at one
+    const u32 sh = (u32)S & 15u;
+    const u8* unit = reinterpret_cast<const u8*>(S - sh);
+    uint4 L0 = s.carry, L1 = make_uint4(0, 0, 0, 0);
+    if (!pos || !sh) L0 = *reinterpret_cast<const uint4*>(unit);
+    if (sh && rem > 16 - sh) L1 = *reinterpret_cast<const uint4*>(unit + 16);
+    s.carry = L1;
+    const u32 W[8] = { L0.x, L0.y, L0.z, L0.w, L1.x, L1.y, L1.z, L1.w };
+    const u32 q = sh >> 2, r8 = (sh & 3u) * 8;
+    u32 Y[5];
+#pragma unroll
+    for (u32 i = 0; i < 5; i++) Y[i] = q == 0 ? W[i] : q == 1 ? W[i + 1] : q == 2 ? W[i + 2] : W[i + 3];
+#pragma unroll
+    for (u32 i = 0; i < 4; i++) X[i] = (u32)((((u64)Y[i + 1] << 32) | Y[i]) >> r8);
+    if (!pos && (X[0] & 0xFFu) != 0x0Au) X[0] = (X[0] & ~0xFFu) | 0x40u;       // the line's first byte: '@' to both sides
+    u32 f[4];
+#pragma unroll
+    for (u32 i = 0; i < 4; i++) {
+        const TextDword d(X[i]);
+        f[i] = ne_flags(d, 0x0a0a0a0au) & ne_flags(d, 0x20202020u) & ne_flags(d, 0x09090909u);      // 0x80: no delimiter
+    }
+    const u32 valid = rem < 16 ? (u32)rem : 16u;
+    return (~gather16<7>(f[0], f[1], f[2], f[3]) | (0xFFFFu << valid)) & 0xFFFFu;
+}
+// bytes j - 2 and j - 1 of a step (j < 16), prev: the four bytes in front of it
+__device__ __forceinline__ u32 two_before(u32 prev, const u32 (&X)[4], u32 j) {
+    const u32 q = (j + 2) >> 2, r8 = ((j + 2) & 3u) * 8;
+    const u32 lo = q == 0 ? prev : q == 1 ? X[0] : q == 2 ? X[1] : q == 3 ? X[2] : X[3];
+    const u32 hi = q == 0 ? X[0] : q == 1 ? X[1] : q == 2 ? X[2] : X[3];     // (q == 4: both bytes lie in lo)
+    return (u32)((((u64)hi << 32) | lo) >> r8) & 0xFFFFu;
+}
+__device__ __forceinline__ void name_end(NameSide& s, u64 pos, u32 dm, const u32 (&X)[4]) {
+    if (!s.done && dm) {
+        const u32 j = (u32)__ffs((int)dm) - 1;
+        s.len = pos + j; s.tail = two_before(s.prev, X, j); s.done = true;
+    }
+    s.prev = X[3];
+}
+// a name's length from its line's: without the first byte, without a "/1" or "/2" at its end
+__device__ __forceinline__ u64 name_bytes(const NameSide& s) {
+    const u64 l = s.len ? s.len - 1 : 0;
+    return l >= 2 && (s.tail == 0x312Fu || s.tail == 0x322Fu) ? l - 2 : l;
+}
+__device__ __forceinline__ bool names_differ(u64 la, u64 na, u64 lb, u64 nb) {
+    NameSide A{ la, na, make_uint4(0, 0, 0, 0), 0, 0, 0, false }, B{ lb, nb, make_uint4(0, 0, 0, 0), 0, 0, 0, false };
+    u64 first = 0; bool seen = false;                          // the first event's offset in the lines
+    for (u64 pos = 0; !(A.done && B.done); pos += 16) {
+        u32 XA[4] = { 0, 0, 0, 0 }, XB[4] = { 0, 0, 0, 0 }, dA = 0, dB = 0;
+        if (!A.done) dA = name_step(A, pos, XA);
+        if (!B.done) dB = name_step(B, pos, XB);
+        if (!seen) {                                           // (neither side is done yet: a side's end is an event)
+            const u32 ev = dA | dB | gather16<7>(nonzero_bytes(XA[0] ^ XB[0]), nonzero_bytes(XA[1] ^ XB[1]), nonzero_bytes(XA[2] ^ XB[2]), nonzero_bytes(XA[3] ^ XB[3]));
+            if (ev) { first = pos + (u32)__ffs((int)ev) - 1; seen = true; }
+        }
+        name_end(A, pos, dA, XA);
+        name_end(B, pos, dB, XB);
+    }
+    const u64 ea = name_bytes(A), eb = name_bytes(B), same = first ? first - 1 : 0;      // name bytes in front of the first event
+    return ea != eb || same < ea;
+}
+// Pair i: the lines at sa[i * stride] of text ta and sb[i * stride] of tb (addresses; na, nb: the texts' bytes).  A wavefront takes
+// 64 pairs at a time; what it found goes out in one atomic add and one atomic min per wavefront.
+__global__ __launch_bounds__(256) void k_pair_names(PairInfo* info, const u64* __restrict__ sa, const u64* __restrict__ sb, u32 stride,
+                                                    u64 ta, u64 na, u64 tb, u64 nb) {
+    if (info->status) return;
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u64 P = info->pieces;
+    u64 count = 0, first = ~0ull;
+    for (u64 i0 = ((u64)blockIdx.x * 4 + wave) * 64; i0 < P; i0 += (u64)gridDim.x * 256) {
+        const u64 i = i0 + lane;
+        bool bad = false;
+        if (i < P) {
+            const u64 oa = sa[i * stride], ob = sb[i * stride];
+            bad = names_differ(ta + oa, na - oa, tb + ob, nb - ob);
+        }
+        const u64 m = __ballot(bad);
+        if (m) { count += (u64)__popcll(m); if (first == ~0ull) first = i0 + (u32)__ffsll((long long)m) - 1; }
+    }
+    if (count && !lane) {
+        atomicAdd(reinterpret_cast<unsigned long long*>(&info->mm_count), (unsigned long long)count);
+        atomicMin(reinterpret_cast<unsigned long long*>(&info->mm_first), (unsigned long long)first);
+    }
+}
+// behind it (the kernel boundary orders them): where the first such pair's lines are
+__global__ void k_pair_names_first(PairInfo* info, const u64* __restrict__ sa, const u64* __restrict__ sb, u32 stride) {
+    if (threadIdx.x || blockIdx.x || info->status || !info->mm_count) return;
+    const u64 i = info->mm_first;
+    info->mm_off[0] = sa[i * stride]; info->mm_off[1] = sb[i * stride];
+}
+
 void starts_of(const PairText& t, u64 cap, hipStream_t st) {
     const QmapScratch q = qmap_scratch(t.d, t.n);
     const u32 mis = (u32)((uintptr_t)t.d & 15);
@@ -226,27 +355,47 @@ CheckText check_of(const PairText& t) {
     const QmapScratch q = qmap_scratch(t.d, t.n);
     return CheckText{ reinterpret_cast<const u64*>(t.scratch + q.before_off) + q.nspans, t.d + t.n - 1, t.n, t.starts };
 }
+// J.nout: at least the output's bytes
 void launch_copy(const PairJob& J, u8* out, PairInfo* info, hipStream_t st) {
     const u32 mis = (u32)((uintptr_t)out & 15);
-    const u64 nspans = (mis + J.nout + SPAN - 1) / SPAN, tiles = (nspans + 3) / 4;
+    const u64 nspans = (mis + J.nout + SPAN - 1) / SPAN, tiles = nspans ? (nspans + 3) / 4 : 1;
     hipLaunchKernelGGL(k_pair_copy, dim3((u32)(tiles < MAX_WG ? tiles : MAX_WG)), dim3(256), 0, st, J, info, out - mis, mis, nspans);
 }
+// pairs: at least the pairs there are; sb = sa + 1 and stride 2 for the records of one text
+void launch_names(const u64* sa, const u64* sb, u32 stride, const PairText& a, const PairText& b, u64 pairs, PairInfo* info, hipStream_t st) {
+    const u64 wg = (pairs + 255) / 256;
+    hipLaunchKernelGGL(k_pair_names, dim3((u32)(wg < NAMES_MAX_WG ? (wg ? wg : 1) : NAMES_MAX_WG)), dim3(256), 0, st, info, sa, sb, stride,
+                       (u64)(uintptr_t)a.d, a.n, (u64)(uintptr_t)b.d, b.n);
+    hipLaunchKernelGGL(k_pair_names_first, dim3(1), dim3(64), 0, st, info, sa, sb, stride);
+}
+const PairWindow NO_WINDOW{ 0, 0, 0, 0, 0 };
 
 }  // namespace
 
-void launch_pair_interleave(const PairText& a, const PairText& b, u64 cap, u8* out, PairInfo* info, hipStream_t st) {
+void launch_pair_interleave(const PairText& a, const PairText& b, u64 cap, bool names, u8* out, PairInfo* info, hipStream_t st) {
     starts_of(a, cap, st);
     starts_of(b, cap, st);
-    hipLaunchKernelGGL(k_pair_check, dim3(1), dim3(64), 0, st, info, 0u, check_of(a), check_of(b), cap);
+    hipLaunchKernelGGL(k_pair_check, dim3(1), dim3(64), 0, st, info, 0u, check_of(a), check_of(b), cap, NO_WINDOW);
+    if (names) launch_names(a.starts, b.starts, 1, a, b, cap, info, st);
     hipLaunchKernelGGL(k_pair_lens, dim3((u32)((cap + 255) / 256)), dim3(256), 0, st, info, (const u64*)a.starts, (const u64*)b.starts, (u32*)nullptr, (u64)0);
-    launch_copy(PairJob{ 0u, a.starts, b.starts, (u64)(uintptr_t)a.d, (u64)(uintptr_t)b.d, a.n + b.n }, out, info, st);
+    launch_copy(PairJob{ 0u, a.starts, b.starts, (u64)(uintptr_t)a.d, (u64)(uintptr_t)b.d, a.n + b.n, 0 }, out, info, st);
 }
 
-void launch_pair_split(const PairText& t, u64 cap, u32* lens, u64* offa, u64* scan_tmp, u8* out, PairInfo* info, hipStream_t st) {
-    const u64 nlens = cap / 2 + 1;
+void launch_pair_split(const PairText& t, u64 cap, const PairWindow& win, u32* lens, u64* offa, u64* scan_tmp, u8* out, PairInfo* info, hipStream_t st) {
+    // a window: the lengths and their scan cover its even records alone, the copy's grid what the output can hold of the text
+    const u64 all = cap / 2 + 1, nlens = win.on && win.nr / 2 + 1 < all ? win.nr / 2 + 1 : all;
+    const u64* s = t.starts + (win.on && win.r0 <= cap ? win.r0 : 0);         // (behind cap: the check refuses, nothing reads it)
     starts_of(t, cap, st);
-    hipLaunchKernelGGL(k_pair_check, dim3(1), dim3(64), 0, st, info, 1u, check_of(t), check_of(t), cap);
-    hipLaunchKernelGGL(k_pair_lens, dim3((u32)((nlens + 255) / 256)), dim3(256), 0, st, info, (const u64*)t.starts, (const u64*)nullptr, lens, nlens);
+    hipLaunchKernelGGL(k_pair_check, dim3(1), dim3(64), 0, st, info, 1u, check_of(t), check_of(t), cap, win);
+    hipLaunchKernelGGL(k_pair_lens, dim3((u32)((nlens + 255) / 256)), dim3(256), 0, st, info, s, (const u64*)nullptr, lens, nlens);
     launch_scan_u32(lens, offa, nlens, scan_tmp, st);
-    launch_copy(PairJob{ 1u, t.starts, offa, (u64)(uintptr_t)t.d, 0, t.n }, out, info, st);
+    launch_copy(PairJob{ 1u, s, offa, (u64)(uintptr_t)t.d, 0, win.on && win.out_cap < t.n ? win.out_cap : t.n, 0 }, out, info, st);
+}
+
+void launch_pair_names(const PairText& a, const PairText& b, u64 cap, PairInfo* info, hipStream_t st) {
+    starts_of(a, cap, st);
+    if (b.d) starts_of(b, cap, st);
+    hipLaunchKernelGGL(k_pair_check, dim3(1), dim3(64), 0, st, info, b.d ? 0u : 1u, check_of(a), check_of(b.d ? b : a), cap, NO_WINDOW);
+    if (b.d) launch_names(a.starts, b.starts, 1, a, b, cap, info, st);
+    else launch_names(a.starts, a.starts + 1, 2, a, a, cap / 2 + 1, info, st);
 }
