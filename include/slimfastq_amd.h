@@ -448,6 +448,42 @@ int sfq_decode_pair_range_host(sfq_ctx* ctx, const sfq_params* params, const sfq
                                uint64_t first_pair, uint64_t n_pairs,
                                uint8_t* h_out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* split, sfq_result* result);
 
+/* ---- picked lines ---------------------------------------------------------------------------------------------------------
+ * What a consumer of a decoded FASTQ often reads is part of it: FASTA, the read names, the base lines or the quality lines.  The
+ * pass (pick.hip) picks those lines on the device, text to text like the paired files' passes, behind a decode's assembly; no
+ * stream, coder or block format knows of it.  A line is the bytes up to and including a '\n'; a text without a final '\n' ends in
+ * a line all the same, whose piece then lacks the '\n' and so does the result.  A record is four lines; '\r' is a byte like any
+ * other.  Every record contributes ONE contiguous piece of the text, and the result is the pieces in record order with nothing
+ * between them.  Every piece holds at least one byte, so the result is never larger than the text: out_cap = n always suffices. */
+#define SFQ_PICK_FASTA 1   /* lines 1 and 2 of every record; the first byte of line 1 becomes '>' */
+#define SFQ_PICK_NAMES 2   /* line 1 without its first byte (the '@') */
+#define SFQ_PICK_BASES 3   /* line 2 */
+#define SFQ_PICK_QUALS 4   /* line 4 */
+/* Records [first_record, first_record + n_records) of d_text, picked; n_records = UINT64_MAX: to the text's last record.
+ * *out_bytes = the bytes of the result (on SFQ_E_OVERFLOW: the size needed), *n_picked (may be NULL) = records picked.
+ * SFQ_E_ARG: a null pointer, n == 0, an unknown selection, n_records == 0, a range that ends behind the last record (with UINT64_MAX:
+ * a first_record that is no record of the text).  SFQ_E_FORMAT: a text whose lines are no multiple of four; under SFQ_PICK_FASTA and
+ * SFQ_PICK_NAMES a record IN THE RANGE whose first byte is not '@' (sfq_last_error names the smallest such record and its byte
+ * offset; SFQ_PICK_BASES and SFQ_PICK_QUALS do not look at that byte).  SFQ_E_OVERFLOW: a result larger than out_cap.
+ * SFQ_E_UNSUPPORTED: a record whose piece holds 4 GiB or more.  Every refusal is decided on the device before the copy: a refused call
+ * writes nothing to d_out.  A call that succeeds writes d_out[0, *out_bytes) and nothing else: the bytes behind the result stay as
+ * they were, inside out_cap too.  d_out must not overlap d_text.  The call runs on the context's stream and synchronises once.
+ * Like sfq_crc32 it may read the whole aligned 16-byte units of the text's first and last byte. */
+int sfq_pick_lines(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, int what, uint64_t first_record, uint64_t n_records,
+                   uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* n_picked);
+/* what != 0: sfq_decode_blocks_host, sfq_decode_block_range_host and sfq_decode_pair_range_host hand back the picked lines of
+ * the text they decoded instead of the text; 0: off (default).  SFQ_E_ARG for an unknown selection (the setting stays).
+ * The pick is the call's last pass: behind the checksum pass (the CRCs, installed ones included, stay those of the decoded FASTQ
+ * text) and behind the pair split or the pair window's cut-and-split, where either runs.  A split layout is picked as one text --
+ * first mates, then second mates, both whole records -- and the boundary that sfq_get_pair_split and sfq_decode_pair_range_host's
+ * *split report is then the boundary IN THE PICKED RESULT.  out_cap keeps sizing the DECODED text; only the picked bytes cross
+ * the link, and *out_bytes is their count.  Costs one more device buffer of the text's size, held while the switch is on.  The
+ * device-pointer decode entries are not affected: call sfq_pick_lines on their output.  Default off: nothing is launched,
+ * allocated or copied that is not today. */
+int sfq_ctx_set_pick(sfq_ctx* ctx, int what);
+/* 1: the last decode call picked; *what, *text_bytes (the decoded text's size before the pick), *n_records; 0: it did not (all zeroed) */
+int sfq_get_pick(const sfq_ctx* ctx, int* what, uint64_t* text_bytes, uint64_t* n_records);
+
 /* ---- the ".sfq" container (host only) ----------------------------------------------------------
  * Replaces FilerSave + the info page (filer.cpp:217-242, config.cpp:334-347) for hosts that assemble an archive
  * themselves: info_text is the info page ("key=value\n" lines), then n_streams named byte streams (names of at most

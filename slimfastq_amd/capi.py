@@ -20,6 +20,9 @@ TABLES_ADAPTIVE, TABLES_FROZEN, TABLES_AUTO = 0, 1, 2
 LDS_ROWS_NONE = 0xFFFFFFFF
 QMAP_ILLUMINA8, QMAP_NOVASEQ4 = 1, 2
 QMAP_PRESETS = {"illumina8": QMAP_ILLUMINA8, "novaseq4": QMAP_NOVASEQ4}
+PICK_FASTA, PICK_NAMES, PICK_BASES, PICK_QUALS = 1, 2, 3, 4
+PICKS = {"fasta": PICK_FASTA, "names": PICK_NAMES, "bases": PICK_BASES, "quals": PICK_QUALS}
+PICK_TO_END = 0xFFFFFFFFFFFFFFFF
 
 EXPORTS = [
     "sfq_stream_name", "sfq_ctx_create", "sfq_ctx_destroy", "sfq_last_error", "sfq_ctx_set_table_budget",
@@ -34,7 +37,7 @@ EXPORTS = [
     "sfq_quality_map_preset", "sfq_quality_map_check", "sfq_map_qualities", "sfq_ctx_set_quality_map", "sfq_get_quality_map_changed",
     "sfq_interleave", "sfq_split_pairs", "sfq_encode_pairs_host", "sfq_ctx_set_pair_split", "sfq_get_pair_split",
     "sfq_split_pairs_range", "sfq_check_mates", "sfq_ctx_set_mate_check", "sfq_get_mate_report", "sfq_pair_window_blocks",
-    "sfq_decode_pair_range_host",
+    "sfq_decode_pair_range_host", "sfq_pick_lines", "sfq_ctx_set_pick", "sfq_get_pick",
 ]
 
 
@@ -215,6 +218,9 @@ def lib():
         L.sfq_pair_window_blocks.argtypes = [C.POINTER(BlockInfo), C.c_uint32, u64, u64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.sfq_decode_pair_range_host.argtypes = [vp, C.POINTER(Params), C.POINTER(BlockInfo), C.c_uint32, u8p, u64, u8p, u64, C.POINTER(u64),
                                                  u64, u64, u8p, u64, u64p, u64p, C.POINTER(Result)]
+        L.sfq_pick_lines.argtypes = [vp, vp, u64, C.c_int, u64, u64, vp, u64, u64p, u64p]
+        L.sfq_ctx_set_pick.argtypes = [vp, C.c_int]
+        L.sfq_get_pick.argtypes = [vp, C.POINTER(C.c_int), u64p, u64p]
         _lib = L
     return _lib
 
@@ -492,6 +498,33 @@ class Context:
         if rc < 0:
             self._check(rc)
         return (int(first.value), int(pairs.value)) if rc == 1 else None
+
+    def pick_lines(self, d_text, nbytes, what, d_out, out_cap, first_record=0, n_records=None):
+        """Of records [first_record, first_record + n_records) (None: to the last) of the FASTQ text in the device buffer at d_text
+        the lines `what` selects (PICK_*), one behind the other into the one at d_out (sfq_pick_lines); returns (bytes written,
+        records picked).  An SfqError of code E_OVERFLOW carries the size needed as .needed."""
+        n, recs = C.c_uint64(), C.c_uint64()
+        rc = lib().sfq_pick_lines(self._h, C.c_void_p(d_text), int(nbytes), int(what), int(first_record),
+                                  PICK_TO_END if n_records is None else int(n_records), C.c_void_p(d_out), int(out_cap), C.byref(n), C.byref(recs))
+        try:
+            self._check(rc)
+        except SfqError as e:
+            e.needed = int(n.value)
+            raise
+        return int(n.value), int(recs.value)
+
+    def set_pick(self, what=0):
+        """PICK_*: decode_host, decode_range_host and decode_pair_range_host return the picked lines of the text they decoded instead
+        of the text (get_pick() says of what); 0: off."""
+        self._check(lib().sfq_ctx_set_pick(self._h, int(what)))
+
+    def get_pick(self):
+        """(selection, the decoded text's bytes, records) of the last decode call; None where it did not pick."""
+        what, n, recs = C.c_int(), C.c_uint64(), C.c_uint64()
+        rc = lib().sfq_get_pick(self._h, C.byref(what), C.byref(n), C.byref(recs))
+        if rc < 0:
+            self._check(rc)
+        return (int(what.value), int(n.value), int(recs.value)) if rc == 1 else None
 
     def set_block_checksums(self, crcs):
         """The expected CRCs of the next decode call's blocks (consumed by it)."""

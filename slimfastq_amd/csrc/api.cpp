@@ -198,6 +198,10 @@ struct sfq_ctx {
     bool pair_split_done = false; u64 pair_first = 0, pair_n = 0;     // the last decode call's
     bool mate_check_on = false;                       // sfq_ctx_set_mate_check
     bool mate_report_valid = false; sfq_mate_report mate_report{};    // the last sfq_encode_pairs_host's
+    // picked lines (pick.hip): the pass works in pair_work and reports through pair_pin; nothing of this exists until the switch is on
+    int pick_what = 0;                                // sfq_ctx_set_pick
+    DevBuf pick_out;                                  // the picked lines of a decoded text (while the switch is on)
+    int pick_done = 0; u64 pick_text = 0, pick_recs = 0;      // the last decode call's: its selection, the text's bytes, the records
 };
 
 namespace {
@@ -960,7 +964,7 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
         &ctx->oflags, &ctx->okbytes, &ctx->ofpos, &ctx->okoff, &ctx->ofilt, &ctx->orecmap, &ctx->olist, &ctx->line_off_o, &ctx->ono, &ctx->opiece,
         &ctx->otxt[0], &ctx->otxt[1], &ctx->otxt[2], &ctx->osize_all, &ctx->oroff_all, &ctx->oroff_k, &ctx->ocnt,
         &ctx->crc_tab, &ctx->crc_tiles, &ctx->crc_grps, &ctx->crc_bounds, &ctx->crc_out, &ctx->stats_acc, &ctx->qmap_dev,
-        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out };
+        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out, &ctx->pick_out };
     for (DevBuf* b : all) release(*b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->pin2) (void)hipHostFree(ctx->pin2);
@@ -2133,6 +2137,88 @@ int sfq_get_pair_split(const sfq_ctx* ctx, uint64_t* first_bytes, uint64_t* n_pa
     return ctx->pair_split_done ? 1 : 0;
 }
 
+// ---- picked lines (pick.hip) ------------------------------------------------------------------------------------------------------
+// One pass on the context's stream, one synchronise, in pair_run's working buffers and with its sizing: the arrays are laid out for
+// one record per 64 bytes (or what an earlier call learned), and only a text with more records runs twice.  mark: the piece (counted
+// from first_record) whose destination got->mark_off reports.
+static_assert(PICK_FASTA == SFQ_PICK_FASTA && PICK_NAMES == SFQ_PICK_NAMES && PICK_BASES == SFQ_PICK_BASES && PICK_QUALS == SFQ_PICK_QUALS, "pick.hip's selections");
+static int pick_run(sfq_ctx* ctx, const u8* text, u64 n, int what, u64 first_record, u64 n_records, u8* out, u64 out_cap, u64 mark, PickInfo* got) {
+    int rc;
+    if ((rc = reserve_pinned_buf(ctx, ctx->pair_pin, ctx->pair_pin_cap, std::max(sizeof(PairInfo), sizeof(PickInfo))))) return rc;
+    for (int attempt = 0; ; attempt++) {
+        const u64 cap = std::max<u64>(ctx->pair_cap, n / 64 + 1024);
+        const u64 nlens = std::min(n_records, cap);
+        auto up = [](u64 v) { return (v + 15) & ~15ull; };
+        u64 at = up(std::max(sizeof(PairInfo), sizeof(PickInfo)));
+        const u64 sc = at; at += up(qmap_scratch(text, n).bytes);
+        const u64 from = at; at += up((cap + 1) * 8);
+        const u64 to = at; at += up((cap + 1) * 8);
+        const u64 lens = at; at += up(nlens * 4);
+        const u64 dst = at; at += up((nlens + 1) * 8);
+        const u64 tmp = at; at += up((nlens / 1024 + 2) * 8);
+        if ((rc = reserve(ctx, ctx->pair_work, (size_t)at))) return rc;
+        u8* w = (u8*)ctx->pair_work.p;
+        PickInfo* info = (PickInfo*)w;
+        HIPC(hipMemsetAsync(info, 0, sizeof(PickInfo), ctx->st));
+        const PairText t{ text, n, w + sc, (u64*)(w + from) };
+        const PickJob job{ (u32)what, 0, first_record, n_records, out_cap, mark };
+        launch_pick(t, (u64*)(w + to), cap, job, (u32*)(w + lens), (u64*)(w + dst), (u64*)(w + tmp), nlens, out, info, ctx->st);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(ctx->pair_pin, info, sizeof(PickInfo), hipMemcpyDeviceToHost, ctx->st));
+        HIPC(hipStreamSynchronize(ctx->st));
+        memcpy(got, ctx->pair_pin, sizeof(PickInfo));
+        if (got->status != PICK_CAP) break;
+        if (attempt) return fail(ctx, SFQ_E_HIP, "picked lines: the records did not fit twice");
+        ctx->pair_cap = got->recs;
+    }
+    switch (got->status) {
+    case PICK_OK: return SFQ_OK;
+    case PICK_LINES: return fail(ctx, SFQ_E_FORMAT, "picked lines: the text holds %llu lines, not a multiple of four", (unsigned long long)got->lines);
+    case PICK_RANGE:
+        if (n_records == ~0ull) return fail(ctx, SFQ_E_ARG, "picked lines: record %llu lies behind the text's %llu records", (unsigned long long)first_record, (unsigned long long)got->recs);
+        return fail(ctx, SFQ_E_ARG, "picked lines: records %llu..+%llu end behind the text's %llu records", (unsigned long long)first_record, (unsigned long long)n_records, (unsigned long long)got->recs);
+    case PICK_LONG: return fail(ctx, SFQ_E_UNSUPPORTED, "picked lines: a record whose picked lines hold 4 GiB or more");
+    case PICK_AT: return fail(ctx, SFQ_E_FORMAT, "picked lines: record %llu (at byte %llu) does not begin with '@'", (unsigned long long)got->bad_first, (unsigned long long)got->bad_off);
+    case PICK_ROOM: return fail(ctx, SFQ_E_OVERFLOW, "picked lines: the result needs %llu bytes", (unsigned long long)got->nout);
+    default: return fail(ctx, SFQ_E_HIP, "picked lines: status %u", got->status);
+    }
+}
+static bool pick_known(int what) { return what >= SFQ_PICK_FASTA && what <= SFQ_PICK_QUALS; }
+int sfq_pick_lines(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, int what, uint64_t first_record, uint64_t n_records,
+                   uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* n_picked) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!d_text || !d_out || !out_bytes) return fail(ctx, SFQ_E_ARG, "null argument");
+    *out_bytes = 0;
+    if (n_picked) *n_picked = 0;
+    if (!n) return fail(ctx, SFQ_E_ARG, "picked lines: an empty text");
+    if (!pick_known(what)) return fail(ctx, SFQ_E_ARG, "picked lines: selection %d is none of SFQ_PICK_*", what);
+    if (!n_records) return fail(ctx, SFQ_E_ARG, "picked lines: no records asked for");
+    HIPC(hipSetDevice(ctx->dev));
+    Settle settle(ctx);
+    PickInfo got;
+    const int rc = pick_run(ctx, d_text, n, what, first_record, n_records, d_out, out_cap, 0, &got);
+    if (rc == SFQ_E_OVERFLOW) *out_bytes = got.nout;
+    if (rc) return rc;
+    *out_bytes = got.nout;
+    if (n_picked) *n_picked = got.pieces;
+    settle.ok = true;
+    return SFQ_OK;
+}
+int sfq_ctx_set_pick(sfq_ctx* ctx, int what) {
+    if (!ctx) return SFQ_E_ARG;
+    if (what && !pick_known(what)) return fail(ctx, SFQ_E_ARG, "picked lines: selection %d is none of SFQ_PICK_*", what);
+    ctx->pick_what = what;
+    if (!what) release(ctx->pick_out);
+    return SFQ_OK;
+}
+int sfq_get_pick(const sfq_ctx* ctx, int* what, uint64_t* text_bytes, uint64_t* n_records) {
+    if (!ctx) return SFQ_E_ARG;
+    if (what) *what = ctx->pick_done;
+    if (text_bytes) *text_bytes = ctx->pick_done ? ctx->pick_text : 0;
+    if (n_records) *n_records = ctx->pick_done ? ctx->pick_recs : 0;
+    return ctx->pick_done ? 1 : 0;
+}
+
 int sfq_get_block_index(sfq_ctx* ctx, sfq_block_info* h_blocks, uint32_t cap) {
     if (!ctx || !h_blocks) return SFQ_E_ARG;
     if (cap < ctx->index.size()) return fail(ctx, SFQ_E_ARG, "index has %zu blocks", ctx->index.size());
@@ -2213,7 +2299,7 @@ static int decode_device(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_inf
     Settle settle(ctx);
     drop_encode_blobs(ctx);                             // whatever an encode left behind is not this archive's
     ctx->crcs.clear(); ctx->text_crc = 0;
-    ctx->pair_split_done = false;
+    ctx->pair_split_done = false; ctx->pick_done = 0;
     if (w.ranged && ctx->pair_split_on && !w.pairs)
         return fail(ctx, SFQ_E_UNSUPPORTED, "a window of blocks may start at a second mate and is not split: sfq_ctx_set_pair_split(ctx, 0) comes first");
     const bool check = ex.set;
@@ -3019,6 +3105,19 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
         settle.ok = true;
         d_text = (const u8*)ctx->pair_out.p;
         ctx->pair_split_done = true; ctx->pair_first = got.split; ctx->pair_n = got.recs[0] >> 1;
+    }
+    if (ctx->pick_what) {                                  // the last pass: of the text as it stands, split or not, the picked lines alone
+        if (!*out_bytes) return fail(ctx, SFQ_E_FORMAT, "picked lines: an empty text");
+        if ((rc = reserve(ctx, ctx->pick_out, (size_t)*out_bytes + 16))) return rc;
+        Settle settle(ctx);
+        PickInfo got;
+        // a split layout is whole records, first mates then second: the boundary moves to where record pair_n's piece went
+        if ((rc = pick_run(ctx, d_text, *out_bytes, ctx->pick_what, 0, ~0ull, (u8*)ctx->pick_out.p, *out_bytes, ctx->pair_split_done ? ctx->pair_n : 0, &got))) return rc;
+        settle.ok = true;
+        ctx->pick_done = ctx->pick_what; ctx->pick_text = *out_bytes; ctx->pick_recs = got.pieces;
+        if (ctx->pair_split_done) { ctx->pair_first = got.mark_off; if (split) *split = got.mark_off; }
+        d_text = (const u8*)ctx->pick_out.p;
+        *out_bytes = got.nout;
     }
     HIPC(hipMemcpyAsync(h_out, d_text, (size_t)*out_bytes, hipMemcpyDeviceToHost, ctx->st));
     HIPC(hipStreamSynchronize(ctx->st));

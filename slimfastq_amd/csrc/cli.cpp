@@ -107,6 +107,9 @@ static void usage() {
            "-W first:count   : with -d and -p: write pairs first .. first+count-1 only (numbered from 0 over the whole archive; count is\n"
            "                   clipped at the end): first mates to -u, second mates to -p; only the blocks that hold them are decoded,\n"
            "                   and they are cut to the pairs and split on the GPU; needs -d, -u and -p, not with -R or -b\n"
+           "-x fasta|names|bases|quals : with -d: write those lines of every record only, picked on the GPU before the text comes back --\n"
+           "                   FASTA (lines 1 and 2, '>' for '@'), the names (line 1 without its '@'), the base lines or the quality lines;\n"
+           "                   goes with -R, -p, -W, -K and -b (-p and -W write each mate's lines to its file)\n"
            "-M               : with -p on a compress run: compare the names of every pair of mates on the GPU before it is coded (the\n"
            "                   header's first word, without a final /1 or /2); a pair that differs ends the run with its index and both\n"
            "                   names, and no archive is written\n"
@@ -145,6 +148,7 @@ struct Opts {
     std::string pair;                                                  // -p: the second file of a pair
     bool window = false; uint64_t w_first = 0, w_count = 0;            // -W first:count (pairs)
     bool mates = false;                                                // -M
+    int pick = 0; std::string pick_name;                               // -x: SFQ_PICK_* (0 = none, -1 = no such word) and the word
 };
 // "FIRST:COUNT", both decimal, COUNT > 0
 static bool parse_range(const char* t, uint64_t& first, uint64_t& count) {
@@ -169,10 +173,10 @@ static std::string mate_name(const uint8_t* t, size_t n, uint64_t off) {
     for (char& c : s) if ((unsigned char)c < 32 || (unsigned char)c > 126) c = '?';
     return s;
 }
-// where the first `skip` records (four lines each) of a text end, or n where it has fewer
-static size_t records_end(const uint8_t* t, size_t n, uint64_t skip) {
+// where the first `skip` records (four lines each; of picked lines, -x: two or one) of a text end, or n where it has fewer
+static size_t records_end(const uint8_t* t, size_t n, uint64_t skip, uint64_t lines = 4) {
     size_t at = 0;
-    for (uint64_t l = 0; l < 4 * skip && at < n; l++) {
+    for (uint64_t l = 0; l < lines * skip && at < n; l++) {
         const void* q = memchr(t + at, '\n', n - at);
         at = q ? (size_t)((const uint8_t*)q - t) + 1 : n;
     }
@@ -711,6 +715,8 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     // (a -b worker keeps its context from job to job: a -K encode before this job left the pass on; installed checksums run it)
     if (sfq_ctx_set_checksums(ctx, 0)) croak("%s", sfq_last_error(ctx));
     if (sfq_ctx_set_pair_split(ctx, paired ? 1 : 0)) croak("%s", sfq_last_error(ctx));
+    if (sfq_ctx_set_pick(ctx, o.pick)) croak("%s", sfq_last_error(ctx));
+    const uint64_t rec_lines = !o.pick ? 4 : o.pick == SFQ_PICK_FASTA ? 2 : 1;      // the lines of a record in what a call hands back
     // walk the segments: each one's blocks, its slice of every stream (streams are segment-major), its prior
     size_t b0 = 0, pri_off = 0, chn_off = 0, rpr_off = 0;
     uint64_t spos[SFQ_NSTREAMS] = {0};
@@ -812,11 +818,11 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         if (rc) croak("%s", sfq_last_error(ctx));
         tick("sfq_decode_blocks_host");
         const bool in_out = dst == out.p;                              // (not a page-locked buffer: written before the next segment reuses it)
-        if (o.range) {                                                 // the window's first and last block, cut to records: four lines each
+        if (o.range) {                                                 // the window's first and last block, cut to records: rec_lines lines each
             const uint64_t wrec0 = rec0 + (uint64_t)w0 * sb[0].n_records;
             const uint64_t lo = std::max(r_lo, wrec0), hi = std::min(r_hi, wrec0 + res.n_records);
-            const size_t from = records_end(dst, (size_t)got, lo - wrec0);
-            const size_t to = from + records_end(dst + from, (size_t)got - from, hi - lo);
+            const size_t from = records_end(dst, (size_t)got, lo - wrec0, rec_lines);
+            const size_t to = from + records_end(dst + from, (size_t)got - from, hi - lo, rec_lines);
             dst += from; got = to - from;
         }
         // -p: the call handed back the first mates, then (from `first` on) the second mates
@@ -846,7 +852,7 @@ int main(int argc, char** argv) {
     Opts o;
     bool statistics = false;
     if (argc == 1) usage();
-    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKYM1234u:f:l:B:g:S:T:C:t:R:Q:p:W:")) != -1;) {
+    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKYM1234u:f:l:B:g:S:T:C:t:R:Q:p:W:x:")) != -1;) {
         switch (opt) {
         case 'u': g_usr = optarg; break;
         case 'f': fil = optarg; break;
@@ -880,6 +886,11 @@ int main(int argc, char** argv) {
             o.window = true;
             break;
         case 'M': o.mates = true; break;
+        case 'x':
+            o.pick_name = optarg;
+            o.pick = o.pick_name == "fasta" ? SFQ_PICK_FASTA : o.pick_name == "names" ? SFQ_PICK_NAMES : o.pick_name == "bases" ? SFQ_PICK_BASES :
+                     o.pick_name == "quals" ? SFQ_PICK_QUALS : -1;
+            break;
         case 'C': o.chain_reads = strtol(optarg, 0, 0); break;
         case 't': o.io_threads = std::min(64, std::max(1, atoi(optarg))); break;
         case 'v': printf("Version %s\nInternal format version=%u (block format %u)\n", kUserVersion, kInternalVersion, kBlockVersion); exit(0);
@@ -916,6 +927,15 @@ int main(int argc, char** argv) {
     if (o.mates && (!g_encode || o.pair.empty())) {
         fprintf(stderr, "slimfastq: -M (the mates' names are compared) goes with -p on a compress run: %s\n",
                 !g_encode ? "a decode writes what the archive holds" : "it compares the records of -u with those of -p");
+        return 1;
+    }
+
+    if (o.pick < 0) {
+        fprintf(stderr, "slimfastq: -x %s: no such selection (fasta, names, bases or quals)\n", o.pick_name.c_str());
+        return 1;
+    }
+    if (o.pick && (g_encode || statistics)) {
+        fprintf(stderr, "slimfastq: -x (picked lines) goes with -d: it picks the lines a decode writes%s\n", statistics ? "; -s writes no text" : "");
         return 1;
     }
 

@@ -1,5 +1,5 @@
 // dev_lines.h -- a text read as aligned 16-byte units, a wavefront per SPAN: the device helpers of the passes that count the line
-// ends themselves because they have no line index (qmap.hip, pair.hip).
+// ends themselves because they have no line index (qmap.hip, pair.hip, pick.hip).
 // Spans are laid from the aligned 16-byte unit that holds the text's first byte.  A pass READS whole aligned units: up to 15 bytes in
 // front of the text and behind it, inside the units of its first and last byte.
 #pragma once

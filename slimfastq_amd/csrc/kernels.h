@@ -313,3 +313,27 @@ void launch_pair_split(const PairText& t, u64 cap, const PairWindow& win, u32* l
 // the record starts, the rules and the name pass, no copy: b.d null = t is interleaved (record 2k against 2k + 1, a split's rules),
 // else record i of a against record i of b (an interleave's rules).  Writes info alone.
 void launch_pair_names(const PairText& a, const PairText& b, u64 cap, PairInfo* info, hipStream_t st);
+
+// Picked lines (pick.hip): of every record of a text one contiguous piece -- lines 1 and 2 with a '>' in front, the name, the base line
+// or the quality line -- the pieces of records [r0, r0 + nr) one behind the other.  Like pair.hip the pass finds the lines itself,
+// checks what it found and copies only where it holds: *info tells the host, which synchronises once.
+enum PickWhat : u32 { PICK_FASTA = 1, PICK_NAMES = 2, PICK_BASES = 3, PICK_QUALS = 4 };      // SFQ_PICK_*
+enum PickStatus : u32 {
+    PICK_OK = 0,
+    PICK_LINES,             // the text's lines are no multiple of four
+    PICK_RANGE,             // records that end behind the text's last record
+    PICK_CAP,               // more records than the arrays hold: info->recs says how many, nothing else was done
+    PICK_LONG,              // a piece of 4 GiB or more
+    PICK_AT,                // FASTA, NAMES: a record of the range does not begin with '@': info->bad_first (the smallest), info->bad_off
+    PICK_ROOM               // the pieces need more than the output holds: info->nout says how much
+};
+// r0, pieces: the range as the check found it; nout: the result's bytes; mark_off: where piece job.mark went (nout behind the last)
+struct PickInfo { u64 lines, recs; u32 status, pad; u64 r0, pieces, nout, mark_off, bad_first, bad_off; };
+// Record r's piece is text[from[r], to[r]): from[r] = where line fl of the record begins, plus skip; to[r] = where line tl of the
+// record begins (tl = 4: the next record, or the text's end).  cap entries each.
+struct PickLines { u64* from; u64* to; u64 cap; u32 fl, tl, skip; };
+// nr = ~0: to the text's last record; mark: a piece of the range, counted from r0
+struct PickJob { u32 what, pad; u64 r0, nr, out_cap, mark; };
+// t.starts: from[cap]; to[cap]; lens[nlens], dst[nlens + 1], scan_tmp as launch_scan_u32 wants it for nlens, where nlens = min(nr, cap);
+// info: zeroed by the caller.  out: job.out_cap bytes, of which info->nout are written, and none unless info->status stays 0.
+void launch_pick(const PairText& t, u64* to, u64 cap, const PickJob& job, u32* lens, u64* dst, u64* scan_tmp, u64 nlens, u8* out, PickInfo* info, hipStream_t st);
