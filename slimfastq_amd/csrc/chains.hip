@@ -1305,6 +1305,7 @@ void launch_gen_decode_c(const ChainArgs& a, const DecodeArgs& da, u32 c0, u32 c
 // =========================================================================================================
 #include "dev_rec_lane.h"
 #include "dev_wave.h"
+#include "rec_digits.h"
 
 struct RecChainPos { u32 b; u64 r0; u32 nrec; };
 __device__ __forceinline__ RecChainPos rec_chain_pos(const ChainArgs& a, u32 c) {
@@ -1823,66 +1824,109 @@ struct TokStage {                        // into the lane's column of RecTokLds:
     __device__ __forceinline__ void put_u(u32 row0, u64 num) { put_u_rows(*this, row0, num); }
 };
 struct TokStore { u32* p; __device__ __forceinline__ void put(u32 row, u32 sym) { *p++ = (row << 8) | sym; } __device__ __forceinline__ void put_u(u32 row0, u64 num) { put_u_rows(*this, row0, num); } };
-// the symbols of the record in column col (n bytes, nf fields), against the record in column col - 1; since: the fields that have
-// changed since the chain began / the shape last changed.  false: a field types as hexadecimal.
-// a field's type and value (dev_rec.h field_type) over the header in column col.  The usual field is a few decimal digits: one multiply-add a
-// digit, in 32 bits; field_type's general pass -- both readings carried in 64 bits, the classes, the wrap test: 35 instructions a byte, and with
-// two fields parsed per changed field and two passes four fifths of this kernel's instructions -- is for the lanes whose field is anything else
+// A field's type and value over the header in column col, the type as the chain codes it: a number that would not print back (dev_common.h
+// rec_number_prints_back) is a string.  The usual field is at most nine decimal digits: rec_digits.h converts it four digits a step from the staged
+// dwords, without a loop; field_type's general pass -- both readings carried in 64 bits, the classes, the wrap test: 35 instructions a byte -- is for
+// the lanes whose field is anything else.  (A short decimal prints back unless it is empty.)
 template <typename LT>
 __device__ __forceinline__ u32 nw_tok(const LT& L, u32 col, u32 off, u32 len, u64& num) {
-    u32 v = 0, lead = 0;
-    bool plain = len <= 9u;
-    if (plain)
-        for (u32 j = 0; j < len; j++) {
-            const u32 d = L.byte(col, off + j) - '0';
-            plain = plain && d <= 9u;
-            lead |= (j < 2u && d == 0u) ? 1u << j : 0u;
-            v = v * 10u + d;
-        }
-    if (plain) {
-        num = (lead & 3u) == 3u ? 0u : v;                                       // "00...": field_type's first test
-        return (lead & 3u) == 3u ? ST_STR : (lead & 1u) ? ST_DGT_Z : ST_DGT;
+    const RdField r = rd_parse9(L.tw[col], off, len);                          // (a longer field: its value is not used, its reads stay in the column)
+    if (len <= 9u && r.plain) {
+        const bool str = r.lead == 3u || len == 0u;                             // "00...": field_type's first test
+        num = str ? 0u : r.value;
+        return str ? ST_STR : (r.lead & 1u) ? ST_DGT_Z : ST_DGT;
     }
-    return field_type([&](u32 j) -> u32 { return L.byte(col, off + j); }, len, num, 0);
+    u32 type = field_type([&](u32 j) -> u32 { return L.byte(col, off + j); }, len, num, 0);
+    if (type != ST_STR && !rec_number_prints_back(type, len, L.byte(col, off))) type = ST_STR;
+    return type;
 }
+// put_u_rows' symbols without its loop (rec_digits.h): one, two or six predicated puts; ten keep a loop for the last four
+template <typename EM>
+__device__ __forceinline__ void tok_put_u(EM& em, u32 row0, u64 num) {
+    const u32 n = rd_u_count(num);
+    em.put(row0, rd_u_sym0(n, num));
+    if (n >= 2u) em.put(row0 + 1, rd_u_sym1(n, num));
+    if (n >= 6u) {
+        const u32 r = row0 + (n == 6u ? 2u : 6u), lo = (u32)num;
+        em.put(r, lo & 0xffu); em.put(r + 1, (lo >> 8) & 0xffu); em.put(r + 2, (lo >> 16) & 0xffu); em.put(r + 3, lo >> 24);
+    }
+    if (n == 10u) {
+        const u32 hi = (u32)(num >> 32);
+#pragma nounroll
+        for (u32 j = 0; j < 4; j++) em.put(row0 + 10 + j, (hi >> (8 * j)) & 0xffu);
+    }
+}
+__device__ __forceinline__ u32 wave_or(u32 x) {                               // the OR of x over the 64 lanes, in every lane
+    x |= (u32)__builtin_amdgcn_update_dpp(0, (int)x, DPP_ROW_SHR(1), 0xf, 0xf, false);
+    x |= (u32)__builtin_amdgcn_update_dpp(0, (int)x, DPP_ROW_SHR(2), 0xf, 0xf, false);
+    x |= (u32)__builtin_amdgcn_update_dpp(0, (int)x, DPP_ROW_SHR(4), 0xf, 0xf, false);
+    x |= (u32)__builtin_amdgcn_update_dpp(0, (int)x, DPP_ROW_SHR(8), 0xf, 0xf, false);
+    x |= (u32)__builtin_amdgcn_update_dpp(0, (int)x, DPP_ROW_BCAST15, 0xa, 0xf, false);
+    x |= (u32)__builtin_amdgcn_update_dpp(0, (int)x, DPP_ROW_BCAST31, 0xc, 0xf, false);
+    return rl(x, 63);
+}
+// What a round's 64 records code, every lane its own record (column lane + 1; n bytes, nf fields) against the record in the column before; called by
+// the whole wave.  map: the record's changed fields (0 for a record that is spelled out: shape); since: the fields that have changed since the chain
+// began / the shape last changed.  The fields are walked ONCE FOR THE WAVE, by the bits of orm -- the OR of the lanes' maps --: in step f a lane
+// parses its own field f if `need` says so -- its own map has f, or its right neighbour's map and since have it, or it is lane 63, whose numbers the
+// next round's lane 0 starts from --, and a changed field's previous VALUE (recs.cpp:333) is what the lane to the left has just parsed, moved one
+// lane up.  Lane 0's comes from the round before -- lane f keeps what lane 63 made of field f: cw_in, and kept_in, the fields lane 63 parsed then;
+// cw_out gets this round's --, or, where that round did not walk the field, from column 0's text as before.  A record's symbols stay in the order of
+// its fields.  false: a changed field types as hexadecimal.
 template <typename LT, typename EM>
-__device__ __forceinline__ bool rec_tokens(const LT& L, u32 col, u32 n, u32 nf, bool shape, u64 map, u64 since, EM& em) {
-    em.put(REC_FLAG_ROW, shape ? 1u : 0u);
-    if (shape) {                                                              // recs.cpp:292-305, in the chain itself
-        em.put_u(REC_FLAG_ROW + 2, n);
-        for (u32 j = 0; j < n; j++) em.put(REC_FLAG_ROW + 1, L.byte(col, j));
-        return true;
+__device__ __forceinline__ bool rec_tokens(const LT& L, u64 cw_in, u32 kept_in, u64& cw_out, u32 lane, bool valid, u32 n, u32 nf, bool shape,
+                                           u32 map, u32 since, u32 orm, u32 need, EM& em) {
+    const u32 col = lane + 1;
+    if (valid) {
+        em.put(REC_FLAG_ROW, shape ? 1u : 0u);
+        if (shape) {                                                          // recs.cpp:292-305, in the chain itself
+            tok_put_u(em, REC_FLAG_ROW + 2, n);
+            for (u32 j = 0; j < n; j++) em.put(REC_FLAG_ROW + 1, L.byte(col, j));
+        } else tok_put_u(em, 0 * 16 + 2, map);                                // put_num(0, map) recs.cpp:313
     }
-    em.put_u(0 * 16 + 2, map);                                                // put_num(0, map) recs.cpp:313
-    for (u64 todo = map; todo; todo &= todo - 1) {                            // the changed fields, in order
-        const u32 f = (u32)__ffsll((long long)todo) - 1u;
-        const u32 o = L.off[0][f][col], wl = L.wln[0][f][col];
-        u64 fnum;
-        u32 type = nw_tok(L, col, o, wl, fnum);
-        if (type != ST_STR && !rec_number_prints_back(type, wl, L.byte(col, o))) type = ST_STR;
-        if (type >= ST_HGT && type <= ST_HLTC_Z) return false;
-        const u32 rr = (f + 1) * 16;
-        if (type == ST_STR) {                                                 // recs.cpp:324-331
-            em.put(rr + 0, type);
-            em.put_u(rr + 2, wl);
-            for (u32 j = 0; j < wl; j++) em.put(rr + 1, L.byte(col, o + j));
-            continue;
+    bool ok = true;
+    for (u32 todo = orm; todo; todo &= todo - 1) {                            // the wave's changed fields, in order: todo is the same in every lane
+        const u32 f = (u32)__ffs((int)todo) - 1u;
+        const bool own = (map >> f) & 1u, parse = (need >> f) & 1u;
+        const bool want_was = own && ((since >> f) & 1u);
+        const bool kept = (kept_in >> f) & 1u;
+        const bool left0 = want_was && lane == 0 && !kept;                    // lane 0, and the round before did not walk this field
+        u32 type = ST_STR, o = 0, wl = 0;
+        u64 fnum = 0, give = 0, was0 = 0;
+        // one statement of the parse: a first turn for column 0 where lane 0 needs it (rare), then every lane's own column
+#pragma nounroll
+        for (u32 turn = __any(left0) ? 0u : 1u; turn < 2u; turn++) {
+            const u32 pc = turn ? col : 0u;
+            if (turn ? parse : left0) {
+                o = L.off[0][f][pc]; wl = L.wln[0][f][pc];
+                type = nw_tok(L, pc, o, wl, fnum);
+                give = (type == ST_DGT || type == ST_DGT_Z) ? fnum : 0ull;   // what the record to the right takes as `was`
+            }
+            if (!turn) was0 = give;
         }
-        u64 was = 0;                                                         // recs.cpp:333: the previous VALUE, if the field has one
-        if ((since >> f) & 1) {
-            const u32 po = L.off[0][f][col - 1], pwl = L.wln[0][f][col - 1];
-            u64 pn;
-            u32 pt = nw_tok(L, col - 1, po, pwl, pn);
-            if (pt != ST_STR && !rec_number_prints_back(pt, pwl, L.byte(col - 1, po))) pt = ST_STR;
-            if (pt == ST_DGT || pt == ST_DGT_Z) was = pn;
+        const u32 g_lo = (u32)give, g_hi = (u32)(give >> 32);
+        const u64 last = (u64)rl(g_lo, 63) | ((u64)rl(g_hi, 63) << 32), before = (u64)rl((u32)cw_in, f) | ((u64)rl((u32)(cw_in >> 32), f) << 32);
+        if (lane == f) cw_out = last;
+        u64 was = (u64)wave_shr1(g_lo, 0u) | ((u64)wave_shr1(g_hi, 0u) << 32);
+        if (lane == 0) was = kept ? before : was0;
+        if (!want_was) was = 0;                                               // a field that has not changed before: types start cold
+        if (own) {
+            const u32 rr = (f + 1) * 16;
+            if (type >= ST_HGT && type <= ST_HLTC_Z) ok = false;
+            else if (type == ST_STR) {                                        // recs.cpp:324-331
+                em.put(rr + 0, type);
+                tok_put_u(em, rr + 2, wl);
+                for (u32 j = 0; j < wl; j++) em.put(rr + 1, L.byte(col, o + j));
+            } else {
+                u64 gap;
+                if (fnum < was) { gap = was - fnum; type++; }
+                else gap = fnum - was;
+                em.put(rr + 0, type);
+                tok_put_u(em, rr + 2, gap);
+            }
         }
-        u64 gap;
-        if (fnum < was) { gap = was - fnum; type++; }
-        else gap = fnum - was;
-        em.put(rr + 0, type);
-        em.put_u(rr + 2, gap);
     }
-    return true;
+    return ok;
 }
 template <u32 ML>
 __global__ __launch_bounds__(64) void k_rec_tokens(ChainArgs a, u32* __restrict__ tok, u32* __restrict__ ntok, u32* __restrict__ flags) {
@@ -1910,6 +1954,7 @@ __global__ __launch_bounds__(64) void k_rec_tokens(ChainArgs a, u32* __restrict_
     u32 hdr_bytes = cp.r0 == base ? rl(base_n, 0) : 0u;
     u64 since0 = 0;                                                           // fields changed since the chain began / the last shape change, before lane 0's record
     u32 total = 0;
+    u32 kept = 0; u64 cw = 0;                                                 // lane f: what lane 63 made of field f the round before, for the fields in `kept`
     u32* const out = tok + cp.r0 * RT_TOK_PER_REC;
     const u32 cap = cp.nrec * RT_TOK_PER_REC;
     for (u64 rb = first; rb < end; rb += 64) {
@@ -1962,9 +2007,14 @@ __global__ __launch_bounds__(64) void k_rec_tokens(ChainArgs a, u32* __restrict_
         }
         // the symbols: made once, into LDS; placed by a wave scan of their numbers; copied out.  (Round 4 walked every record twice -- count, then write --,
         // each walk typing the changed fields and their left neighbours' again: 47 + 27 of this kernel's 100 M instructions per 2 M records.)
+        // (the fields are walked once for the wave: rec_tokens)
+        const u32 map32 = (u32)map, since32 = (u32)since;                     // (RF_NF fields at the most)
+        const u32 orm = wave_or(map32);
+        u32 need = map32 | wave_shl1(map32 & since32, 0u);
+        if (lane == 63 && valid) need |= orm & ((1u << nf) - 1u);
+        u64 cw_out = 0;
         TokStage tl; tl.p = &L.tokst[0][lane]; tl.n = 0;
-        bool ok = true;
-        if (valid) ok = rec_tokens(L, col, n, nf, shape, map, since, tl);
+        const bool ok = rec_tokens(L, cw, kept, cw_out, lane, valid, n, nf, shape, map32, since32, orm, need, tl);
         if (__any(!ok)) { if (lane == 0) flags[c] = 1; return; }
         const u32 cnt = tl.n;
         const u32 incl = wave_incl_scan(cnt);
@@ -1972,10 +2022,12 @@ __global__ __launch_bounds__(64) void k_rec_tokens(ChainArgs a, u32* __restrict_
         if (total + round > cap) { if (lane == 0) flags[c] = 1; return; }
         u32* const dst = out + total + (incl - cnt);
         if (__any(cnt > RT_STAGED)) {                                         // (a record that spells its header out: the walk again, to memory)
-            if (valid) { TokStore ts; ts.p = dst; rec_tokens(L, col, n, nf, shape, map, since, ts); }
+            TokStore ts; ts.p = dst;
+            rec_tokens(L, cw, kept, cw_out, lane, valid, n, nf, shape, map32, since32, orm, need, ts);
         } else
             for (u32 j = 0; __any(j < cnt); j++) if (j < cnt) dst[j] = L.tokst[j][lane];
         total += round;
+        kept = rl(need, 63); cw = cw_out;
         hdr_bytes += rl(wave_incl_scan(n), 63);
         __syncthreads();
         if (rb + 64 < end) {                                                  // lane 63's record is the next round's left neighbour
