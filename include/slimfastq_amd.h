@@ -484,6 +484,86 @@ int sfq_ctx_set_pick(sfq_ctx* ctx, int what);
 /* 1: the last decode call picked; *what, *text_bytes (the decoded text's size before the pick), *n_records; 0: it did not (all zeroed) */
 int sfq_get_pick(const sfq_ctx* ctx, int* what, uint64_t* text_bytes, uint64_t* n_records);
 
+/* ---- selected records -------------------------------------------------------------------------------------------------------
+ * A subset of a decoded FASTQ chosen by CONTENT, while the text is on the device: the records of a range that pass a filter and a
+ * reproducible sample, whole and in order (sel.hip).  Text to text like the picked lines, whose copy the pass uses; no stream, coder
+ * or block format knows of it.
+ * Lines and records: they are sfq_pick_lines' own.  A line ends at '\n'; a text without a final '\n' still ends in a line; '\r' is a
+ *   byte like any other.  Line lengths exclude the '\n'.
+ * Content verdict: the AND of the terms that are on; if invert is set, the result is negated.
+ *   Length: min_len <= L2 <= max_len, where L2 is the length of line 2.
+ *   N: the count of 'N' and 'n' bytes in line 2 is <= max_n.
+ *   Quality: with S the sum of line 4's bytes and L its length, the term holds when 100 * (S - qual_base * L) >= min_mean_q_x100 * L.
+ *     The arithmetic is signed 64-bit.  An empty quality line passes (min_len is what catches empty lines).  Sums are 64-bit: a line
+ *     may hold close to 4 GiB.
+ *   Motif: the motif occurs as a substring of line 2, compared without regard to letter case.  With motif_rc, its reverse complement
+ *     counts as an occurrence too.  Only line 2 counts: an occurrence in a header, in a '+' line that repeats the header, or in a
+ *     quality line (ACGT are legal quality bytes) is no occurrence.  An occurrence never runs across a line end.
+ * Pairs: a pair's content verdict is the AND (SFQ_SELECT_BOTH) or the OR (SFQ_SELECT_EITHER) of its mates' content verdicts, taken
+ *   after invert.
+ * Sampling: works on the index i = index_base + record number; with pairs, i is shifted right by one, so that mates share it.
+ *     h = sample_seed + (i + 1) * 0x9E3779B97F4A7C15
+ *     h ^= h >> 30; h *= 0xBF58476D1CE4E5B9
+ *     h ^= h >> 27; h *= 0x94D049BB133111EB
+ *     h ^= h >> 31                                        (all arithmetic mod 2^64)
+ *   The record is kept where (h >> 32) < sample.  invert does not touch the range or the sample.
+ * Kept records: a record is kept when it is in the range, it is sampled, and its content verdict holds.  The result is the kept
+ *   records, whole (four lines each), in order, with nothing between them. */
+#define SFQ_SELECT_BOTH 1
+#define SFQ_SELECT_EITHER 2
+typedef struct sfq_select {
+    uint64_t first_record, n_records;   /* the range the selection looks at; n_records = UINT64_MAX: to the last record. Records outside are dropped */
+    uint32_t min_len, max_len;          /* bytes of line 2 without its '\n'; 0 / UINT32_MAX = off */
+    uint32_t max_n;                     /* bytes 'N' or 'n' in line 2; UINT32_MAX = off */
+    uint32_t min_mean_q_x100;           /* 0 = off */
+    uint32_t qual_base;                 /* subtracted from every quality byte (33 for Phred+33); <= 126 */
+    uint32_t motif_len;                 /* 0 = off, at most 32 */
+    uint8_t  motif[32];                 /* 'A' 'C' 'G' 'T' only */
+    uint32_t motif_rc;                  /* != 0: the reverse complement counts as an occurrence too */
+    uint32_t invert;                    /* != 0: the CONTENT verdict is negated (grep -v) */
+    uint32_t pairs;                     /* 0: records stand alone; SFQ_SELECT_BOTH / SFQ_SELECT_EITHER: records 2k, 2k+1 are kept or dropped together */
+    uint32_t sample;                    /* 0 = off; else keep where (h >> 32) < sample */
+    uint64_t sample_seed, index_base;
+} sfq_select;
+typedef struct sfq_select_report {
+    uint64_t n_in_range, n_kept, text_bytes, kept_bytes;
+    uint64_t n_fail[4];                 /* records in range that fail the length / N / quality / motif term (before invert); 0 for a term that is off */
+} sfq_select_report;
+/* host only, no GPU: SFQ_OK, or SFQ_E_ARG for a null pointer, a motif byte outside ACGT, motif_len > 32, min_len > max_len,
+ * qual_base > 126, pairs > 2, n_records == 0, or, with pairs, an odd first_record or index_base */
+int sfq_select_check(const sfq_select* sel);
+/* host only, no GPU: a rule from the CLI's -k SPEC, a comma-separated list of the terms minlen=N, maxlen=N, maxn=N, meanq=Q (a decimal
+ * with up to two fraction digits; Phred+33), seq=MOTIF (upper or lower case, stored upper case), rc, invert, either and sample=F[:SEED]
+ * (0 < F < 1, sample = floor(F * 2^32), seed 0 if absent).  *sel: the rule, every term that is not named off, the range (0, UINT64_MAX),
+ * pairs = 0; *either (may be NULL) = 1 where the list names `either` -- whether records are pairs is the caller's to know.
+ * SFQ_E_ARG for an unknown term, a bad number, a motif with a byte outside ACGTacgt or longer than 32; err (may be NULL) then says which. */
+int sfq_select_parse(const char* spec, sfq_select* sel, int* either, char* err, uint64_t err_cap);
+/* The selection of d_text[0, n) into d_out; *out_bytes = the bytes of the result (on SFQ_E_OVERFLOW: the size needed).
+ * SFQ_E_ARG: a null pointer (report may be NULL), n == 0, a struct that sfq_select_check refuses, a range that ends behind the last
+ * record.  SFQ_E_FORMAT: lines that are no multiple of four; with pairs, an odd record count in the range (n_records odd, or odd to
+ * the end).  SFQ_E_UNSUPPORTED: a record of 4 GiB or more.  SFQ_E_OVERFLOW: a result larger than out_cap.
+ * No record kept is not an error: SFQ_OK with *out_bytes = 0 and nothing written.  Every refusal is decided on the device before the
+ * copy: a refused call writes nothing.  A call that succeeds writes d_out[0, *out_bytes) and nothing else.  d_out must not overlap
+ * the text.  The call runs on the context's stream and synchronises once.  Like the other side passes, it may read the whole aligned
+ * 16-byte units that hold the text's first and last byte. */
+int sfq_select_records(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, const sfq_select* sel,
+                       uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_select_report* report);
+/* sel != NULL: sfq_decode_blocks_host, sfq_decode_block_range_host and sfq_decode_pair_range_host hand back the selection of the text
+ * they decoded (the struct is copied; SFQ_E_ARG, and the setting stays, where sfq_select_check refuses it); NULL: off (default).
+ * The selection is the first pass behind the checksum pass: the CRCs, installed ones included, stay those of the decoded text.  It
+ * runs in front of the pair split and in front of the pick, which then run unchanged on the selected text.  Because the range is part
+ * of the struct, a caller can cut a window of blocks down to records without a host pass.  While the pair split is on, a selection
+ * with pairs == 0 is refused with SFQ_E_ARG: the mates would fall out of step.  sfq_decode_pair_range_host supplies the range
+ * itself, the window's pairs: the selection runs first, on the decoded blocks, with that range, and the cut-and-split then runs as a
+ * plain split of the whole selected text; the struct's own range must be (0, UINT64_MAX) and pairs must not be 0 (SFQ_E_ARG;
+ * likewise a window whose first pair is an odd record of the blocks that hold it -- blocks of an odd record count).
+ * out_cap keeps sizing the DECODED text.  With nothing kept the _host entries return SFQ_OK and 0 bytes; the split and the pick are
+ * skipped and their get_* calls answer 0.  Costs one more device buffer of the text's size, held while the switch is on.  The
+ * device-pointer decode entries are not affected.  Default off: nothing is launched, allocated or copied that is not today. */
+int sfq_ctx_set_select(sfq_ctx* ctx, const sfq_select* sel);
+/* 1: the last decode call selected, *out = what it found; 0: it did not (*out zeroed) */
+int sfq_get_select(const sfq_ctx* ctx, sfq_select_report* out);
+
 /* ---- the ".sfq" container (host only) ----------------------------------------------------------
  * Replaces FilerSave + the info page (filer.cpp:217-242, config.cpp:334-347) for hosts that assemble an archive
  * themselves: info_text is the info page ("key=value\n" lines), then n_streams named byte streams (names of at most

@@ -23,6 +23,8 @@ QMAP_PRESETS = {"illumina8": QMAP_ILLUMINA8, "novaseq4": QMAP_NOVASEQ4}
 PICK_FASTA, PICK_NAMES, PICK_BASES, PICK_QUALS = 1, 2, 3, 4
 PICKS = {"fasta": PICK_FASTA, "names": PICK_NAMES, "bases": PICK_BASES, "quals": PICK_QUALS}
 PICK_TO_END = 0xFFFFFFFFFFFFFFFF
+SELECT_BOTH, SELECT_EITHER = 1, 2
+SELECT_TO_END = 0xFFFFFFFFFFFFFFFF
 
 EXPORTS = [
     "sfq_stream_name", "sfq_ctx_create", "sfq_ctx_destroy", "sfq_last_error", "sfq_ctx_set_table_budget",
@@ -38,6 +40,7 @@ EXPORTS = [
     "sfq_interleave", "sfq_split_pairs", "sfq_encode_pairs_host", "sfq_ctx_set_pair_split", "sfq_get_pair_split",
     "sfq_split_pairs_range", "sfq_check_mates", "sfq_ctx_set_mate_check", "sfq_get_mate_report", "sfq_pair_window_blocks",
     "sfq_decode_pair_range_host", "sfq_pick_lines", "sfq_ctx_set_pick", "sfq_get_pick",
+    "sfq_select_check", "sfq_select_parse", "sfq_select_records", "sfq_ctx_set_select", "sfq_get_select",
 ]
 
 
@@ -97,6 +100,45 @@ class MateReport(C.Structure):
     """sfq_mate_report: what the name pass found (pair.hip k_pair_names)."""
     _fields_ = [("n_pairs", C.c_uint64), ("n_mismatch", C.c_uint64), ("first_mismatch", C.c_uint64),
                 ("first_off_a", C.c_uint64), ("first_off_b", C.c_uint64)]
+
+
+class Select(C.Structure):
+    """sfq_select: the rule of a selection (sel.hip).  Select() is the rule that keeps every record: every term off."""
+    _fields_ = [("first_record", C.c_uint64), ("n_records", C.c_uint64), ("min_len", C.c_uint32), ("max_len", C.c_uint32),
+                ("max_n", C.c_uint32), ("min_mean_q_x100", C.c_uint32), ("qual_base", C.c_uint32), ("motif_len", C.c_uint32),
+                ("motif", C.c_uint8 * 32), ("motif_rc", C.c_uint32), ("invert", C.c_uint32), ("pairs", C.c_uint32), ("sample", C.c_uint32),
+                ("sample_seed", C.c_uint64), ("index_base", C.c_uint64)]
+
+    def __init__(self, first_record=0, n_records=None, min_len=0, max_len=0xFFFFFFFF, max_n=0xFFFFFFFF, min_mean_q_x100=0, qual_base=33,
+                 motif=b"", motif_rc=False, invert=False, pairs=0, sample=0, sample_seed=0, index_base=0, motif_len=None):
+        super().__init__()
+        self.first_record, self.n_records = first_record, SELECT_TO_END if n_records is None else n_records
+        self.min_len, self.max_len, self.max_n = min_len, max_len, max_n
+        self.min_mean_q_x100, self.qual_base = min_mean_q_x100, qual_base
+        self.motif_len = len(motif) if motif_len is None else motif_len
+        for i, b in enumerate(bytes(motif)[:32]):
+            self.motif[i] = b
+        self.motif_rc, self.invert, self.pairs = int(motif_rc), int(invert), pairs
+        self.sample, self.sample_seed, self.index_base = sample, sample_seed, index_base
+
+
+class SelectReport(C.Structure):
+    """sfq_select_report: what a selection found."""
+    _fields_ = [("n_in_range", C.c_uint64), ("n_kept", C.c_uint64), ("text_bytes", C.c_uint64), ("kept_bytes", C.c_uint64),
+                ("n_fail", C.c_uint64 * 4)]
+
+
+def select_check(sel) -> int:
+    """sfq_select_check (no GPU): 0, or E_ARG for a rule the library refuses."""
+    return int(lib().sfq_select_check(C.byref(sel)))
+
+
+def select_parse(spec: str):
+    """sfq_select_parse (no GPU): (Select, either) of the CLI's -k SPEC; ValueError with the library's words where it refuses."""
+    sel, either, err = Select(), C.c_int(), C.create_string_buffer(256)
+    if lib().sfq_select_parse(spec.encode(), C.byref(sel), C.byref(either), err, 256):
+        raise ValueError(err.value.decode("latin1"))
+    return sel, bool(either.value)
 
 
 class SfqError(RuntimeError):
@@ -221,6 +263,11 @@ def lib():
         L.sfq_pick_lines.argtypes = [vp, vp, u64, C.c_int, u64, u64, vp, u64, u64p, u64p]
         L.sfq_ctx_set_pick.argtypes = [vp, C.c_int]
         L.sfq_get_pick.argtypes = [vp, C.POINTER(C.c_int), u64p, u64p]
+        L.sfq_select_check.argtypes = [C.POINTER(Select)]
+        L.sfq_select_parse.argtypes = [C.c_char_p, C.POINTER(Select), C.POINTER(C.c_int), C.c_char_p, u64]
+        L.sfq_select_records.argtypes = [vp, vp, u64, C.POINTER(Select), vp, u64, u64p, C.POINTER(SelectReport)]
+        L.sfq_ctx_set_select.argtypes = [vp, C.POINTER(Select)]
+        L.sfq_get_select.argtypes = [vp, C.POINTER(SelectReport)]
         _lib = L
     return _lib
 
@@ -525,6 +572,33 @@ class Context:
         if rc < 0:
             self._check(rc)
         return (int(what.value), int(n.value), int(recs.value)) if rc == 1 else None
+
+    def select_records(self, d_text, nbytes, sel, d_out, out_cap):
+        """The records of the FASTQ text in the device buffer at d_text that the Select keeps, whole and in order, into the one at
+        d_out (sfq_select_records); returns (bytes written, SelectReport).  An SfqError of code E_OVERFLOW carries the size needed
+        as .needed."""
+        n, rep = C.c_uint64(), SelectReport()
+        rc = lib().sfq_select_records(self._h, C.c_void_p(d_text), int(nbytes), C.byref(sel), C.c_void_p(d_out), int(out_cap),
+                                      C.byref(n), C.byref(rep))
+        try:
+            self._check(rc)
+        except SfqError as e:
+            e.needed = int(n.value)
+            raise
+        return int(n.value), rep
+
+    def set_select(self, sel=None):
+        """A Select: decode_host, decode_range_host and decode_pair_range_host return the selection of the text they decoded instead
+        of the text (get_select() says what it kept); None: off."""
+        self._check(lib().sfq_ctx_set_select(self._h, None if sel is None else C.byref(sel)))
+
+    def get_select(self):
+        """The SelectReport of the last decode call; None where it did not select."""
+        rep = SelectReport()
+        rc = lib().sfq_get_select(self._h, C.byref(rep))
+        if rc < 0:
+            self._check(rc)
+        return rep if rc == 1 else None
 
     def set_block_checksums(self, crcs):
         """The expected CRCs of the next decode call's blocks (consumed by it)."""

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdlib>
 #include <cstdio>
@@ -202,6 +203,10 @@ struct sfq_ctx {
     int pick_what = 0;                                // sfq_ctx_set_pick
     DevBuf pick_out;                                  // the picked lines of a decoded text (while the switch is on)
     int pick_done = 0; u64 pick_text = 0, pick_recs = 0;      // the last decode call's: its selection, the text's bytes, the records
+    // selected records (sel.hip): works in pair_work and reports through pair_pin too; nothing of this exists until the switch is on
+    bool sel_on = false; sfq_select sel{};            // sfq_ctx_set_select
+    DevBuf sel_out;                                   // the selected records of a decoded text (while the switch is on)
+    bool sel_done = false; sfq_select_report sel_report{};    // the last decode call's
 };
 
 namespace {
@@ -964,7 +969,7 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
         &ctx->oflags, &ctx->okbytes, &ctx->ofpos, &ctx->okoff, &ctx->ofilt, &ctx->orecmap, &ctx->olist, &ctx->line_off_o, &ctx->ono, &ctx->opiece,
         &ctx->otxt[0], &ctx->otxt[1], &ctx->otxt[2], &ctx->osize_all, &ctx->oroff_all, &ctx->oroff_k, &ctx->ocnt,
         &ctx->crc_tab, &ctx->crc_tiles, &ctx->crc_grps, &ctx->crc_bounds, &ctx->crc_out, &ctx->stats_acc, &ctx->qmap_dev,
-        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out, &ctx->pick_out };
+        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out, &ctx->pick_out, &ctx->sel_out };
     for (DevBuf* b : all) release(*b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->pin2) (void)hipHostFree(ctx->pin2);
@@ -2219,6 +2224,184 @@ int sfq_get_pick(const sfq_ctx* ctx, int* what, uint64_t* text_bytes, uint64_t* 
     return ctx->pick_done ? 1 : 0;
 }
 
+// ---- selected records (sel.hip) ---------------------------------------------------------------------------------------------------
+int sfq_select_check(const sfq_select* s) {
+    if (!s) return SFQ_E_ARG;
+    if (s->motif_len > 32 || s->min_len > s->max_len || s->qual_base > 126 || s->pairs > 2 || !s->n_records) return SFQ_E_ARG;
+    for (u32 i = 0; i < s->motif_len; i++)
+        if (s->motif[i] != 'A' && s->motif[i] != 'C' && s->motif[i] != 'G' && s->motif[i] != 'T') return SFQ_E_ARG;
+    if (s->pairs && ((s->first_record | s->index_base) & 1)) return SFQ_E_ARG;
+    return SFQ_OK;
+}
+// "term,term,...": see slimfastq_amd.h
+int sfq_select_parse(const char* spec, sfq_select* sel, int* either, char* err, uint64_t err_cap) {
+    auto bad = [&](const char* fmt, const std::string& what) {
+        if (err && err_cap) snprintf(err, (size_t)err_cap, fmt, what.c_str());
+        return SFQ_E_ARG;
+    };
+    if (!spec || !sel) return SFQ_E_ARG;
+    memset(sel, 0, sizeof *sel);
+    sel->n_records = ~0ull; sel->max_len = ~0u; sel->max_n = ~0u; sel->qual_base = 33;
+    if (either) *either = 0;
+    auto number = [](const std::string& t, u64 max, u64* v) {      // decimal digits only, at most max
+        if (t.empty() || t.size() > 19) return false;
+        u64 x = 0;
+        for (char c : t) { if (c < '0' || c > '9') return false; x = x * 10 + (u64)(c - '0'); }
+        *v = x;
+        return x <= max;
+    };
+    const std::string all = spec;
+    if (all.empty()) return bad("an empty list of terms%s", "");
+    for (size_t at = 0; at <= all.size(); ) {
+        const size_t comma = std::min(all.find(',', at), all.size());
+        const std::string term = all.substr(at, comma - at);
+        at = comma + 1;
+        const size_t eq = term.find('=');
+        const std::string key = term.substr(0, eq), val = eq == std::string::npos ? "" : term.substr(eq + 1);
+        const bool has = eq != std::string::npos;
+        u64 v = 0;
+        if (key == "minlen" && has) { if (!number(val, 0xFFFFFFFFull, &v)) return bad("minlen=%s: not a number of bytes", val); sel->min_len = (u32)v; }
+        else if (key == "maxlen" && has) { if (!number(val, 0xFFFFFFFFull, &v)) return bad("maxlen=%s: not a number of bytes", val); sel->max_len = (u32)v; }
+        else if (key == "maxn" && has) { if (!number(val, 0xFFFFFFFFull, &v)) return bad("maxn=%s: not a number of bytes", val); sel->max_n = (u32)v; }
+        else if (key == "meanq" && has) {                      // a decimal with up to two fraction digits, times 100
+            const size_t dot = val.find('.');
+            std::string ip = val.substr(0, dot), fp = dot == std::string::npos ? "" : val.substr(dot + 1);
+            u64 f = 0;
+            if (dot != std::string::npos && (fp.empty() || fp.size() > 2)) return bad("meanq=%s: a decimal with up to two fraction digits", val);
+            if (fp.size() == 1) fp += "0";
+            if (!number(ip, 40000000ull, &v) || (!fp.empty() && !number(fp, 99, &f))) return bad("meanq=%s: a decimal with up to two fraction digits", val);
+            sel->min_mean_q_x100 = (u32)(v * 100 + f);
+        } else if (key == "seq" && has) {
+            if (val.empty() || val.size() > 32) return bad("seq=%s: a motif holds 1 to 32 bases", val);
+            for (size_t i = 0; i < val.size(); i++) {
+                const char c = (char)(val[i] & ~0x20);
+                if (c != 'A' && c != 'C' && c != 'G' && c != 'T') return bad("seq=%s: a motif holds the bases ACGT only", val);
+                sel->motif[i] = (u8)c;
+            }
+            sel->motif_len = (u32)val.size();
+        } else if (key == "sample" && has) {                   // F[:SEED], 0 < F < 1
+            const size_t colon = val.find(':');
+            const std::string fs = val.substr(0, colon);
+            if (colon != std::string::npos && !number(val.substr(colon + 1), ~0ull, &v)) return bad("sample=%s: the seed is a decimal number", val);
+            bool digits = !fs.empty() && fs.size() < 32;
+            for (char c : fs) if ((c < '0' || c > '9') && c != '.') digits = false;
+            char* e = nullptr;
+            const double f = digits ? strtod(fs.c_str(), &e) : 0.0;
+            if (!digits || !e || *e || !(f > 0.0) || !(f < 1.0)) return bad("sample=%s: a share above 0 and below 1, as F or F:SEED", val);
+            sel->sample = (u32)std::floor(f * 4294967296.0);
+            if (!sel->sample) return bad("sample=%s: a share too small to keep a record", val);
+            sel->sample_seed = colon == std::string::npos ? 0 : v;
+        } else if (term == "rc") sel->motif_rc = 1;
+        else if (term == "invert") sel->invert = 1;
+        else if (term == "either") { if (either) *either = 1; }
+        else return bad("%s: no such term (minlen= maxlen= maxn= meanq= seq= rc invert either sample=)", term);
+    }
+    if (sel->min_len > sel->max_len) return bad("minlen above maxlen: no record can pass%s", "");
+    if (sel->motif_rc && !sel->motif_len) return bad("rc goes with seq=MOTIF%s", "");
+    return SFQ_OK;
+}
+// pick_run's shape: one pass on the context's stream, one synchronise, in pair_run's working buffers and with its sizing; only a
+// text with more records than the arrays were laid out for runs twice.  *rep: what the device found (filled on SFQ_E_OVERFLOW too).
+static int select_run(sfq_ctx* ctx, const u8* text, u64 n, const sfq_select& s, u8* out, u64 out_cap, sfq_select_report* rep) {
+    int rc;
+    if ((rc = reserve_pinned_buf(ctx, ctx->pair_pin, ctx->pair_pin_cap, std::max({ sizeof(PairInfo), sizeof(PickInfo), sizeof(SelInfo) })))) return rc;
+    SelJob job{};
+    job.r0 = s.first_record; job.nr = s.n_records; job.out_cap = out_cap;
+    job.min_len = s.min_len; job.max_len = s.max_len; job.max_n = s.max_n; job.min_q = s.min_mean_q_x100; job.qual_base = s.qual_base;
+    job.motif_len = s.motif_len; job.invert = s.invert != 0; job.pairs = s.pairs; job.sample = s.sample;
+    job.seed = s.sample_seed; job.index_base = s.index_base;
+    for (u32 i = 0; i < s.motif_len; i++) {                // two bits a base, (byte >> 1) & 3: the complement is the code ^ 2
+        job.motif |= (u64)((s.motif[i] >> 1) & 3) << (2 * i);
+        job.motif_rev |= (u64)(((s.motif[s.motif_len - 1 - i] >> 1) & 3) ^ 2) << (2 * i);
+    }
+    if (!s.motif_rc) job.motif_rev = job.motif;
+    SelInfo got;
+    for (int attempt = 0; ; attempt++) {
+        const u64 cap = std::max<u64>(ctx->pair_cap, n / 64 + 1024);
+        const u64 nlens = std::min(s.n_records, cap);
+        auto up = [](u64 v) { return (v + 15) & ~15ull; };
+        u64 at = up(std::max({ sizeof(PairInfo), sizeof(PickInfo), sizeof(SelInfo) }));
+        const u64 sc = at; at += up(qmap_scratch(text, n).bytes);
+        const u64 ls = at; at += up((4 * cap + 1) * 8);
+        const u64 acc = at; at += up(2 * cap * 8);
+        const u64 hit = at; at += up(cap);
+        const u64 keep = at; at += up(nlens * 4);
+        const u64 rlen = at; at += up(nlens * 4);
+        const u64 pos = at; at += up((nlens + 1) * 8);
+        const u64 lens = at; at += up(nlens * 4);
+        const u64 from = at; at += up(nlens * 8);
+        const u64 dst = at; at += up((nlens + 1) * 8);
+        const u64 tmp = at; at += up((nlens / 1024 + 2) * 8);
+        if ((rc = reserve(ctx, ctx->pair_work, (size_t)at))) return rc;
+        u8* w = (u8*)ctx->pair_work.p;
+        SelInfo* info = (SelInfo*)w;
+        HIPC(hipMemsetAsync(info, 0, sizeof(SelInfo), ctx->st));
+        const PairText t{ text, n, w + sc, nullptr };
+        const SelArrays A{ (u64*)(w + ls), (u64*)(w + acc), w + hit, (u32*)(w + keep), (u32*)(w + rlen), (u64*)(w + pos), (u32*)(w + lens),
+                           (u64*)(w + from), (u64*)(w + dst), (u64*)(w + tmp), cap, nlens };
+        launch_select(t, A, job, out, info, ctx->st);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(ctx->pair_pin, info, sizeof(SelInfo), hipMemcpyDeviceToHost, ctx->st));
+        HIPC(hipStreamSynchronize(ctx->st));
+        memcpy(&got, ctx->pair_pin, sizeof(SelInfo));
+        if (got.status != SEL_CAP) break;
+        if (attempt) return fail(ctx, SFQ_E_HIP, "selected records: the records did not fit twice");
+        ctx->pair_cap = got.recs;
+    }
+    memset(rep, 0, sizeof *rep);
+    rep->text_bytes = n;
+    const unsigned long long r0 = s.first_record, nr = s.n_records, recs = got.recs;
+    switch (got.status) {
+    case SEL_OK: break;
+    case SEL_LINES: return fail(ctx, SFQ_E_FORMAT, "selected records: the text holds %llu lines, not a multiple of four", (unsigned long long)got.lines);
+    case SEL_RANGE:
+        if (s.n_records == ~0ull) return fail(ctx, SFQ_E_ARG, "selected records: record %llu lies behind the text's %llu records", r0, recs);
+        return fail(ctx, SFQ_E_ARG, "selected records: records %llu..+%llu end behind the text's %llu records", r0, nr, recs);
+    case SEL_ODD: return fail(ctx, SFQ_E_FORMAT, "selected records: the range holds an odd number of records, which are no pairs (records %llu.. of %llu)", r0, recs);
+    case SEL_LONG: return fail(ctx, SFQ_E_UNSUPPORTED, "selected records: a record of 4 GiB or more");
+    case SEL_ROOM:
+        rep->kept_bytes = got.copy.nout;
+        return fail(ctx, SFQ_E_OVERFLOW, "selected records: the result needs %llu bytes", (unsigned long long)got.copy.nout);
+    default: return fail(ctx, SFQ_E_HIP, "selected records: status %u", got.status);
+    }
+    rep->n_in_range = got.nr; rep->n_kept = got.copy.pieces; rep->kept_bytes = got.copy.nout;
+    for (int i = 0; i < 4; i++) rep->n_fail[i] = got.n_fail[i];
+    return SFQ_OK;
+}
+int sfq_select_records(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, const sfq_select* sel,
+                       uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_select_report* report) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!d_text || !d_out || !out_bytes || !sel) return fail(ctx, SFQ_E_ARG, "null argument");
+    *out_bytes = 0;
+    if (report) memset(report, 0, sizeof *report);
+    if (!n) return fail(ctx, SFQ_E_ARG, "selected records: an empty text");
+    if (sfq_select_check(sel)) return fail(ctx, SFQ_E_ARG, "selected records: a selection that sfq_select_check refuses");
+    HIPC(hipSetDevice(ctx->dev));
+    Settle settle(ctx);
+    sfq_select_report rep;
+    const int rc = select_run(ctx, d_text, n, *sel, d_out, out_cap, &rep);
+    if (rc == SFQ_E_OVERFLOW) *out_bytes = rep.kept_bytes;
+    if (rc) return rc;
+    *out_bytes = rep.kept_bytes;
+    if (report) *report = rep;
+    settle.ok = true;
+    return SFQ_OK;
+}
+int sfq_ctx_set_select(sfq_ctx* ctx, const sfq_select* sel) {
+    if (!ctx) return SFQ_E_ARG;
+    if (sel && sfq_select_check(sel)) return fail(ctx, SFQ_E_ARG, "selected records: a selection that sfq_select_check refuses");
+    ctx->sel_on = sel != nullptr;
+    if (sel) ctx->sel = *sel;
+    else release(ctx->sel_out);
+    return SFQ_OK;
+}
+int sfq_get_select(const sfq_ctx* ctx, sfq_select_report* out) {
+    if (!ctx || !out) return SFQ_E_ARG;
+    if (!ctx->sel_done) { memset(out, 0, sizeof *out); return 0; }
+    *out = ctx->sel_report;
+    return 1;
+}
+
 int sfq_get_block_index(sfq_ctx* ctx, sfq_block_info* h_blocks, uint32_t cap) {
     if (!ctx || !h_blocks) return SFQ_E_ARG;
     if (cap < ctx->index.size()) return fail(ctx, SFQ_E_ARG, "index has %zu blocks", ctx->index.size());
@@ -2299,7 +2482,7 @@ static int decode_device(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_inf
     Settle settle(ctx);
     drop_encode_blobs(ctx);                             // whatever an encode left behind is not this archive's
     ctx->crcs.clear(); ctx->text_crc = 0;
-    ctx->pair_split_done = false; ctx->pick_done = 0;
+    ctx->pair_split_done = false; ctx->pick_done = 0; ctx->sel_done = false;
     if (w.ranged && ctx->pair_split_on && !w.pairs)
         return fail(ctx, SFQ_E_UNSUPPORTED, "a window of blocks may start at a second mate and is not split: sfq_ctx_set_pair_split(ctx, 0) comes first");
     const bool check = ex.set;
@@ -3039,6 +3222,15 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
         for (u32 b = 0; b < w.b0; b++) rec0 -= h_blocks[b].n_records;
     }
     if (w.n == 0 || w.b0 >= n_blocks || w.n > n_blocks - w.b0) return fail(ctx, SFQ_E_ARG, "blocks %u..+%u: not a window of the call's %u blocks", w.b0, w.n, n_blocks);
+    if (ctx->sel_on) {
+        if (w.pairs && (ctx->sel.first_record || ctx->sel.n_records != ~0ull || !ctx->sel.pairs))
+            return fail(ctx, SFQ_E_ARG, "selected records: a window of pairs is the range: the selection's own must be (0, UINT64_MAX), and its pairs not 0");
+        if (w.pairs && (rec0 & 1))
+            return fail(ctx, SFQ_E_ARG, "selected records: the window's first pair is record %llu of the blocks that hold it: mates share a sample index only from an even record on",
+                        (unsigned long long)rec0);
+        if (!w.pairs && ctx->pair_split_on && !ctx->sel.pairs)
+            return fail(ctx, SFQ_E_ARG, "selected records: while the pair split is on a selection keeps or drops pairs (pairs must not be 0): the mates would fall out of step");
+    }
     HIPC(hipSetDevice(ctx->dev));
     int rc;
     // the index is untrusted: every stream's blocks must lie inside the bytes handed over (the device entry point cannot
@@ -3085,7 +3277,30 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
                        stream_offset, (u8*)ctx->out_stage.p, out_cap, out_bytes, result, ex, w);
     if (rc) return rc;
     const u8* d_text = (const u8*)ctx->out_stage.p;
-    if (w.pairs) {                                         // behind the checksum pass too: cut to the pairs and split in one copy
+    const bool selected = ctx->sel_on;
+    if (selected) {                                        // the first pass behind the checksum pass: the split and the pick see what it kept
+        if (!*out_bytes) return fail(ctx, SFQ_E_FORMAT, "selected records: an empty text");
+        if ((rc = reserve(ctx, ctx->sel_out, (size_t)*out_bytes + 16))) return rc;
+        Settle settle(ctx);
+        sfq_select s = ctx->sel;
+        if (w.pairs) { s.first_record = rec0; s.n_records = 2 * w.n_pairs; }      // the window's pairs, cut here
+        if ((rc = select_run(ctx, d_text, *out_bytes, s, (u8*)ctx->sel_out.p, *out_bytes, &ctx->sel_report))) return rc;
+        settle.ok = true;
+        ctx->sel_done = true;
+        d_text = (const u8*)ctx->sel_out.p;
+        *out_bytes = ctx->sel_report.kept_bytes;
+        if (!*out_bytes) return SFQ_OK;                    // nothing kept: neither the split nor the pick takes an empty text
+    }
+    if (w.pairs && selected) {                             // the selection cut to the window: a plain split of what it kept
+        if ((rc = reserve(ctx, ctx->pair_out, (size_t)*out_bytes + 16))) return rc;
+        Settle settle(ctx);
+        PairInfo got;
+        if ((rc = pair_run(ctx, d_text, *out_bytes, nullptr, 0, (u8*)ctx->pair_out.p, &got))) return rc;
+        settle.ok = true;
+        d_text = (const u8*)ctx->pair_out.p;
+        *split = got.split;
+        ctx->pair_split_done = true; ctx->pair_first = got.split; ctx->pair_n = got.recs[0] >> 1;
+    } else if (w.pairs) {                                  // behind the checksum pass too: cut to the pairs and split in one copy
         if (!*out_bytes) return fail(ctx, SFQ_E_FORMAT, "paired files: an empty text");
         if ((rc = reserve(ctx, ctx->pair_out, (size_t)*out_bytes + 16))) return rc;
         Settle settle(ctx);

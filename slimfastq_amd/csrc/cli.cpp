@@ -15,6 +15,7 @@
 //               with -d: the second mates go here, the first to -u
 //   -W F:N    : with -d and -p: pairs F .. F + N - 1 only (numbered from 0 over the archive), cut and split on the GPU
 //   -M        : with -p on encode: the mates' names are compared on the GPU before a slab is coded; a mismatch ends the run
+//   -k terms  : with -d: the records that pass a filter only (length, N count, mean quality, a motif, a sample), chosen on the GPU
 // All model / coder work happens in libslimfastq_amd.so on the GPU; this file parses arguments, reads and
 // writes files and fills the info page.
 #include <sys/stat.h>
@@ -110,6 +111,12 @@ static void usage() {
            "-x fasta|names|bases|quals : with -d: write those lines of every record only, picked on the GPU before the text comes back --\n"
            "                   FASTA (lines 1 and 2, '>' for '@'), the names (line 1 without its '@'), the base lines or the quality lines;\n"
            "                   goes with -R, -p, -W, -K and -b (-p and -W write each mate's lines to its file)\n"
+           "-k terms         : with -d: write only the records that pass a filter, chosen on the GPU before the text comes back; terms is a\n"
+           "                   comma-separated list of minlen=N, maxlen=N (bases), maxn=N (N bases at most), meanq=Q (mean quality at least Q,\n"
+           "                   Phred+33, up to two fraction digits), seq=MOTIF (the base line holds it; at most 32 of ACGT, either case), rc\n"
+           "                   (or its reverse complement), invert (the records that fail), sample=F[:SEED] (a reproducible share 0 < F < 1)\n"
+           "                   and either; an archive written with -p keeps or drops whole pairs: where both mates pass, with either where\n"
+           "                   one does; goes with -R, -W, -p, -x, -K and -b; without -q one line on stderr says what was kept\n"
            "-M               : with -p on a compress run: compare the names of every pair of mates on the GPU before it is coded (the\n"
            "                   header's first word, without a final /1 or /2); a pair that differs ends the run with its index and both\n"
            "                   names, and no archive is written\n"
@@ -149,6 +156,8 @@ struct Opts {
     bool window = false; uint64_t w_first = 0, w_count = 0;            // -W first:count (pairs)
     bool mates = false;                                                // -M
     int pick = 0; std::string pick_name;                               // -x: SFQ_PICK_* (0 = none, -1 = no such word) and the word
+    bool select = false; std::string select_spec;                      // -k terms
+    sfq_select sel; bool sel_either = false;                           // ... parsed: the rule (its range and pairs are the decode's), `either`
 };
 // "FIRST:COUNT", both decimal, COUNT > 0
 static bool parse_range(const char* t, uint64_t& first, uint64_t& count) {
@@ -690,6 +699,9 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         r_lo = 2 * o.w_first; r_hi = o.w_count > total - o.w_first ? 2 * total : r_lo + 2 * o.w_count;
     }
     const bool paired = !o.pair.empty();
+    // -k: an archive written from paired files keeps or drops whole pairs, split (-p, -W) or not
+    const bool sel_pairs = o.select && a.get_long("usr.pair", 0) == 1;
+    if (o.select && o.sel_either && !sel_pairs) croak("-k either: %s was not written from paired files (no usr.pair in its info): its records stand alone", fil.c_str());
     if (paired && a.get_long("usr.pair", 0) != 1) croak("-p: %s was not written from paired files (no usr.pair in its info): decode it without -p", fil.c_str());
     FILE* of = stdout;
     FILE* of2 = nullptr;
@@ -716,6 +728,8 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     if (sfq_ctx_set_checksums(ctx, 0)) croak("%s", sfq_last_error(ctx));
     if (sfq_ctx_set_pair_split(ctx, paired ? 1 : 0)) croak("%s", sfq_last_error(ctx));
     if (sfq_ctx_set_pick(ctx, o.pick)) croak("%s", sfq_last_error(ctx));
+    if (sfq_ctx_set_select(ctx, nullptr)) croak("%s", sfq_last_error(ctx));       // (set per segment: the range and the index base are the segment's)
+    uint64_t sel_kept = 0, sel_seen = 0, sel_bytes = 0, sel_text = 0;
     const uint64_t rec_lines = !o.pick ? 4 : o.pick == SFQ_PICK_FASTA ? 2 : 1;      // the lines of a record in what a call hands back
     // walk the segments: each one's blocks, its slice of every stream (streams are segment-major), its prior
     size_t b0 = 0, pri_off = 0, chn_off = 0, rpr_off = 0;
@@ -788,6 +802,24 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         //  or, where the window's lines alone outgrow it, a damaged stream: then the segment's size is tried)
         const uint64_t cap_seg = cap;
         if (ranged && wn < sb.size()) cap = std::min<uint64_t>(cap_seg, cap_seg / sb.size() * wn * 2 + (1 << 20));
+        if (o.select) {
+            // the range: the segment's share of -R, counted from the decoded text's first record (-W: the library cuts to the window's
+            // pairs itself); index_base: that record's number in the archive, so that a sample does not depend on segments or windows
+            sfq_select sel = o.sel;
+            const uint64_t text0 = rec0 + sb[w0].first_record;
+            sel.pairs = sel_pairs ? (o.sel_either ? SFQ_SELECT_EITHER : SFQ_SELECT_BOTH) : 0;
+            sel.index_base = text0;
+            if (o.range) {
+                uint64_t wrecs = 0;
+                for (uint32_t b = w0; b < w0 + wn; b++) wrecs += sb[b].n_records;
+                const uint64_t lo = std::max(r_lo, text0), hi = std::min(r_hi, text0 + wrecs);
+                sel.first_record = lo - text0; sel.n_records = hi - lo;
+            }
+            if (sel.pairs && (text0 & 1)) croak("-k: the blocks of %s hold odd numbers of records, so that a decoded text begins at a second mate (record %llu): "
+                                                "pairs are selected from archives written with an even -B", fil.c_str(), (unsigned long long)text0);
+            if (sfq_ctx_set_select(ctx, &sel))
+                croak("-k: %s%s", sfq_last_error(ctx), sel.pairs ? " (an archive written with -p is selected pair by pair: a range begins at a first mate)" : "");
+        }
         sfq_result res;
         int rc = 0;
         uint8_t* dst = nullptr;
@@ -818,7 +850,12 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         if (rc) croak("%s", sfq_last_error(ctx));
         tick("sfq_decode_blocks_host");
         const bool in_out = dst == out.p;                              // (not a page-locked buffer: written before the next segment reuses it)
-        if (o.range) {                                                 // the window's first and last block, cut to records: rec_lines lines each
+        if (o.select) {
+            sfq_select_report rep;
+            if (sfq_get_select(ctx, &rep) != 1) croak("-k: the library did not select");
+            sel_kept += rep.n_kept; sel_seen += rep.n_in_range; sel_bytes += rep.kept_bytes; sel_text += rep.text_bytes;
+        }
+        if (o.range && !o.select) {                                    // the window's first and last block, cut to records: rec_lines lines each
             const uint64_t wrec0 = rec0 + (uint64_t)w0 * sb[0].n_records;
             const uint64_t lo = std::max(r_lo, wrec0), hi = std::min(r_hi, wrec0 + res.n_records);
             const size_t from = records_end(dst, (size_t)got, lo - wrec0, rec_lines);
@@ -827,7 +864,7 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         }
         // -p: the call handed back the first mates, then (from `first` on) the second mates
         uint64_t first = got;
-        if (paired && sfq_get_pair_split(ctx, &first, nullptr) != 1) croak("-p: the library did not split the text");
+        if (paired && got && sfq_get_pair_split(ctx, &first, nullptr) != 1) croak("-p: the library did not split the text");
         auto write_out = [dst, got, first, of, of2]() {
             return fwrite(dst, 1, (size_t)first, of) == first && (got == first || fwrite(dst + first, 1, (size_t)(got - first), of2) == got - first);
         };
@@ -845,6 +882,9 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     if (wbad) croak("USR: Error writing output");
     if (of != stdout) fclose(of); else fflush(stdout);
     if (of2) fclose(of2);
+    if (o.select && !o.quiet)
+        fprintf(stderr, "kept %llu of %llu records (%llu of %llu bytes)\n", (unsigned long long)sel_kept, (unsigned long long)sel_seen,
+                (unsigned long long)sel_bytes, (unsigned long long)sel_text);
 }
 
 int main(int argc, char** argv) {
@@ -852,7 +892,7 @@ int main(int argc, char** argv) {
     Opts o;
     bool statistics = false;
     if (argc == 1) usage();
-    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKYM1234u:f:l:B:g:S:T:C:t:R:Q:p:W:x:")) != -1;) {
+    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKYM1234u:f:l:B:g:S:T:C:t:R:Q:p:W:x:k:")) != -1;) {
         switch (opt) {
         case 'u': g_usr = optarg; break;
         case 'f': fil = optarg; break;
@@ -891,6 +931,7 @@ int main(int argc, char** argv) {
             o.pick = o.pick_name == "fasta" ? SFQ_PICK_FASTA : o.pick_name == "names" ? SFQ_PICK_NAMES : o.pick_name == "bases" ? SFQ_PICK_BASES :
                      o.pick_name == "quals" ? SFQ_PICK_QUALS : -1;
             break;
+        case 'k': o.select = true; o.select_spec = optarg; break;
         case 'C': o.chain_reads = strtol(optarg, 0, 0); break;
         case 't': o.io_threads = std::min(64, std::max(1, atoi(optarg))); break;
         case 'v': printf("Version %s\nInternal format version=%u (block format %u)\n", kUserVersion, kInternalVersion, kBlockVersion); exit(0);
@@ -937,6 +978,20 @@ int main(int argc, char** argv) {
     if (o.pick && (g_encode || statistics)) {
         fprintf(stderr, "slimfastq: -x (picked lines) goes with -d: it picks the lines a decode writes%s\n", statistics ? "; -s writes no text" : "");
         return 1;
+    }
+
+    if (o.select) {
+        char err[256] = "";
+        int either = 0;
+        if (sfq_select_parse(o.select_spec.c_str(), &o.sel, &either, err, sizeof err)) {
+            fprintf(stderr, "slimfastq: -k %s: %s\n", o.select_spec.c_str(), err);
+            return 1;
+        }
+        o.sel_either = either != 0;
+        if (g_encode || statistics) {
+            fprintf(stderr, "slimfastq: -k (selected records) goes with -d: it chooses the records a decode writes%s\n", statistics ? "; -s writes no text" : "");
+            return 1;
+        }
     }
 
     if (!o.pair.empty() && g_batch) {

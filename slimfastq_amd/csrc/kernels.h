@@ -337,3 +337,37 @@ struct PickJob { u32 what, pad; u64 r0, nr, out_cap, mark; };
 // t.starts: from[cap]; to[cap]; lens[nlens], dst[nlens + 1], scan_tmp as launch_scan_u32 wants it for nlens, where nlens = min(nr, cap);
 // info: zeroed by the caller.  out: job.out_cap bytes, of which info->nout are written, and none unless info->status stays 0.
 void launch_pick(const PairText& t, u64* to, u64 cap, const PickJob& job, u32* lens, u64* dst, u64* scan_tmp, u64 nlens, u8* out, PickInfo* info, hipStream_t st);
+// its copy alone, for the passes whose pieces are whole records (sel.hip): P = info->pieces pieces, piece k = text[from[info->r0 + k] ..) to
+// out + dst[k], dst[P] = info->nout; bound: what the output can hold at most (the grid).  Nothing runs where info->status is set.
+void launch_pick_copy(const u64* dst, const u64* from, const u8* text, u64 bound, u8* out, PickInfo* info, hipStream_t st);
+
+// Selected records (sel.hip): the records of [r0, r0 + nr) that pass a filter on their content -- the base line's length, its N count,
+// the quality line's mean, a motif in the base line -- and a reproducible sample, whole and in order.  Like pick.hip the pass finds the
+// lines itself, decides every refusal on the device and copies with pick.hip's copy; *info tells the host, which synchronises once.
+enum SelStatus : u32 {
+    SEL_OK = 0,
+    SEL_LINES,              // the text's lines are no multiple of four
+    SEL_RANGE,              // records that end behind the text's last record
+    SEL_CAP,                // more records than the arrays hold: info->recs says how many, nothing else was done
+    SEL_LONG,               // a record of 4 GiB or more
+    SEL_ODD,                // pairs: an odd number of records in the range
+    SEL_ROOM                // the kept records need more than the output holds: info->copy.nout says how much
+};
+// copy: what k_pick_copy reads -- r0 = 0, pieces = the records kept, nout = their bytes, status != 0 wherever there is nothing to copy
+// (a refusal, or no record kept: SEL_NOTHING there while status stays SEL_OK).  r0, nr: the range as the check found it.
+constexpr u32 SEL_NOTHING = 0x100;
+struct SelInfo { PickInfo copy; u64 lines, recs, r0, nr; u32 status, pad; u64 n_fail[4]; };
+// the rule (slimfastq_amd.h sfq_select); motif, motif_rev: two bits a base, (byte >> 1) & 3, the first base in the lowest bits
+// (motif_rev = motif where the reverse complement does not count); nr = ~0: to the text's last record
+struct SelJob {
+    u64 r0, nr, out_cap;
+    u32 min_len, max_len, max_n, min_q, qual_base, motif_len, invert, pairs, sample, pad;
+    u64 seed, index_base, motif, motif_rev;
+};
+// ls[4 cap + 1]: where every line begins (ls[lines] = the text's end, one more where its last line has no '\n': a line's length is
+// ls[l + 1] - ls[l] - 1 throughout); acc[2 cap]: per base line its N count, per quality line its byte sum; hit[cap]: the motif occurs;
+// keep, rlen, lens, from: nlens entries, pos, dst: nlens + 1, tmp as launch_scan_u32 wants it for nlens; nlens = min(nr, cap)
+struct SelArrays { u64* ls; u64* acc; u8* hit; u32* keep; u32* rlen; u64* pos; u32* lens; u64* from; u64* dst; u64* tmp; u64 cap, nlens; };
+// t.starts is not used (A.ls is the pass's own); info: zeroed by the caller.  out: job.out_cap bytes, of which info->copy.nout are
+// written, and none unless info->status and info->copy.status stay 0.
+void launch_select(const PairText& t, const SelArrays& A, const SelJob& job, u8* out, SelInfo* info, hipStream_t st);

@@ -248,6 +248,19 @@ PickLines pick_lines_of(u32 what, u64* from, u64* to, u64 cap) {
 
 }  // namespace
 
+// the copy's grid: over what the output can hold of the text
+static void launch_pick_copy(const u64* dst, const u64* from, const u8* text, u64 bound, u8* out, PickInfo* info, hipStream_t st, bool gt) {
+    const u32 omis = (u32)((uintptr_t)out & 15);
+    const u64 ospans = (omis + bound + SPAN - 1) / SPAN, otiles = ospans ? (ospans + 3) / 4 : 1;
+    const CopyJob J{ dst, from, (u64)(uintptr_t)text, bound };
+    const dim3 grid((u32)(otiles < MAX_WG ? otiles : MAX_WG));
+    if (gt) hipLaunchKernelGGL(k_pick_copy<true>, grid, dim3(256), 0, st, J, info, out - omis, omis, ospans);
+    else hipLaunchKernelGGL(k_pick_copy<false>, grid, dim3(256), 0, st, J, info, out - omis, omis, ospans);
+}
+void launch_pick_copy(const u64* dst, const u64* from, const u8* text, u64 bound, u8* out, PickInfo* info, hipStream_t st) {
+    launch_pick_copy(dst, from, text, bound, out, info, st, false);
+}
+
 void launch_pick(const PairText& t, u64* to, u64 cap, const PickJob& job, u32* lens, u64* dst, u64* scan_tmp, u64 nlens, u8* out, PickInfo* info, hipStream_t st) {
     const QmapScratch q = qmap_scratch(t.d, t.n);
     const u32 mis = (u32)((uintptr_t)t.d & 15);
@@ -263,12 +276,5 @@ void launch_pick(const PairText& t, u64* to, u64 cap, const PickJob& job, u32* l
     hipLaunchKernelGGL(k_pick_lens, dim3((u32)((nlens + 255) / 256)), dim3(256), 0, st, info, L, t.d, first, lens, nlens);
     launch_scan_u32(lens, dst, nlens, scan_tmp, st);
     hipLaunchKernelGGL(k_pick_room, dim3(1), dim3(64), 0, st, info, L, (const u64*)dst, job.out_cap, job.mark);
-    // the copy's grid: over what the output can hold of the text
-    const u32 omis = (u32)((uintptr_t)out & 15);
-    const u64 bound = job.out_cap < t.n ? job.out_cap : t.n;
-    const u64 ospans = (omis + bound + SPAN - 1) / SPAN, otiles = ospans ? (ospans + 3) / 4 : 1;
-    const CopyJob J{ dst, t.starts, (u64)(uintptr_t)t.d, bound };
-    const dim3 grid((u32)(otiles < MAX_WG ? otiles : MAX_WG));
-    if (job.what == PICK_FASTA) hipLaunchKernelGGL(k_pick_copy<true>, grid, dim3(256), 0, st, J, info, out - omis, omis, ospans);
-    else hipLaunchKernelGGL(k_pick_copy<false>, grid, dim3(256), 0, st, J, info, out - omis, omis, ospans);
+    launch_pick_copy(dst, t.starts, t.d, job.out_cap < t.n ? job.out_cap : t.n, out, info, st, job.what == PICK_FASTA);
 }
