@@ -564,6 +564,78 @@ int sfq_ctx_set_select(sfq_ctx* ctx, const sfq_select* sel);
 /* 1: the last decode call selected, *out = what it found; 0: it did not (*out zeroed) */
 int sfq_get_select(const sfq_ctx* ctx, sfq_select_report* out);
 
+/* ---- trimmed records ----------------------------------------------------------------------------------------------------------
+ * What a consumer of FASTQ does first is trim: crop fixed ends, cut low-quality ends, clip the read-through adapter.  The pass
+ * (trim.hip) does it while the text is on the device, text to text like the selected records, whose line starts and copy it uses; no
+ * stream, coder or block format knows of it.  It is the first pass that changes a record's inside: NO RECORD IS EVER DROPPED, a record
+ * cut to nothing keeps its four lines, two of them empty (sfq_select's min_len is what drops it).
+ * Lines and records: they are sfq_pick_lines' own.  A line ends at '\n'; a text without a final '\n' still ends in a line; '\r' is a
+ *   byte like any other.  Lengths exclude the '\n'.
+ * The rule, for one record: L = the length of line 2, which line 4 must share; q(p) = line4[p] - qual_base, signed.  Every term is a
+ * function of the ORIGINAL record alone, so the terms have no order, and the cut is their intersection:
+ *   a_head  = min(head, L)                                   b_tail  = L - min(tail, L)
+ *   a_lead  = lead_q  ? smallest p with q(p) >= lead_q  (L if none)      : 0
+ *   b_trail = trail_q ? 1 + largest p with q(p) >= trail_q (0 if none)   : L
+ *   b_win   = win_len ? smallest p in [0, L - win_len] with
+ *                       100 * sum_{j<win_len} q(p+j) < win_q_x100 * win_len   (signed 64-bit; L if none, L if L < win_len) : L
+ *   b_ad    = adapter_len ? smallest p in [0, L) at which the adapter matches (L if none) : L
+ *   s = max(a_head, a_lead);  e = min(b_tail, b_trail, b_win, b_ad);  if e < s: e = s
+ *   if max_len != UINT32_MAX: e = min(e, s + max_len)
+ * The adapter matches at p when k = min(adapter_len, L - p) is at least adapter_min (a partial overlap at the 3' end) and the number
+ *   of j < k with upper(line2[p+j]) != adapter[j] is at most adapter_mm * k / adapter_len (integer division).  A byte that is none of
+ *   ACGTacgt mismatches every adapter byte: an N in the read is a mismatch.  An occurrence never runs across a line end, and only
+ *   line 2 is compared (ACGT are legal quality and header bytes).
+ * The output record is line 1, bytes [s, e) of line 2, line 3, bytes [s, e) of line 4, each with the '\n' it had (the last line of a
+ *   text without a final '\n' still lacks it; where THAT line is cut to nothing the result ends in an empty line without a line end,
+ *   which no reader can tell from no line -- the texts of a decode end in '\n').  Records stay in step, so the pair split, the pair window and the pick run unchanged on
+ *   a trimmed text.  The result is never larger than the text: out_cap = n always suffices.  With every term off it is the text. */
+typedef struct sfq_trim {
+    uint32_t head, tail;          /* 0 = off */
+    uint32_t max_len;             /* UINT32_MAX = off; 0 is legal (every base line empty) */
+    uint32_t lead_q, trail_q;     /* 0 = off */
+    uint32_t win_len;             /* 0 = off, at most 32 */
+    uint32_t win_q_x100;
+    uint32_t qual_base;           /* <= 126 */
+    uint32_t adapter_len;         /* 0 = off, at most 32 */
+    uint8_t  adapter[32];         /* 'A' 'C' 'G' 'T' only */
+    uint32_t adapter_mm;          /* <= adapter_len */
+    uint32_t adapter_min;         /* with an adapter: 1 .. adapter_len */
+} sfq_trim;
+typedef struct sfq_trim_report {
+    uint64_t n_records, n_changed, n_emptied;      /* changed: (s, e) != (0, L); emptied: L > 0 and s == e */
+    uint64_t text_bytes, out_bytes, bases_in, bases_out;
+    uint64_t n_cut[4];            /* records where lead_q / trail_q / the window / the adapter ALONE cuts a base (a_lead > 0, b_trail < L, b_win < L, b_ad < L); 0 for a term that is off */
+} sfq_trim_report;
+/* host only, no GPU: SFQ_OK, or SFQ_E_ARG for a null pointer, win_len or adapter_len over 32, an adapter byte outside ACGT,
+ * adapter_mm > adapter_len, adapter_min outside 1 .. adapter_len while an adapter is on, or qual_base > 126 */
+int sfq_trim_check(const sfq_trim* trim);
+/* host only, no GPU: a rule from the CLI's -c SPEC, a comma-separated list of the terms head=N, tail=N, maxlen=N, q5=Q, q3=Q (lead_q,
+ * trail_q: integers), win=W:Q (Q a decimal with up to two fraction digits), adapter=SEQ (either case, stored upper case), mm=N and
+ * overlap=N (adapter_mm, adapter_min).  *trim: the rule, every term that is not named off, qual_base = 33, mm = 0,
+ * overlap = min(3, adapter_len).  SFQ_E_ARG for an unknown term, a bad number, mm or overlap without an adapter, or a rule that
+ * sfq_trim_check refuses; err (may be NULL) then says which term. */
+int sfq_trim_parse(const char* spec, sfq_trim* trim, char* err, uint64_t err_cap);
+/* The records of d_text[0, n), trimmed, into d_out; *out_bytes = the bytes of the result (on SFQ_E_OVERFLOW: the size needed).
+ * SFQ_E_ARG: a null pointer (report may be NULL), n == 0, a struct that sfq_trim_check refuses.  SFQ_E_FORMAT: lines that are no
+ * multiple of four, or a record whose lines 2 and 4 differ in length -- a trim has no meaning there; sfq_last_error names the smallest
+ * such record and its byte offset.  SFQ_E_UNSUPPORTED: a line of 4 GiB or more (or a record whose lines together hold as much).
+ * SFQ_E_OVERFLOW: a result larger than out_cap.  Every refusal is decided on the device before the copy: a refused call writes
+ * nothing.  A call that succeeds writes d_out[0, *out_bytes) and nothing else.  d_out must not overlap the text.  The call runs on
+ * the context's stream and synchronises once.  Like the other side passes, it may read the whole aligned 16-byte units that hold the
+ * text's first and last byte. */
+int sfq_trim_records(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, const sfq_trim* trim,
+                     uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_trim_report* report);
+/* trim != NULL: sfq_decode_blocks_host, sfq_decode_block_range_host and sfq_decode_pair_range_host trim the text they decoded (the
+ * struct is copied; SFQ_E_ARG, and the setting stays, where sfq_trim_check refuses it); NULL: off (default).  The trim is the FIRST
+ * pass behind the checksum pass: the CRCs, installed ones included, stay those of the decoded text.  It runs in front of the selection,
+ * of the pair split or the pair window's cut, and of the pick: all of them see an ordinary FASTQ text whose record numbering is
+ * unchanged, and a selection's min_len judges the trimmed length.  out_cap keeps sizing the DECODED text.  Costs one more device
+ * buffer of the text's size, held while the switch is on.  The device-pointer decode entries are not affected.  Default off: nothing
+ * is launched, allocated or copied that is not today. */
+int sfq_ctx_set_trim(sfq_ctx* ctx, const sfq_trim* trim);
+/* 1: the last decode call trimmed, *out = what it found; 0: it did not (*out zeroed) */
+int sfq_get_trim(const sfq_ctx* ctx, sfq_trim_report* out);
+
 /* ---- the ".sfq" container (host only) ----------------------------------------------------------
  * Replaces FilerSave + the info page (filer.cpp:217-242, config.cpp:334-347) for hosts that assemble an archive
  * themselves: info_text is the info page ("key=value\n" lines), then n_streams named byte streams (names of at most

@@ -41,6 +41,7 @@ EXPORTS = [
     "sfq_split_pairs_range", "sfq_check_mates", "sfq_ctx_set_mate_check", "sfq_get_mate_report", "sfq_pair_window_blocks",
     "sfq_decode_pair_range_host", "sfq_pick_lines", "sfq_ctx_set_pick", "sfq_get_pick",
     "sfq_select_check", "sfq_select_parse", "sfq_select_records", "sfq_ctx_set_select", "sfq_get_select",
+    "sfq_trim_check", "sfq_trim_parse", "sfq_trim_records", "sfq_ctx_set_trim", "sfq_get_trim",
 ]
 
 
@@ -139,6 +140,43 @@ def select_parse(spec: str):
     if lib().sfq_select_parse(spec.encode(), C.byref(sel), C.byref(either), err, 256):
         raise ValueError(err.value.decode("latin1"))
     return sel, bool(either.value)
+
+
+class Trim(C.Structure):
+    """sfq_trim: the rule of a trim (trim.hip).  Trim() is the rule that changes nothing: every term off."""
+    _fields_ = [("head", C.c_uint32), ("tail", C.c_uint32), ("max_len", C.c_uint32), ("lead_q", C.c_uint32), ("trail_q", C.c_uint32),
+                ("win_len", C.c_uint32), ("win_q_x100", C.c_uint32), ("qual_base", C.c_uint32), ("adapter_len", C.c_uint32),
+                ("adapter", C.c_uint8 * 32), ("adapter_mm", C.c_uint32), ("adapter_min", C.c_uint32)]
+
+    def __init__(self, head=0, tail=0, max_len=0xFFFFFFFF, lead_q=0, trail_q=0, win_len=0, win_q_x100=0, qual_base=33, adapter=b"",
+                 adapter_mm=0, adapter_min=None, adapter_len=None):
+        super().__init__()
+        self.head, self.tail, self.max_len, self.lead_q, self.trail_q = head, tail, max_len, lead_q, trail_q
+        self.win_len, self.win_q_x100, self.qual_base = win_len, win_q_x100, qual_base
+        self.adapter_len = len(adapter) if adapter_len is None else adapter_len
+        for i, b in enumerate(bytes(adapter)[:32]):
+            self.adapter[i] = b
+        self.adapter_mm = adapter_mm
+        self.adapter_min = min(3, len(adapter)) if adapter_min is None else adapter_min
+
+
+class TrimReport(C.Structure):
+    """sfq_trim_report: what a trim found."""
+    _fields_ = [("n_records", C.c_uint64), ("n_changed", C.c_uint64), ("n_emptied", C.c_uint64), ("text_bytes", C.c_uint64),
+                ("out_bytes", C.c_uint64), ("bases_in", C.c_uint64), ("bases_out", C.c_uint64), ("n_cut", C.c_uint64 * 4)]
+
+
+def trim_check(trim) -> int:
+    """sfq_trim_check (no GPU): 0, or E_ARG for a rule the library refuses."""
+    return int(lib().sfq_trim_check(C.byref(trim)))
+
+
+def trim_parse(spec: str):
+    """sfq_trim_parse (no GPU): the Trim of the CLI's -c SPEC; ValueError with the library's words where it refuses."""
+    trim, err = Trim(), C.create_string_buffer(256)
+    if lib().sfq_trim_parse(spec.encode(), C.byref(trim), err, 256):
+        raise ValueError(err.value.decode("latin1"))
+    return trim
 
 
 class SfqError(RuntimeError):
@@ -268,6 +306,11 @@ def lib():
         L.sfq_select_records.argtypes = [vp, vp, u64, C.POINTER(Select), vp, u64, u64p, C.POINTER(SelectReport)]
         L.sfq_ctx_set_select.argtypes = [vp, C.POINTER(Select)]
         L.sfq_get_select.argtypes = [vp, C.POINTER(SelectReport)]
+        L.sfq_trim_check.argtypes = [C.POINTER(Trim)]
+        L.sfq_trim_parse.argtypes = [C.c_char_p, C.POINTER(Trim), C.c_char_p, u64]
+        L.sfq_trim_records.argtypes = [vp, vp, u64, C.POINTER(Trim), vp, u64, u64p, C.POINTER(TrimReport)]
+        L.sfq_ctx_set_trim.argtypes = [vp, C.POINTER(Trim)]
+        L.sfq_get_trim.argtypes = [vp, C.POINTER(TrimReport)]
         _lib = L
     return _lib
 
@@ -596,6 +639,32 @@ class Context:
         """The SelectReport of the last decode call; None where it did not select."""
         rep = SelectReport()
         rc = lib().sfq_get_select(self._h, C.byref(rep))
+        if rc < 0:
+            self._check(rc)
+        return rep if rc == 1 else None
+
+    def trim_records(self, d_text, nbytes, trim, d_out, out_cap):
+        """The records of the FASTQ text in the device buffer at d_text, trimmed by the Trim, into the one at d_out
+        (sfq_trim_records); returns (bytes written, TrimReport).  An SfqError of code E_OVERFLOW carries the size needed as .needed."""
+        n, rep = C.c_uint64(), TrimReport()
+        rc = lib().sfq_trim_records(self._h, C.c_void_p(d_text), int(nbytes), C.byref(trim), C.c_void_p(d_out), int(out_cap),
+                                    C.byref(n), C.byref(rep))
+        try:
+            self._check(rc)
+        except SfqError as e:
+            e.needed = int(n.value)
+            raise
+        return int(n.value), rep
+
+    def set_trim(self, trim=None):
+        """A Trim: decode_host, decode_range_host and decode_pair_range_host trim the text they decoded before every other pass
+        (get_trim() says what was cut); None: off."""
+        self._check(lib().sfq_ctx_set_trim(self._h, None if trim is None else C.byref(trim)))
+
+    def get_trim(self):
+        """The TrimReport of the last decode call; None where it did not trim."""
+        rep = TrimReport()
+        rc = lib().sfq_get_trim(self._h, C.byref(rep))
         if rc < 0:
             self._check(rc)
         return rep if rc == 1 else None

@@ -207,6 +207,10 @@ struct sfq_ctx {
     bool sel_on = false; sfq_select sel{};            // sfq_ctx_set_select
     DevBuf sel_out;                                   // the selected records of a decoded text (while the switch is on)
     bool sel_done = false; sfq_select_report sel_report{};    // the last decode call's
+    // trimmed records (trim.hip): works in pair_work and reports through pair_pin too; nothing of this exists until the switch is on
+    bool trim_on = false; sfq_trim trim{};            // sfq_ctx_set_trim
+    DevBuf trim_out;                                  // the trimmed text of a decoded text (while the switch is on)
+    bool trim_done = false; sfq_trim_report trim_report{};    // the last decode call's
 };
 
 namespace {
@@ -969,7 +973,7 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
         &ctx->oflags, &ctx->okbytes, &ctx->ofpos, &ctx->okoff, &ctx->ofilt, &ctx->orecmap, &ctx->olist, &ctx->line_off_o, &ctx->ono, &ctx->opiece,
         &ctx->otxt[0], &ctx->otxt[1], &ctx->otxt[2], &ctx->osize_all, &ctx->oroff_all, &ctx->oroff_k, &ctx->ocnt,
         &ctx->crc_tab, &ctx->crc_tiles, &ctx->crc_grps, &ctx->crc_bounds, &ctx->crc_out, &ctx->stats_acc, &ctx->qmap_dev,
-        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out, &ctx->pick_out, &ctx->sel_out };
+        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out, &ctx->pick_out, &ctx->sel_out, &ctx->trim_out };
     for (DevBuf* b : all) release(*b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->pin2) (void)hipHostFree(ctx->pin2);
@@ -2402,6 +2406,180 @@ int sfq_get_select(const sfq_ctx* ctx, sfq_select_report* out) {
     return 1;
 }
 
+// ---- trimmed records (trim.hip) ---------------------------------------------------------------------------------------------------
+int sfq_trim_check(const sfq_trim* t) {
+    if (!t) return SFQ_E_ARG;
+    if (t->win_len > 32 || t->adapter_len > 32 || t->qual_base > 126 || t->adapter_mm > t->adapter_len) return SFQ_E_ARG;
+    if (t->adapter_len && (t->adapter_min < 1 || t->adapter_min > t->adapter_len)) return SFQ_E_ARG;
+    for (u32 i = 0; i < t->adapter_len; i++)
+        if (t->adapter[i] != 'A' && t->adapter[i] != 'C' && t->adapter[i] != 'G' && t->adapter[i] != 'T') return SFQ_E_ARG;
+    return SFQ_OK;
+}
+// "term,term,...": see slimfastq_amd.h
+int sfq_trim_parse(const char* spec, sfq_trim* trim, char* err, uint64_t err_cap) {
+    auto bad = [&](const char* fmt, const std::string& what) {
+        if (err && err_cap) snprintf(err, (size_t)err_cap, fmt, what.c_str());
+        return SFQ_E_ARG;
+    };
+    if (!spec || !trim) return SFQ_E_ARG;
+    memset(trim, 0, sizeof *trim);
+    trim->max_len = ~0u; trim->qual_base = 33;
+    auto number = [](const std::string& t, u64 max, u64* v) {      // decimal digits only, at most max
+        if (t.empty() || t.size() > 19) return false;
+        u64 x = 0;
+        for (char c : t) { if (c < '0' || c > '9') return false; x = x * 10 + (u64)(c - '0'); }
+        *v = x;
+        return x <= max;
+    };
+    const std::string all = spec;
+    if (all.empty()) return bad("an empty list of terms%s", "");
+    bool has_mm = false, has_overlap = false;
+    for (size_t at = 0; at <= all.size(); ) {
+        const size_t comma = std::min(all.find(',', at), all.size());
+        const std::string term = all.substr(at, comma - at);
+        at = comma + 1;
+        const size_t eq = term.find('=');
+        const std::string key = term.substr(0, eq), val = eq == std::string::npos ? "" : term.substr(eq + 1);
+        const bool has = eq != std::string::npos;
+        u64 v = 0;
+        if (key == "head" && has) { if (!number(val, 0xFFFFFFFFull, &v)) return bad("head=%s: not a number of bases", val); trim->head = (u32)v; }
+        else if (key == "tail" && has) { if (!number(val, 0xFFFFFFFFull, &v)) return bad("tail=%s: not a number of bases", val); trim->tail = (u32)v; }
+        else if (key == "maxlen" && has) { if (!number(val, 0xFFFFFFFEull, &v)) return bad("maxlen=%s: not a number of bases", val); trim->max_len = (u32)v; }
+        else if (key == "q5" && has) { if (!number(val, 0xFFFFFFFFull, &v)) return bad("q5=%s: not a quality", val); trim->lead_q = (u32)v; }
+        else if (key == "q3" && has) { if (!number(val, 0xFFFFFFFFull, &v)) return bad("q3=%s: not a quality", val); trim->trail_q = (u32)v; }
+        else if (key == "win" && has) {                        // W:Q, Q a decimal with up to two fraction digits, times 100
+            const size_t colon = val.find(':');
+            const std::string ws = val.substr(0, colon), qs = colon == std::string::npos ? "" : val.substr(colon + 1);
+            const size_t dot = qs.find('.');
+            std::string ip = qs.substr(0, dot), fp = dot == std::string::npos ? "" : qs.substr(dot + 1);
+            u64 w = 0, f = 0;
+            if (colon == std::string::npos || !number(ws, 32, &w) || !w) return bad("win=%s: a window of 1 to 32 bases and a mean quality, as W:Q", val);
+            if (dot != std::string::npos && (fp.empty() || fp.size() > 2)) return bad("win=%s: the quality is a decimal with up to two fraction digits", val);
+            if (fp.size() == 1) fp += "0";
+            if (!number(ip, 40000000ull, &v) || (!fp.empty() && !number(fp, 99, &f))) return bad("win=%s: the quality is a decimal with up to two fraction digits", val);
+            trim->win_len = (u32)w; trim->win_q_x100 = (u32)(v * 100 + f);
+        } else if (key == "adapter" && has) {
+            if (val.empty() || val.size() > 32) return bad("adapter=%s: an adapter holds 1 to 32 bases", val);
+            for (size_t i = 0; i < val.size(); i++) {
+                const char c = (char)(val[i] & ~0x20);
+                if (c != 'A' && c != 'C' && c != 'G' && c != 'T') return bad("adapter=%s: an adapter holds the bases ACGT only", val);
+                trim->adapter[i] = (u8)c;
+            }
+            trim->adapter_len = (u32)val.size();
+        } else if (key == "mm" && has) { if (!number(val, 0xFFFFFFFFull, &v)) return bad("mm=%s: not a number of mismatches", val); trim->adapter_mm = (u32)v; has_mm = true; }
+        else if (key == "overlap" && has) { if (!number(val, 0xFFFFFFFFull, &v)) return bad("overlap=%s: not a number of bases", val); trim->adapter_min = (u32)v; has_overlap = true; }
+        else return bad("%s: no such term (head= tail= maxlen= q5= q3= win= adapter= mm= overlap=)", term);
+    }
+    if (has_mm && !trim->adapter_len) return bad("mm= goes with adapter=SEQ%s", "");
+    if (has_overlap && !trim->adapter_len) return bad("overlap= goes with adapter=SEQ%s", "");
+    if (trim->adapter_len && !has_overlap) trim->adapter_min = std::min(3u, trim->adapter_len);
+    if (trim->adapter_mm > trim->adapter_len) return bad("mm= above the adapter's length%s", "");
+    if (trim->adapter_len && (trim->adapter_min < 1 || trim->adapter_min > trim->adapter_len)) return bad("overlap= is 1 to the adapter's length%s", "");
+    if (sfq_trim_check(trim)) return bad("a rule that sfq_trim_check refuses%s", "");
+    return SFQ_OK;
+}
+// select_run's shape: one pass on the context's stream, one synchronise, in pair_run's working buffers and with its sizing; only a
+// text with more records than the arrays were laid out for runs twice.  *rep: what the device found (out_bytes on SFQ_E_OVERFLOW too).
+static int trim_run(sfq_ctx* ctx, const u8* text, u64 n, const sfq_trim& s, u8* out, u64 out_cap, sfq_trim_report* rep) {
+    int rc;
+    const size_t infos = std::max({ sizeof(PairInfo), sizeof(PickInfo), sizeof(SelInfo), sizeof(TrimInfo) });
+    if ((rc = reserve_pinned_buf(ctx, ctx->pair_pin, ctx->pair_pin_cap, infos))) return rc;
+    TrimJob job{};
+    job.out_cap = out_cap; job.head = s.head; job.tail = s.tail; job.max_len = s.max_len;
+    // q(p) >= Q is byte >= qual_base + Q; above 255 no byte does
+    job.lead_thr = s.lead_q ? (u32)std::min<u64>((u64)s.qual_base + s.lead_q, 256) : 0;
+    job.trail_thr = s.trail_q ? (u32)std::min<u64>((u64)s.qual_base + s.trail_q, 256) : 0;
+    // 100 * (S - base * w) < q_x100 * w is S < base * w + ceil(q_x100 * w / 100), S the window's byte sum (at most 255 * 32)
+    job.win_len = s.win_len;
+    job.win_sum = (u32)std::min<u64>((u64)s.qual_base * s.win_len + ((u64)s.win_q_x100 * s.win_len + 99) / 100, 0xFFFF);
+    job.ad_len = s.adapter_len; job.ad_mm = s.adapter_mm; job.ad_min = s.adapter_min;
+    for (u32 i = 0; i < s.adapter_len; i++) job.adapter |= (u64)((s.adapter[i] >> 1) & 3) << (2 * i);     // two bits a base, (byte >> 1) & 3
+    TrimInfo got;
+    for (int attempt = 0; ; attempt++) {
+        const u64 cap = std::max<u64>(ctx->pair_cap, n / 64 + 1024);
+        auto up = [](u64 v) { return (v + 15) & ~15ull; };
+        u64 at = up(infos);
+        const u64 sc = at; at += up(qmap_scratch(text, n).bytes);
+        const u64 ls = at; at += up((4 * cap + 1) * 8);
+        const u64 lead = at; at += up(cap * 4);
+        const u64 trail = at; at += up(cap * 4);
+        const u64 win = at; at += up(cap * 4);
+        const u64 ad = at; at += up(cap * 4);
+        const u64 se = at; at += up(cap * 8);
+        const u64 cnt = at; at += up(cap * 4);
+        const u64 pos = at; at += up((cap + 1) * 8);
+        const u64 rlen = at; at += up(cap * 4);
+        const u64 rdst = at; at += up((cap + 1) * 8);
+        const u64 from = at; at += up(5 * cap * 8);
+        const u64 dst = at; at += up(5 * cap * 8);
+        const u64 tmp = at; at += up((cap / 1024 + 2) * 8);
+        if ((rc = reserve(ctx, ctx->pair_work, (size_t)at))) return rc;
+        u8* w = (u8*)ctx->pair_work.p;
+        TrimInfo* info = (TrimInfo*)w;
+        HIPC(hipMemsetAsync(info, 0, sizeof(TrimInfo), ctx->st));
+        const PairText t{ text, n, w + sc, nullptr };
+        const TrimArrays A{ (u64*)(w + ls), (u32*)(w + lead), (u32*)(w + trail), (u32*)(w + win), (u32*)(w + ad), (u64*)(w + se), (u32*)(w + cnt),
+                            (u64*)(w + pos), (u32*)(w + rlen), (u64*)(w + rdst), (u64*)(w + from), (u64*)(w + dst), (u64*)(w + tmp), cap };
+        launch_trim(t, A, job, out, info, ctx->st);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(ctx->pair_pin, info, sizeof(TrimInfo), hipMemcpyDeviceToHost, ctx->st));
+        HIPC(hipStreamSynchronize(ctx->st));
+        memcpy(&got, ctx->pair_pin, sizeof(TrimInfo));
+        if (got.status != TRIM_CAP) break;
+        if (attempt) return fail(ctx, SFQ_E_HIP, "trimmed records: the records did not fit twice");
+        ctx->pair_cap = got.recs;
+    }
+    memset(rep, 0, sizeof *rep);
+    rep->text_bytes = n;
+    if (got.status == TRIM_LINES) return fail(ctx, SFQ_E_FORMAT, "trimmed records: the text holds %llu lines, not a multiple of four", (unsigned long long)got.lines);
+    if (got.status == TRIM_OK && got.bad_first != ~0ull)
+        return fail(ctx, SFQ_E_FORMAT, "trimmed records: record %llu (at byte %llu) has a base line and a quality line of different lengths",
+                    (unsigned long long)got.bad_first, (unsigned long long)got.bad_off);
+    if (got.status == TRIM_OK && got.toolong) return fail(ctx, SFQ_E_UNSUPPORTED, "trimmed records: a line of 4 GiB or more");
+    if (got.status == TRIM_ROOM) {
+        rep->out_bytes = got.copy.nout;
+        return fail(ctx, SFQ_E_OVERFLOW, "trimmed records: the result needs %llu bytes", (unsigned long long)got.copy.nout);
+    }
+    if (got.status != TRIM_OK || got.stop) return fail(ctx, SFQ_E_HIP, "trimmed records: status %u", got.status);
+    rep->n_records = got.recs; rep->n_changed = got.n_changed; rep->n_emptied = got.n_emptied;
+    rep->out_bytes = got.copy.nout; rep->bases_in = got.bases_in; rep->bases_out = got.bases_out;
+    for (int i = 0; i < 4; i++) rep->n_cut[i] = got.n_cut[i];
+    return SFQ_OK;
+}
+int sfq_trim_records(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, const sfq_trim* trim,
+                     uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_trim_report* report) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!d_text || !d_out || !out_bytes || !trim) return fail(ctx, SFQ_E_ARG, "null argument");
+    *out_bytes = 0;
+    if (report) memset(report, 0, sizeof *report);
+    if (!n) return fail(ctx, SFQ_E_ARG, "trimmed records: an empty text");
+    if (sfq_trim_check(trim)) return fail(ctx, SFQ_E_ARG, "trimmed records: a rule that sfq_trim_check refuses");
+    HIPC(hipSetDevice(ctx->dev));
+    Settle settle(ctx);
+    sfq_trim_report rep;
+    const int rc = trim_run(ctx, d_text, n, *trim, d_out, out_cap, &rep);
+    if (rc == SFQ_E_OVERFLOW) *out_bytes = rep.out_bytes;
+    if (rc) return rc;
+    *out_bytes = rep.out_bytes;
+    if (report) *report = rep;
+    settle.ok = true;
+    return SFQ_OK;
+}
+int sfq_ctx_set_trim(sfq_ctx* ctx, const sfq_trim* trim) {
+    if (!ctx) return SFQ_E_ARG;
+    if (trim && sfq_trim_check(trim)) return fail(ctx, SFQ_E_ARG, "trimmed records: a rule that sfq_trim_check refuses");
+    ctx->trim_on = trim != nullptr;
+    if (trim) ctx->trim = *trim;
+    else release(ctx->trim_out);
+    return SFQ_OK;
+}
+int sfq_get_trim(const sfq_ctx* ctx, sfq_trim_report* out) {
+    if (!ctx || !out) return SFQ_E_ARG;
+    if (!ctx->trim_done) { memset(out, 0, sizeof *out); return 0; }
+    *out = ctx->trim_report;
+    return 1;
+}
+
 int sfq_get_block_index(sfq_ctx* ctx, sfq_block_info* h_blocks, uint32_t cap) {
     if (!ctx || !h_blocks) return SFQ_E_ARG;
     if (cap < ctx->index.size()) return fail(ctx, SFQ_E_ARG, "index has %zu blocks", ctx->index.size());
@@ -2482,7 +2660,7 @@ static int decode_device(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_inf
     Settle settle(ctx);
     drop_encode_blobs(ctx);                             // whatever an encode left behind is not this archive's
     ctx->crcs.clear(); ctx->text_crc = 0;
-    ctx->pair_split_done = false; ctx->pick_done = 0; ctx->sel_done = false;
+    ctx->pair_split_done = false; ctx->pick_done = 0; ctx->sel_done = false; ctx->trim_done = false;
     if (w.ranged && ctx->pair_split_on && !w.pairs)
         return fail(ctx, SFQ_E_UNSUPPORTED, "a window of blocks may start at a second mate and is not split: sfq_ctx_set_pair_split(ctx, 0) comes first");
     const bool check = ex.set;
@@ -3277,6 +3455,16 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
                        stream_offset, (u8*)ctx->out_stage.p, out_cap, out_bytes, result, ex, w);
     if (rc) return rc;
     const u8* d_text = (const u8*)ctx->out_stage.p;
+    if (ctx->trim_on) {                                    // the first pass behind the checksum pass: every other pass sees the trimmed text
+        if (!*out_bytes) return fail(ctx, SFQ_E_FORMAT, "trimmed records: an empty text");
+        if ((rc = reserve(ctx, ctx->trim_out, (size_t)*out_bytes + 16))) return rc;
+        Settle settle(ctx);
+        if ((rc = trim_run(ctx, d_text, *out_bytes, ctx->trim, (u8*)ctx->trim_out.p, *out_bytes, &ctx->trim_report))) return rc;
+        settle.ok = true;
+        ctx->trim_done = true;
+        d_text = (const u8*)ctx->trim_out.p;
+        *out_bytes = ctx->trim_report.out_bytes;
+    }
     const bool selected = ctx->sel_on;
     if (selected) {                                        // the first pass behind the checksum pass: the split and the pick see what it kept
         if (!*out_bytes) return fail(ctx, SFQ_E_FORMAT, "selected records: an empty text");

@@ -16,6 +16,7 @@
 //   -W F:N    : with -d and -p: pairs F .. F + N - 1 only (numbered from 0 over the archive), cut and split on the GPU
 //   -M        : with -p on encode: the mates' names are compared on the GPU before a slab is coded; a mismatch ends the run
 //   -k terms  : with -d: the records that pass a filter only (length, N count, mean quality, a motif, a sample), chosen on the GPU
+//   -c terms  : with -d: every record trimmed on the GPU (crops, quality cuts from either end, a quality window, a 3' adapter), in front of -k
 // All model / coder work happens in libslimfastq_amd.so on the GPU; this file parses arguments, reads and
 // writes files and fills the info page.
 #include <sys/stat.h>
@@ -117,6 +118,13 @@ static void usage() {
            "                   (or its reverse complement), invert (the records that fail), sample=F[:SEED] (a reproducible share 0 < F < 1)\n"
            "                   and either; an archive written with -p keeps or drops whole pairs: where both mates pass, with either where\n"
            "                   one does; goes with -R, -W, -p, -x, -K and -b; without -q one line on stderr says what was kept\n"
+           "-c terms         : with -d: trim every record on the GPU before the text comes back, and before -k judges it; terms is a\n"
+           "                   comma-separated list of head=N, tail=N (bases cropped), maxlen=N (bases kept at most), q5=Q, q3=Q (cut the\n"
+           "                   bases in front of the first / behind the last quality of at least Q, Phred+33), win=W:Q (cut from the first\n"
+           "                   window of W <= 32 bases whose mean quality is below Q), adapter=SEQ (cut from where it begins; at most 32 of\n"
+           "                   ACGT), mm=N (mismatches allowed over its length) and overlap=N (bases of it that count at the read's end,\n"
+           "                   default 3); no record is dropped (-k minlen= does that); goes with -R, -W, -p, -x, -k, -K and -b, not with\n"
+           "                   -s; without -q one line on stderr says what was cut\n"
            "-M               : with -p on a compress run: compare the names of every pair of mates on the GPU before it is coded (the\n"
            "                   header's first word, without a final /1 or /2); a pair that differs ends the run with its index and both\n"
            "                   names, and no archive is written\n"
@@ -158,6 +166,7 @@ struct Opts {
     int pick = 0; std::string pick_name;                               // -x: SFQ_PICK_* (0 = none, -1 = no such word) and the word
     bool select = false; std::string select_spec;                      // -k terms
     sfq_select sel; bool sel_either = false;                           // ... parsed: the rule (its range and pairs are the decode's), `either`
+    bool trim = false; std::string trim_spec; sfq_trim trim_rule;      // -c terms, and the rule they parse to
 };
 // "FIRST:COUNT", both decimal, COUNT > 0
 static bool parse_range(const char* t, uint64_t& first, uint64_t& count) {
@@ -730,6 +739,8 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     if (sfq_ctx_set_pick(ctx, o.pick)) croak("%s", sfq_last_error(ctx));
     if (sfq_ctx_set_select(ctx, nullptr)) croak("%s", sfq_last_error(ctx));       // (set per segment: the range and the index base are the segment's)
     uint64_t sel_kept = 0, sel_seen = 0, sel_bytes = 0, sel_text = 0;
+    if (sfq_ctx_set_trim(ctx, o.trim ? &o.trim_rule : nullptr)) croak("-c: %s", sfq_last_error(ctx));
+    uint64_t trim_recs = 0, trim_changed = 0, trim_emptied = 0, trim_in = 0, trim_out = 0;
     const uint64_t rec_lines = !o.pick ? 4 : o.pick == SFQ_PICK_FASTA ? 2 : 1;      // the lines of a record in what a call hands back
     // walk the segments: each one's blocks, its slice of every stream (streams are segment-major), its prior
     size_t b0 = 0, pri_off = 0, chn_off = 0, rpr_off = 0;
@@ -855,6 +866,11 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             if (sfq_get_select(ctx, &rep) != 1) croak("-k: the library did not select");
             sel_kept += rep.n_kept; sel_seen += rep.n_in_range; sel_bytes += rep.kept_bytes; sel_text += rep.text_bytes;
         }
+        if (o.trim) {
+            sfq_trim_report rep;
+            if (sfq_get_trim(ctx, &rep) != 1) croak("-c: the library did not trim");
+            trim_recs += rep.n_records; trim_changed += rep.n_changed; trim_emptied += rep.n_emptied; trim_in += rep.bases_in; trim_out += rep.bases_out;
+        }
         if (o.range && !o.select) {                                    // the window's first and last block, cut to records: rec_lines lines each
             const uint64_t wrec0 = rec0 + (uint64_t)w0 * sb[0].n_records;
             const uint64_t lo = std::max(r_lo, wrec0), hi = std::min(r_hi, wrec0 + res.n_records);
@@ -882,6 +898,9 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     if (wbad) croak("USR: Error writing output");
     if (of != stdout) fclose(of); else fflush(stdout);
     if (of2) fclose(of2);
+    if (o.trim && !o.quiet)
+        fprintf(stderr, "trimmed %llu of %llu records, %llu to nothing (%llu of %llu bases left)\n", (unsigned long long)trim_changed, (unsigned long long)trim_recs,
+                (unsigned long long)trim_emptied, (unsigned long long)trim_out, (unsigned long long)trim_in);
     if (o.select && !o.quiet)
         fprintf(stderr, "kept %llu of %llu records (%llu of %llu bytes)\n", (unsigned long long)sel_kept, (unsigned long long)sel_seen,
                 (unsigned long long)sel_bytes, (unsigned long long)sel_text);
@@ -892,7 +911,7 @@ int main(int argc, char** argv) {
     Opts o;
     bool statistics = false;
     if (argc == 1) usage();
-    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKYM1234u:f:l:B:g:S:T:C:t:R:Q:p:W:x:k:")) != -1;) {
+    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKYM1234u:f:l:B:g:S:T:C:t:R:Q:p:W:x:k:c:")) != -1;) {
         switch (opt) {
         case 'u': g_usr = optarg; break;
         case 'f': fil = optarg; break;
@@ -932,6 +951,7 @@ int main(int argc, char** argv) {
                      o.pick_name == "quals" ? SFQ_PICK_QUALS : -1;
             break;
         case 'k': o.select = true; o.select_spec = optarg; break;
+        case 'c': o.trim = true; o.trim_spec = optarg; break;
         case 'C': o.chain_reads = strtol(optarg, 0, 0); break;
         case 't': o.io_threads = std::min(64, std::max(1, atoi(optarg))); break;
         case 'v': printf("Version %s\nInternal format version=%u (block format %u)\n", kUserVersion, kInternalVersion, kBlockVersion); exit(0);
@@ -990,6 +1010,18 @@ int main(int argc, char** argv) {
         o.sel_either = either != 0;
         if (g_encode || statistics) {
             fprintf(stderr, "slimfastq: -k (selected records) goes with -d: it chooses the records a decode writes%s\n", statistics ? "; -s writes no text" : "");
+            return 1;
+        }
+    }
+
+    if (o.trim) {
+        char err[256] = "";
+        if (sfq_trim_parse(o.trim_spec.c_str(), &o.trim_rule, err, sizeof err)) {
+            fprintf(stderr, "slimfastq: -c %s: %s\n", o.trim_spec.c_str(), err);
+            return 1;
+        }
+        if (g_encode || statistics) {
+            fprintf(stderr, "slimfastq: -c (trimmed records) goes with -d: it trims the records a decode writes%s\n", statistics ? "; -s writes no text" : "");
             return 1;
         }
     }

@@ -51,15 +51,44 @@ __device__ __forceinline__ u32 unit_mask(i64 rb, i64 n, u32 lane, i64* ub) {
     const u32 jhi = n - *ub < 16 ? (u32)(n - *ub) : 16u;
     return ((1u << jhi) - 1u) & ~((1u << jlo) - 1u);
 }
-template <bool EDGE>
-__device__ __forceinline__ void load_batch(const u8* fq, i64 n, i64 rb0, u32 lane, uint4 (&v)[BATCH], u32 (&vm)[BATCH]) {
+// NB rows from text offset rb0 on: the lane's unit of each (zeros where none of its bytes is text) and the mask of its bytes that are
+template <bool EDGE, u32 NB>
+__device__ __forceinline__ void load_rows(const u8* fq, i64 n, i64 rb0, u32 lane, uint4 (&v)[NB], u32 (&vm)[NB]) {
 #pragma unroll
-    for (u32 k = 0; k < BATCH; k++) {
+    for (u32 k = 0; k < NB; k++) {
         i64 ub;
         vm[k] = unit_mask<EDGE>(rb0 + (i64)k * ROW, n, lane, &ub);
         v[k] = make_uint4(0, 0, 0, 0);
         if (vm[k]) v[k] = *reinterpret_cast<const uint4*>(fq + ub);
     }
+}
+template <bool EDGE>
+__device__ __forceinline__ void load_batch(const u8* fq, i64 n, i64 rb0, u32 lane, uint4 (&v)[BATCH], u32 (&vm)[BATCH]) {
+    load_rows<EDGE, BATCH>(fq, n, rb0, lane, v, vm);
+}
+
+__device__ __forceinline__ u32 below(u32 j) { return (1u << j) - 1u; }          // the bytes in front of byte j (j <= 16)
+// bit j: byte j of the unit is pat's byte (pat: one byte four times)
+__device__ __forceinline__ u32 eq_mask(const u32 (&w)[4], u32 pat) {
+    u32 m = 0;
+#pragma unroll
+    for (u32 i = 0; i < 4; i++) m |= gather_bit7(~nonzero_bytes(w[i] ^ pat) & 0x80808080u) << (4 * i);
+    return m;
+}
+// the sum of the unit's bytes that m names
+__device__ __forceinline__ u32 byte_sum(const u32 (&w)[4], u32 m) {
+    u32 s = 0;
+#pragma unroll
+    for (u32 i = 0; i < 4; i++) s = __builtin_amdgcn_sad_u8(w[i] & byte_mask(m, i), 0u, s);
+    return s;
+}
+// two bits a byte, (byte >> 1) & 3 -- A 0, C 1, T 2, G 3, either case -- byte j at bits 2 j (per word: the four fields land on bits
+// 18 .. 25 of the product, no two partial products on one bit)
+__device__ __forceinline__ u32 base_codes(const u32 (&w)[4]) {
+    u32 c = 0;
+#pragma unroll
+    for (u32 i = 0; i < 4; i++) c |= (((((w[i] >> 1) & 0x03030303u) * 0x00041041u) >> 18) & 0xFFu) << (8 * i);
+    return c;
 }
 
 }  // namespace textspan

@@ -371,3 +371,39 @@ struct SelArrays { u64* ls; u64* acc; u8* hit; u32* keep; u32* rlen; u64* pos; u
 // t.starts is not used (A.ls is the pass's own); info: zeroed by the caller.  out: job.out_cap bytes, of which info->copy.nout are
 // written, and none unless info->status and info->copy.status stay 0.
 void launch_select(const PairText& t, const SelArrays& A, const SelJob& job, u8* out, SelInfo* info, hipStream_t st);
+// its first two steps alone, for the passes that want the starts of ALL lines (trim.hip): t.scratch's line-end counts and their scan
+// (before[] = the line ends in front of every span, before[nspans] = all of them), then ls[l] = where line l begins for every l in
+// 1 .. lcap that a line end in the text gives; ls[0] and the entry behind the last line are the caller's check's.
+void launch_line_starts(const PairText& t, u64* ls, u64 lcap, hipStream_t st);
+
+// Trimmed records (trim.hip): every record of a text with bytes [s, e) of its lines 2 and 4 alone, where s and e come from crops, quality
+// cuts and an adapter (slimfastq_amd.h "trimmed records").  Like sel.hip the pass finds the lines itself, decides every refusal on the
+// device and copies with pick.hip's copy; *info tells the host, which synchronises once.
+enum TrimStatus : u32 {
+    TRIM_OK = 0,
+    TRIM_LINES,             // the text's lines are no multiple of four
+    TRIM_CAP,               // more records than the arrays hold: info->recs says how many, nothing else was done
+    TRIM_ROOM               // the result needs more than the output holds: info->copy.nout says how much
+};
+// copy: what k_pick_copy reads -- r0 = 0, pieces = the non-empty pieces of all records, nout = their bytes, status != 0 wherever there
+// is nothing to copy.  stop: some refusal, whichever kernel found it; bad_first, bad_off: the smallest record whose lines 2 and 4 differ
+// in length (~0: none) and where it begins; toolong: a line (or a piece of the copy) of 4 GiB or more.
+struct TrimInfo {
+    PickInfo copy; u64 lines, recs; u32 status, stop, toolong, pad; u64 bad_first, bad_off;
+    u64 n_changed, n_emptied, bases_in, bases_out, n_cut[4];
+};
+// the rule, made ready by the host: lead_thr, trail_thr = the smallest BYTE that satisfies the quality cut (0: the term is off, above
+// 255: no byte does); win_sum: a window fails where its byte sum is below it; adapter: two bits a base, (byte >> 1) & 3, the first base
+// in the lowest bits; ad_len = 0: no adapter
+struct TrimJob {
+    u64 out_cap, adapter;
+    u32 head, tail, max_len, lead_thr, trail_thr, win_len, win_sum, ad_len, ad_mm, ad_min;
+};
+// ls[4 cap + 1] as SelArrays'; lead, trail, win, ad[cap]: per record the terms' positions (trail as the complement of the cut, so that
+// all four are minima; all ones = none); se[cap]: s | e << 32; cnt[cap]: the record's non-empty pieces, at[cap + 1] their scan;
+// rlen[cap]: the bytes left of the record, rdst[cap + 1] their scan; from[5 cap], dst[5 cap]: the pieces' sources and destinations;
+// tmp as launch_scan_u32 wants it for cap
+struct TrimArrays { u64* ls; u32* lead; u32* trail; u32* win; u32* ad; u64* se; u32* cnt; u64* at; u32* rlen; u64* rdst; u64* from; u64* dst; u64* tmp; u64 cap; };
+// t.starts is not used; info: zeroed by the caller.  out: job.out_cap bytes, of which info->copy.nout are written, and none unless
+// info->stop stays 0.
+void launch_trim(const PairText& t, const TrimArrays& A, const TrimJob& job, u8* out, TrimInfo* info, hipStream_t st);

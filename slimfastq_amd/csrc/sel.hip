@@ -86,28 +86,6 @@ __global__ void k_sel_check(SelInfo* info, const u64* line_ends, const u8* last,
 // ---- 4. the terms ----------------------------------------------------------------------------------------------------------------
 struct SelTerms { u64* acc; u64 lcap; u8* hit; u64 cap; u64 motif, motif_rev; u32 mlen; };
 
-// bit j: byte j of the unit is pat's byte (pat: one byte four times)
-__device__ __forceinline__ u32 eq_mask(const u32 (&w)[4], u32 pat) {
-    u32 m = 0;
-#pragma unroll
-    for (u32 i = 0; i < 4; i++) m |= gather_bit7(~nonzero_bytes(w[i] ^ pat) & 0x80808080u) << (4 * i);
-    return m;
-}
-// the sum of the unit's bytes that m names
-__device__ __forceinline__ u32 byte_sum(const u32 (&w)[4], u32 m) {
-    u32 s = 0;
-#pragma unroll
-    for (u32 i = 0; i < 4; i++) s = __builtin_amdgcn_sad_u8(w[i] & byte_mask(m, i), 0u, s);
-    return s;
-}
-// two bits a byte, (byte >> 1) & 3 -- A 0, C 1, T 2, G 3, either case -- byte j at bits 2 j (per word: the four fields land on bits
-// 18 .. 25 of the product, no two partial products on one bit)
-__device__ __forceinline__ u32 base_codes(const u32 (&w)[4]) {
-    u32 c = 0;
-#pragma unroll
-    for (u32 i = 0; i < 4; i++) c |= (((((w[i] >> 1) & 0x03030303u) * 0x00041041u) >> 18) & 0xFFu) << (8 * i);
-    return c;
-}
 // what the bytes m of a unit add to line l: the 'N' / 'n' bytes of a base line, the byte sum of a quality line
 template <bool WN, bool WQ>
 __device__ __forceinline__ u32 line_value(const u32 (&w)[4], u32 nmask, u32 m, u64 l) {
@@ -119,7 +97,6 @@ __device__ __forceinline__ u32 line_value(const u32 (&w)[4], u32 nmask, u32 m, u
 __device__ __forceinline__ void line_add(const SelTerms& T, u64 l, u32 x) {
     if (x && l < T.lcap) atomicAdd(reinterpret_cast<unsigned long long*>(T.acc + (l >> 1)), (unsigned long long)x);
 }
-__device__ __forceinline__ u32 below(u32 j) { return (1u << j) - 1u; }          // the bytes in front of byte j (j <= 16)
 
 // line: the line ends in front of the span
 template <bool EDGE, bool WN, bool WQ, bool MOT>
@@ -328,17 +305,25 @@ void launch_terms(bool mot, dim3 grid, hipStream_t st, const SelInfo* info, cons
 
 }  // namespace
 
-void launch_select(const PairText& t, const SelArrays& A, const SelJob& job, u8* out, SelInfo* info, hipStream_t st) {
+void launch_line_starts(const PairText& t, u64* ls, u64 lcap, hipStream_t st) {
     const QmapScratch q = qmap_scratch(t.d, t.n);
     const u32 mis = (u32)((uintptr_t)t.d & 15);
     u32* cnt = reinterpret_cast<u32*>(t.scratch + q.cnt_off);
     u64* before = reinterpret_cast<u64*>(t.scratch + q.before_off);
     const u64 tiles = (q.nspans + 3) / 4;
-    const dim3 grid((u32)(tiles < MAX_WG ? tiles : MAX_WG));
-    const u64 lcap = 4 * A.cap;
     launch_newline_counts(t.d, t.n, cnt, st);
     launch_scan_u32(cnt, before, q.nspans, reinterpret_cast<u64*>(t.scratch + q.tmp_off), st);
-    hipLaunchKernelGGL(k_sel_starts, grid, dim3(256), 0, st, t.d - mis, mis, t.n, q.nspans, (const u64*)before, A.ls, lcap);
+    hipLaunchKernelGGL(k_sel_starts, dim3((u32)(tiles < MAX_WG ? tiles : MAX_WG)), dim3(256), 0, st, t.d - mis, mis, t.n, q.nspans, (const u64*)before, ls, lcap);
+}
+
+void launch_select(const PairText& t, const SelArrays& A, const SelJob& job, u8* out, SelInfo* info, hipStream_t st) {
+    const QmapScratch q = qmap_scratch(t.d, t.n);
+    const u32 mis = (u32)((uintptr_t)t.d & 15);
+    u64* before = reinterpret_cast<u64*>(t.scratch + q.before_off);
+    const u64 tiles = (q.nspans + 3) / 4;
+    const dim3 grid((u32)(tiles < MAX_WG ? tiles : MAX_WG));
+    const u64 lcap = 4 * A.cap;
+    launch_line_starts(t, A.ls, lcap, st);
     hipLaunchKernelGGL(k_sel_check, dim3(1), dim3(64), 0, st, info, (const u64*)before + q.nspans, t.d + t.n - 1, t.n, A.ls, A.cap, job);
     // the terms that are on: only their instructions run, and only their arrays are cleared
     const bool wn = job.max_n != ~0u, wq = job.min_q != 0, mot = job.motif_len != 0;
