@@ -636,6 +636,70 @@ int sfq_ctx_set_trim(sfq_ctx* ctx, const sfq_trim* trim);
 /* 1: the last decode call trimmed, *out = what it found; 0: it did not (*out zeroed) */
 int sfq_get_trim(const sfq_ctx* ctx, sfq_trim_report* out);
 
+/* ---- overlapping mates --------------------------------------------------------------------------------------------------------
+ * Adapter removal for pairs WITHOUT knowing the adapter: where the sequenced fragment is shorter than the reads, both mates run
+ * through into adapter, read 1 and the reverse complement of read 2 agree over the whole insert, and what lies behind it is
+ * read-through.  The pass (ovl.hip) finds that overlap for every pair of an interleaved text while it is on the device, reports the
+ * insert sizes, and cuts the read-through.  Text to text like the trimmed records, whose line starts, piece layout and copy it uses.
+ * Lines and records: they are sfq_pick_lines' own.  A line ends at '\n'; a text without a final '\n' still ends in a line; '\r' is a
+ *   byte like any other.  Lengths exclude the '\n'.
+ * For one pair, record X is the first mate and record Y the second: a = line 2 of X, of length La; b = line 2 of Y, of length Lb;
+ *   b' = the reverse complement of b: b'[j] = comp(b[Lb-1-j]), A <-> T and C <-> G.  Bases are compared without regard to letter case;
+ *   a byte that is none of ACGTacgt, on either side, mismatches everything (the trim pass's convention).
+ * Offsets: for an offset d in [-(Lb-1), La-1], position p of a lies against position p-d of b'.
+ *   lo = max(0, d), hi = min(La, d + Lb), ov(d) = hi - lo; mm(d) = the number of p in [lo, hi) that mismatch.
+ * Acceptance: d is accepted when ov(d) >= min_overlap, mm(d) <= max_mm and 100 * mm(d) <= max_mm_pct * ov(d) (integers).
+ * Winner: the accepted d with the largest ov; among those the largest d.  The order is total: the result does not depend on the
+ *   order of the search.
+ * Insert and cut: the insert is I = d + Lb, 1 <= I <= La + Lb - min_overlap.  With cut set, lines 2 and 4 of X keep their first
+ *   min(La, I) bytes and lines 2 and 4 of Y their first min(Lb, I) bytes: what is behind the insert in either read is read-through.
+ *   Lines 1 and 3 and every '\n' stay.  NO RECORD IS EVER DROPPED, records stay in step; a pair without an accepted offset is unchanged.
+ * Pairs that are not searched: a pair with La or Lb above SFQ_OVERLAP_MAX_LEN passes unchanged and is counted in n_skipped.
+ * Range: the pairs are records (first_record + 2k, first_record + 2k + 1) inside [first_record, first_record + n_records);
+ *   n_records = UINT64_MAX: to the last record.  Records outside the range are copied unchanged. */
+#define SFQ_OVERLAP_MAX_LEN 512
+typedef struct sfq_overlap {
+    uint64_t first_record, n_records;
+    uint32_t min_overlap;    /* 1 .. SFQ_OVERLAP_MAX_LEN */
+    uint32_t max_mm;
+    uint32_t max_mm_pct;     /* 0 .. 100 */
+    uint32_t cut;            /* 0: the text is not changed, the report alone */
+} sfq_overlap;
+typedef struct sfq_overlap_report {
+    uint64_t n_pairs, n_skipped, n_overlap, n_cut;   /* the range's pairs; n_overlap: with an accepted offset; n_cut: pairs that lost a base (with cut == 0: that would) */
+    uint64_t text_bytes, out_bytes, bases_in, bases_out, mismatches;  /* bases_*: of the range's records; mismatches: sum of mm(d) of the winners */
+    uint64_t insert_hist[2 * SFQ_OVERLAP_MAX_LEN + 1]; /* [I]: searched pairs whose insert is I; [0]: searched, none accepted */
+} sfq_overlap_report;
+/* host only, no GPU: SFQ_OK, or SFQ_E_ARG for a null pointer, min_overlap outside 1 .. SFQ_OVERLAP_MAX_LEN, max_mm_pct above 100,
+ * n_records == 0 */
+int sfq_overlap_check(const sfq_overlap* rule);
+/* host only, no GPU: a rule from the CLI's -o SPEC, a comma-separated list of the terms min=N (min_overlap, default 30), mm=N (max_mm,
+ * default 5), pct=N (max_mm_pct, default 20) and nocut (cut = 0, default 1), or the single word `default`.  *rule: the rule, the range
+ * (0, UINT64_MAX).  SFQ_E_ARG for an unknown term, a bad number, an empty list or a rule that sfq_overlap_check refuses; err (may be
+ * NULL) then says which. */
+int sfq_overlap_parse(const char* spec, sfq_overlap* rule, char* err, uint64_t err_cap);
+/* The pairs of d_text[0, n), searched, and with rule->cut the text with the read-through cut into d_out; *out_bytes = the bytes of the
+ * result (on SFQ_E_OVERFLOW: the size needed).  With cut == 0 d_out may be NULL, nothing is written and *out_bytes = n.
+ * SFQ_E_ARG: a null pointer (report may be NULL), n == 0, a struct that sfq_overlap_check refuses, a range that ends behind the last
+ * record.  SFQ_E_FORMAT: lines that are no multiple of four, an odd number of records in the range, or a record of the range whose
+ * lines 2 and 4 differ in length; sfq_last_error names the smallest such record and its byte offset.  SFQ_E_UNSUPPORTED: a line of
+ * 4 GiB or more.  SFQ_E_OVERFLOW: a result larger than out_cap (never with out_cap >= n).  Every refusal is decided on the device
+ * before the copy: a refused call writes nothing.  A call that succeeds writes d_out[0, *out_bytes) and nothing else.  d_out must not
+ * overlap the text.  The call runs on the context's stream and synchronises once.  Like the other side passes, it may read the whole
+ * aligned 16-byte units that hold the text's first and last byte. */
+int sfq_overlap_pairs(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, const sfq_overlap* rule,
+                      uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_overlap_report* report);
+/* rule != NULL: sfq_decode_blocks_host, sfq_decode_block_range_host and sfq_decode_pair_range_host search the pairs of the text they
+ * decoded (the struct is copied; SFQ_E_ARG, and the setting stays, where sfq_overlap_check refuses it); NULL: off (default).  The pass
+ * runs BEHIND the trim and IN FRONT OF the selection: a selection's min_len judges the cut length; the split, the pair window's cut and
+ * the pick then run unchanged.  sfq_decode_pair_range_host supplies the range itself, the window's pairs; the struct's own range must
+ * then be (0, UINT64_MAX), else SFQ_E_ARG.  The CRCs stay those of the decoded text.  With cut == 0 no buffer is reserved and no copy
+ * is made; with cut != 0 the pass costs one more device buffer of the text's size, held while the switch is on.  The device-pointer
+ * decode entries are not affected.  Default off: nothing is launched, allocated or copied that is not today. */
+int sfq_ctx_set_overlap(sfq_ctx* ctx, const sfq_overlap* rule);
+/* 1: the last decode call searched its pairs, *out = what it found; 0: it did not (*out zeroed) */
+int sfq_get_overlap(const sfq_ctx* ctx, sfq_overlap_report* out);
+
 /* ---- the ".sfq" container (host only) ----------------------------------------------------------
  * Replaces FilerSave + the info page (filer.cpp:217-242, config.cpp:334-347) for hosts that assemble an archive
  * themselves: info_text is the info page ("key=value\n" lines), then n_streams named byte streams (names of at most

@@ -42,6 +42,7 @@ EXPORTS = [
     "sfq_decode_pair_range_host", "sfq_pick_lines", "sfq_ctx_set_pick", "sfq_get_pick",
     "sfq_select_check", "sfq_select_parse", "sfq_select_records", "sfq_ctx_set_select", "sfq_get_select",
     "sfq_trim_check", "sfq_trim_parse", "sfq_trim_records", "sfq_ctx_set_trim", "sfq_get_trim",
+    "sfq_overlap_check", "sfq_overlap_parse", "sfq_overlap_pairs", "sfq_ctx_set_overlap", "sfq_get_overlap",
 ]
 
 
@@ -179,6 +180,40 @@ def trim_parse(spec: str):
     return trim
 
 
+OVERLAP_MAX_LEN = 512
+
+
+class Overlap(C.Structure):
+    """sfq_overlap: the rule of the mates' overlap search (ovl.hip).  Overlap() is the CLI's `default`: 30 bases, 5 mismatches, 20 %, cut."""
+    _fields_ = [("first_record", C.c_uint64), ("n_records", C.c_uint64), ("min_overlap", C.c_uint32), ("max_mm", C.c_uint32),
+                ("max_mm_pct", C.c_uint32), ("cut", C.c_uint32)]
+
+    def __init__(self, first_record=0, n_records=None, min_overlap=30, max_mm=5, max_mm_pct=20, cut=1):
+        super().__init__()
+        self.first_record, self.n_records = first_record, SELECT_TO_END if n_records is None else n_records
+        self.min_overlap, self.max_mm, self.max_mm_pct, self.cut = min_overlap, max_mm, max_mm_pct, int(cut)
+
+
+class OverlapReport(C.Structure):
+    """sfq_overlap_report: what the overlap search found."""
+    _fields_ = [("n_pairs", C.c_uint64), ("n_skipped", C.c_uint64), ("n_overlap", C.c_uint64), ("n_cut", C.c_uint64),
+                ("text_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("bases_in", C.c_uint64), ("bases_out", C.c_uint64),
+                ("mismatches", C.c_uint64), ("insert_hist", C.c_uint64 * (2 * OVERLAP_MAX_LEN + 1))]
+
+
+def overlap_check(rule) -> int:
+    """sfq_overlap_check (no GPU): 0, or E_ARG for a rule the library refuses."""
+    return int(lib().sfq_overlap_check(C.byref(rule)))
+
+
+def overlap_parse(spec: str):
+    """sfq_overlap_parse (no GPU): the Overlap of the CLI's -o SPEC; ValueError with the library's words where it refuses."""
+    rule, err = Overlap(), C.create_string_buffer(256)
+    if lib().sfq_overlap_parse(spec.encode(), C.byref(rule), err, 256):
+        raise ValueError(err.value.decode("latin1"))
+    return rule
+
+
 class SfqError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("slimfastq_amd error %d: %s" % (code, msg))
@@ -311,6 +346,11 @@ def lib():
         L.sfq_trim_records.argtypes = [vp, vp, u64, C.POINTER(Trim), vp, u64, u64p, C.POINTER(TrimReport)]
         L.sfq_ctx_set_trim.argtypes = [vp, C.POINTER(Trim)]
         L.sfq_get_trim.argtypes = [vp, C.POINTER(TrimReport)]
+        L.sfq_overlap_check.argtypes = [C.POINTER(Overlap)]
+        L.sfq_overlap_parse.argtypes = [C.c_char_p, C.POINTER(Overlap), C.c_char_p, u64]
+        L.sfq_overlap_pairs.argtypes = [vp, vp, u64, C.POINTER(Overlap), vp, u64, u64p, C.POINTER(OverlapReport)]
+        L.sfq_ctx_set_overlap.argtypes = [vp, C.POINTER(Overlap)]
+        L.sfq_get_overlap.argtypes = [vp, C.POINTER(OverlapReport)]
         _lib = L
     return _lib
 
@@ -665,6 +705,33 @@ class Context:
         """The TrimReport of the last decode call; None where it did not trim."""
         rep = TrimReport()
         rc = lib().sfq_get_trim(self._h, C.byref(rep))
+        if rc < 0:
+            self._check(rc)
+        return rep if rc == 1 else None
+
+    def overlap_pairs(self, d_text, nbytes, rule, d_out, out_cap):
+        """The pairs of the interleaved FASTQ text in the device buffer at d_text, searched for the mates' overlap by the Overlap, and
+        with rule.cut the text without the read-through into the one at d_out (sfq_overlap_pairs; d_out may be None where cut is 0);
+        returns (bytes of the result, OverlapReport).  An SfqError of code E_OVERFLOW carries the size needed as .needed."""
+        n, rep = C.c_uint64(), OverlapReport()
+        rc = lib().sfq_overlap_pairs(self._h, C.c_void_p(d_text), int(nbytes), C.byref(rule), C.c_void_p(d_out), int(out_cap),
+                                     C.byref(n), C.byref(rep))
+        try:
+            self._check(rc)
+        except SfqError as e:
+            e.needed = int(n.value)
+            raise
+        return int(n.value), rep
+
+    def set_overlap(self, rule=None):
+        """An Overlap: decode_host, decode_range_host and decode_pair_range_host search the pairs of the text they decoded, behind the
+        trim and in front of the selection, and with rule.cut cut the read-through (get_overlap() says what was found); None: off."""
+        self._check(lib().sfq_ctx_set_overlap(self._h, None if rule is None else C.byref(rule)))
+
+    def get_overlap(self):
+        """The OverlapReport of the last decode call; None where it did not search."""
+        rep = OverlapReport()
+        rc = lib().sfq_get_overlap(self._h, C.byref(rep))
         if rc < 0:
             self._check(rc)
         return rep if rc == 1 else None

@@ -211,6 +211,10 @@ struct sfq_ctx {
     bool trim_on = false; sfq_trim trim{};            // sfq_ctx_set_trim
     DevBuf trim_out;                                  // the trimmed text of a decoded text (while the switch is on)
     bool trim_done = false; sfq_trim_report trim_report{};    // the last decode call's
+    // overlapping mates (ovl.hip): works in pair_work and reports through pair_pin too; nothing of this exists until the switch is on
+    bool ovl_on = false; sfq_overlap ovl{};           // sfq_ctx_set_overlap
+    DevBuf ovl_out;                                   // the cut text of a decoded text (while the switch is on with cut set)
+    bool ovl_done = false; sfq_overlap_report ovl_report{};   // the last decode call's
 };
 
 namespace {
@@ -973,7 +977,7 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
         &ctx->oflags, &ctx->okbytes, &ctx->ofpos, &ctx->okoff, &ctx->ofilt, &ctx->orecmap, &ctx->olist, &ctx->line_off_o, &ctx->ono, &ctx->opiece,
         &ctx->otxt[0], &ctx->otxt[1], &ctx->otxt[2], &ctx->osize_all, &ctx->oroff_all, &ctx->oroff_k, &ctx->ocnt,
         &ctx->crc_tab, &ctx->crc_tiles, &ctx->crc_grps, &ctx->crc_bounds, &ctx->crc_out, &ctx->stats_acc, &ctx->qmap_dev,
-        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out, &ctx->pick_out, &ctx->sel_out, &ctx->trim_out };
+        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out, &ctx->pick_out, &ctx->sel_out, &ctx->trim_out, &ctx->ovl_out };
     for (DevBuf* b : all) release(*b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->pin2) (void)hipHostFree(ctx->pin2);
@@ -2237,6 +2241,14 @@ int sfq_select_check(const sfq_select* s) {
     if (s->pairs && ((s->first_record | s->index_base) & 1)) return SFQ_E_ARG;
     return SFQ_OK;
 }
+// a term's number in the lists of the CLI's -k, -c and -o: decimal digits only, at most max
+static bool number(const std::string& t, u64 max, u64* v) {
+    if (t.empty() || t.size() > 19) return false;
+    u64 x = 0;
+    for (char c : t) { if (c < '0' || c > '9') return false; x = x * 10 + (u64)(c - '0'); }
+    *v = x;
+    return x <= max;
+}
 // "term,term,...": see slimfastq_amd.h
 int sfq_select_parse(const char* spec, sfq_select* sel, int* either, char* err, uint64_t err_cap) {
     auto bad = [&](const char* fmt, const std::string& what) {
@@ -2247,13 +2259,6 @@ int sfq_select_parse(const char* spec, sfq_select* sel, int* either, char* err, 
     memset(sel, 0, sizeof *sel);
     sel->n_records = ~0ull; sel->max_len = ~0u; sel->max_n = ~0u; sel->qual_base = 33;
     if (either) *either = 0;
-    auto number = [](const std::string& t, u64 max, u64* v) {      // decimal digits only, at most max
-        if (t.empty() || t.size() > 19) return false;
-        u64 x = 0;
-        for (char c : t) { if (c < '0' || c > '9') return false; x = x * 10 + (u64)(c - '0'); }
-        *v = x;
-        return x <= max;
-    };
     const std::string all = spec;
     if (all.empty()) return bad("an empty list of terms%s", "");
     for (size_t at = 0; at <= all.size(); ) {
@@ -2424,13 +2429,6 @@ int sfq_trim_parse(const char* spec, sfq_trim* trim, char* err, uint64_t err_cap
     if (!spec || !trim) return SFQ_E_ARG;
     memset(trim, 0, sizeof *trim);
     trim->max_len = ~0u; trim->qual_base = 33;
-    auto number = [](const std::string& t, u64 max, u64* v) {      // decimal digits only, at most max
-        if (t.empty() || t.size() > 19) return false;
-        u64 x = 0;
-        for (char c : t) { if (c < '0' || c > '9') return false; x = x * 10 + (u64)(c - '0'); }
-        *v = x;
-        return x <= max;
-    };
     const std::string all = spec;
     if (all.empty()) return bad("an empty list of terms%s", "");
     bool has_mm = false, has_overlap = false;
@@ -2580,6 +2578,141 @@ int sfq_get_trim(const sfq_ctx* ctx, sfq_trim_report* out) {
     return 1;
 }
 
+// ---- overlapping mates (ovl.hip) --------------------------------------------------------------------------------------------------
+static_assert(SFQ_OVERLAP_MAX_LEN == OVL_MAX_LEN, "the header's bound is the kernels'");
+int sfq_overlap_check(const sfq_overlap* o) {
+    if (!o) return SFQ_E_ARG;
+    if (o->min_overlap < 1 || o->min_overlap > SFQ_OVERLAP_MAX_LEN || o->max_mm_pct > 100 || !o->n_records) return SFQ_E_ARG;
+    return SFQ_OK;
+}
+// "term,term,...": see slimfastq_amd.h
+int sfq_overlap_parse(const char* spec, sfq_overlap* rule, char* err, uint64_t err_cap) {
+    auto bad = [&](const char* fmt, const std::string& what) {
+        if (err && err_cap) snprintf(err, (size_t)err_cap, fmt, what.c_str());
+        return SFQ_E_ARG;
+    };
+    if (!spec || !rule) return SFQ_E_ARG;
+    memset(rule, 0, sizeof *rule);
+    rule->n_records = ~0ull; rule->min_overlap = 30; rule->max_mm = 5; rule->max_mm_pct = 20; rule->cut = 1;
+    const std::string all = spec;
+    if (all.empty()) return bad("an empty list of terms%s", "");
+    if (all == "default") return SFQ_OK;
+    for (size_t at = 0; at <= all.size(); ) {
+        const size_t comma = std::min(all.find(',', at), all.size());
+        const std::string term = all.substr(at, comma - at);
+        at = comma + 1;
+        const size_t eq = term.find('=');
+        const std::string key = term.substr(0, eq), val = eq == std::string::npos ? "" : term.substr(eq + 1);
+        const bool has = eq != std::string::npos;
+        u64 v = 0;
+        if (key == "min" && has) {
+            if (!number(val, SFQ_OVERLAP_MAX_LEN, &v) || !v) return bad("min=%s: an overlap of 1 to 512 bases", val);
+            rule->min_overlap = (u32)v;
+        } else if (key == "mm" && has) { if (!number(val, 0xFFFFFFFFull, &v)) return bad("mm=%s: not a number of mismatches", val); rule->max_mm = (u32)v; }
+        else if (key == "pct" && has) { if (!number(val, 100, &v)) return bad("pct=%s: a percentage of 0 to 100", val); rule->max_mm_pct = (u32)v; }
+        else if (term == "nocut") rule->cut = 0;
+        else return bad("%s: no such term (min= mm= pct= nocut, or default alone)", term);
+    }
+    if (sfq_overlap_check(rule)) return bad("a rule that sfq_overlap_check refuses%s", "");
+    return SFQ_OK;
+}
+// trim_run's shape: one pass on the context's stream, one synchronise, in pair_run's working buffers and with its sizing; only a
+// text with more records than the arrays were laid out for runs twice.  out: not touched where s.cut is 0.  *rep: what the device
+// found (out_bytes on SFQ_E_OVERFLOW too).
+static int overlap_run(sfq_ctx* ctx, const u8* text, u64 n, const sfq_overlap& s, u8* out, u64 out_cap, sfq_overlap_report* rep) {
+    int rc;
+    const size_t infos = std::max({ sizeof(PairInfo), sizeof(PickInfo), sizeof(SelInfo), sizeof(TrimInfo), sizeof(OvlInfo) });
+    if ((rc = reserve_pinned_buf(ctx, ctx->pair_pin, ctx->pair_pin_cap, infos))) return rc;
+    const OvlJob job{ s.first_record, s.n_records, out_cap, s.min_overlap, s.max_mm, s.max_mm_pct, s.cut };
+    OvlInfo& got = *(OvlInfo*)ctx->pair_pin;
+    for (int attempt = 0; ; attempt++) {
+        const u64 cap = std::max<u64>(ctx->pair_cap, n / 64 + 1024);
+        auto up = [](u64 v) { return (v + 15) & ~15ull; };
+        u64 at = up(infos);
+        const u64 sc = at; at += up(qmap_scratch(text, n).bytes);
+        const u64 ls = at; at += up((4 * cap + 1) * 8);
+        const u64 ins = at; at += up((cap / 2 + 1) * 4);
+        const u64 mm = at; at += up((cap / 2 + 1) * 4);
+        const u64 keep = at; at += up(cap * 4);
+        const u64 cnt = at; at += up(cap * 4);
+        const u64 pos = at; at += up((cap + 1) * 8);
+        const u64 rlen = at; at += up(cap * 4);
+        const u64 rdst = at; at += up((cap + 1) * 8);
+        const u64 from = at; at += up(3 * cap * 8);
+        const u64 dst = at; at += up(3 * cap * 8);
+        const u64 tmp = at; at += up((cap / 1024 + 2) * 8);
+        if ((rc = reserve(ctx, ctx->pair_work, (size_t)at))) return rc;
+        u8* w = (u8*)ctx->pair_work.p;
+        OvlInfo* info = (OvlInfo*)w;
+        HIPC(hipMemsetAsync(info, 0, sizeof(OvlInfo), ctx->st));
+        const PairText t{ text, n, w + sc, nullptr };
+        const OvlArrays A{ (u64*)(w + ls), (u32*)(w + ins), (u32*)(w + mm), (u32*)(w + keep), (u32*)(w + cnt), (u64*)(w + pos), (u32*)(w + rlen),
+                           (u64*)(w + rdst), (u64*)(w + from), (u64*)(w + dst), (u64*)(w + tmp), cap };
+        launch_overlap(t, A, job, out, info, ctx->st);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(ctx->pair_pin, info, sizeof(OvlInfo), hipMemcpyDeviceToHost, ctx->st));
+        HIPC(hipStreamSynchronize(ctx->st));
+        if (got.status != OVL_CAP) break;
+        if (attempt) return fail(ctx, SFQ_E_HIP, "overlapping mates: the records did not fit twice");
+        ctx->pair_cap = got.recs;
+    }
+    memset(rep, 0, sizeof *rep);
+    rep->text_bytes = n;
+    if (got.status == OVL_LINES) return fail(ctx, SFQ_E_FORMAT, "overlapping mates: the text holds %llu lines, not a multiple of four", (unsigned long long)got.lines);
+    if (got.status == OVL_RANGE)
+        return fail(ctx, SFQ_E_ARG, "overlapping mates: records %llu..+%llu: not a range of the text's %llu records", (unsigned long long)s.first_record,
+                    (unsigned long long)s.n_records, (unsigned long long)got.recs);
+    if (got.status == OVL_ODD)
+        return fail(ctx, SFQ_E_FORMAT, "overlapping mates: the range holds %llu records, an odd number is no pairs",
+                    (unsigned long long)(s.n_records == ~0ull ? got.recs - s.first_record : s.n_records));
+    if (got.status == OVL_OK && got.bad_first != ~0ull)
+        return fail(ctx, SFQ_E_FORMAT, "overlapping mates: record %llu (at byte %llu) has a base line and a quality line of different lengths",
+                    (unsigned long long)got.bad_first, (unsigned long long)got.bad_off);
+    if (got.status == OVL_OK && got.toolong) return fail(ctx, SFQ_E_UNSUPPORTED, "overlapping mates: a line of 4 GiB or more");
+    if (got.status == OVL_ROOM) {
+        rep->out_bytes = got.copy.nout;
+        return fail(ctx, SFQ_E_OVERFLOW, "overlapping mates: the result needs %llu bytes", (unsigned long long)got.copy.nout);
+    }
+    if (got.status != OVL_OK || got.stop) return fail(ctx, SFQ_E_HIP, "overlapping mates: status %u", got.status);
+    rep->n_pairs = got.n_pairs; rep->n_skipped = got.n_skipped; rep->n_overlap = got.n_overlap; rep->n_cut = got.n_cut;
+    rep->out_bytes = s.cut ? got.copy.nout : n; rep->bases_in = got.bases_in; rep->bases_out = got.bases_out; rep->mismatches = got.mismatches;
+    memcpy(rep->insert_hist, got.hist, sizeof rep->insert_hist);
+    return SFQ_OK;
+}
+int sfq_overlap_pairs(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, const sfq_overlap* rule,
+                      uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_overlap_report* report) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!d_text || !out_bytes || !rule || (!d_out && rule->cut)) return fail(ctx, SFQ_E_ARG, "null argument");
+    *out_bytes = 0;
+    if (report) memset(report, 0, sizeof *report);
+    if (!n) return fail(ctx, SFQ_E_ARG, "overlapping mates: an empty text");
+    if (sfq_overlap_check(rule)) return fail(ctx, SFQ_E_ARG, "overlapping mates: a rule that sfq_overlap_check refuses");
+    HIPC(hipSetDevice(ctx->dev));
+    Settle settle(ctx);
+    sfq_overlap_report rep;
+    const int rc = overlap_run(ctx, d_text, n, *rule, d_out, out_cap, &rep);
+    if (rc == SFQ_E_OVERFLOW) *out_bytes = rep.out_bytes;
+    if (rc) return rc;
+    *out_bytes = rep.out_bytes;
+    if (report) *report = rep;
+    settle.ok = true;
+    return SFQ_OK;
+}
+int sfq_ctx_set_overlap(sfq_ctx* ctx, const sfq_overlap* rule) {
+    if (!ctx) return SFQ_E_ARG;
+    if (rule && sfq_overlap_check(rule)) return fail(ctx, SFQ_E_ARG, "overlapping mates: a rule that sfq_overlap_check refuses");
+    ctx->ovl_on = rule != nullptr;
+    if (rule) ctx->ovl = *rule;
+    if (!rule || !rule->cut) release(ctx->ovl_out);
+    return SFQ_OK;
+}
+int sfq_get_overlap(const sfq_ctx* ctx, sfq_overlap_report* out) {
+    if (!ctx || !out) return SFQ_E_ARG;
+    if (!ctx->ovl_done) { memset(out, 0, sizeof *out); return 0; }
+    *out = ctx->ovl_report;
+    return 1;
+}
+
 int sfq_get_block_index(sfq_ctx* ctx, sfq_block_info* h_blocks, uint32_t cap) {
     if (!ctx || !h_blocks) return SFQ_E_ARG;
     if (cap < ctx->index.size()) return fail(ctx, SFQ_E_ARG, "index has %zu blocks", ctx->index.size());
@@ -2660,7 +2793,7 @@ static int decode_device(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_inf
     Settle settle(ctx);
     drop_encode_blobs(ctx);                             // whatever an encode left behind is not this archive's
     ctx->crcs.clear(); ctx->text_crc = 0;
-    ctx->pair_split_done = false; ctx->pick_done = 0; ctx->sel_done = false; ctx->trim_done = false;
+    ctx->pair_split_done = false; ctx->pick_done = 0; ctx->sel_done = false; ctx->trim_done = false; ctx->ovl_done = false;
     if (w.ranged && ctx->pair_split_on && !w.pairs)
         return fail(ctx, SFQ_E_UNSUPPORTED, "a window of blocks may start at a second mate and is not split: sfq_ctx_set_pair_split(ctx, 0) comes first");
     const bool check = ex.set;
@@ -3409,6 +3542,8 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
         if (!w.pairs && ctx->pair_split_on && !ctx->sel.pairs)
             return fail(ctx, SFQ_E_ARG, "selected records: while the pair split is on a selection keeps or drops pairs (pairs must not be 0): the mates would fall out of step");
     }
+    if (ctx->ovl_on && w.pairs && (ctx->ovl.first_record || ctx->ovl.n_records != ~0ull))
+        return fail(ctx, SFQ_E_ARG, "overlapping mates: a window of pairs is the range: the rule's own must be (0, UINT64_MAX)");
     HIPC(hipSetDevice(ctx->dev));
     int rc;
     // the index is untrusted: every stream's blocks must lie inside the bytes handed over (the device entry point cannot
@@ -3465,8 +3600,19 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
         d_text = (const u8*)ctx->trim_out.p;
         *out_bytes = ctx->trim_report.out_bytes;
     }
+    if (ctx->ovl_on) {                                     // behind the trim, in front of the selection: its min_len judges the cut length
+        if (!*out_bytes) return fail(ctx, SFQ_E_FORMAT, "overlapping mates: an empty text");
+        sfq_overlap o = ctx->ovl;
+        if (w.pairs) { o.first_record = rec0; o.n_records = 2 * w.n_pairs; }      // the window's pairs
+        if (o.cut && (rc = reserve(ctx, ctx->ovl_out, (size_t)*out_bytes + 16))) return rc;
+        Settle settle(ctx);
+        if ((rc = overlap_run(ctx, d_text, *out_bytes, o, o.cut ? (u8*)ctx->ovl_out.p : nullptr, *out_bytes, &ctx->ovl_report))) return rc;
+        settle.ok = true;
+        ctx->ovl_done = true;
+        if (o.cut) { d_text = (const u8*)ctx->ovl_out.p; *out_bytes = ctx->ovl_report.out_bytes; }
+    }
     const bool selected = ctx->sel_on;
-    if (selected) {                                        // the first pass behind the checksum pass: the split and the pick see what it kept
+    if (selected) {                                      // the first pass behind the checksum pass: the split and the pick see what it kept
         if (!*out_bytes) return fail(ctx, SFQ_E_FORMAT, "selected records: an empty text");
         if ((rc = reserve(ctx, ctx->sel_out, (size_t)*out_bytes + 16))) return rc;
         Settle settle(ctx);

@@ -17,6 +17,8 @@
 //   -M        : with -p on encode: the mates' names are compared on the GPU before a slab is coded; a mismatch ends the run
 //   -k terms  : with -d: the records that pass a filter only (length, N count, mean quality, a motif, a sample), chosen on the GPU
 //   -c terms  : with -d: every record trimmed on the GPU (crops, quality cuts from either end, a quality window, a 3' adapter), in front of -k
+//   -o terms  : with -d: the mates of every pair overlapped on the GPU, the read-through behind the insert cut, the insert sizes counted;
+//               behind -c, in front of -k
 // All model / coder work happens in libslimfastq_amd.so on the GPU; this file parses arguments, reads and
 // writes files and fills the info page.
 #include <sys/stat.h>
@@ -125,6 +127,13 @@ static void usage() {
            "                   ACGT), mm=N (mismatches allowed over its length) and overlap=N (bases of it that count at the read's end,\n"
            "                   default 3); no record is dropped (-k minlen= does that); goes with -R, -W, -p, -x, -k, -K and -b, not with\n"
            "                   -s; without -q one line on stderr says what was cut\n"
+           "-o terms         : with -d, of an archive of pairs: overlap the mates of every pair on the GPU (read 1 against the reverse complement\n"
+           "                   of read 2) and cut what lies behind the insert off both, the adapter read through into, whatever it is;\n"
+           "                   behind -c and before -k judges the records; terms is a comma-separated list of min=N (bases that must overlap,\n"
+           "                   default 30), mm=N (mismatches at most, default 5), pct=N (and at most that share of the overlap, default 20),\n"
+           "                   nocut (count only, the text stays) and hist=PATH (the insert sizes as 'insert<TAB>pairs' lines; insert 0: no\n"
+           "                   overlap found), or the word default; no record is dropped; goes with -R, -W, -p, -x, -k, -c and -K, not\n"
+           "                   with -s or -b; without -q one line on stderr says what was found\n"
            "-M               : with -p on a compress run: compare the names of every pair of mates on the GPU before it is coded (the\n"
            "                   header's first word, without a final /1 or /2); a pair that differs ends the run with its index and both\n"
            "                   names, and no archive is written\n"
@@ -167,6 +176,7 @@ struct Opts {
     bool select = false; std::string select_spec;                      // -k terms
     sfq_select sel; bool sel_either = false;                           // ... parsed: the rule (its range and pairs are the decode's), `either`
     bool trim = false; std::string trim_spec; sfq_trim trim_rule;      // -c terms, and the rule they parse to
+    bool ovl = false; std::string ovl_spec, ovl_hist; sfq_overlap ovl_rule;        // -o terms, the hist=PATH among them, and the rule the others parse to
 };
 // "FIRST:COUNT", both decimal, COUNT > 0
 static bool parse_range(const char* t, uint64_t& first, uint64_t& count) {
@@ -712,6 +722,17 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     const bool sel_pairs = o.select && a.get_long("usr.pair", 0) == 1;
     if (o.select && o.sel_either && !sel_pairs) croak("-k either: %s was not written from paired files (no usr.pair in its info): its records stand alone", fil.c_str());
     if (paired && a.get_long("usr.pair", 0) != 1) croak("-p: %s was not written from paired files (no usr.pair in its info): decode it without -p", fil.c_str());
+    // -o: pairs are the archive's, and no pair lies across two segments (-W's rule, found here before an output file is opened)
+    if (o.ovl) {
+        size_t at = 0;
+        for (const sfqc::Segment& g : segs) {
+            if (g.nblocks == 0 || g.nblocks > blocks.size() - at) croak("bad segment index");
+            const uint64_t seg0 = blocks[at].first_record, seg_end = blocks[at + g.nblocks - 1].first_record + blocks[at + g.nblocks - 1].n_records;
+            if ((seg0 | seg_end) & 1) croak("-o: segment %zu holds records %llu..%llu, not whole pairs: %s was not written by -p",
+                                            (size_t)(&g - segs.data()), (unsigned long long)seg0, (unsigned long long)seg_end, fil.c_str());
+            at += g.nblocks;
+        }
+    }
     FILE* of = stdout;
     FILE* of2 = nullptr;
     if (paired) {
@@ -741,6 +762,8 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     uint64_t sel_kept = 0, sel_seen = 0, sel_bytes = 0, sel_text = 0;
     if (sfq_ctx_set_trim(ctx, o.trim ? &o.trim_rule : nullptr)) croak("-c: %s", sfq_last_error(ctx));
     uint64_t trim_recs = 0, trim_changed = 0, trim_emptied = 0, trim_in = 0, trim_out = 0;
+    if (sfq_ctx_set_overlap(ctx, nullptr)) croak("%s", sfq_last_error(ctx));      // (set per segment: the range is the segment's)
+    sfq_overlap_report ovl_sum; memset(&ovl_sum, 0, sizeof ovl_sum);
     const uint64_t rec_lines = !o.pick ? 4 : o.pick == SFQ_PICK_FASTA ? 2 : 1;      // the lines of a record in what a call hands back
     // walk the segments: each one's blocks, its slice of every stream (streams are segment-major), its prior
     size_t b0 = 0, pri_off = 0, chn_off = 0, rpr_off = 0;
@@ -831,6 +854,18 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             if (sfq_ctx_set_select(ctx, &sel))
                 croak("-k: %s%s", sfq_last_error(ctx), sel.pairs ? " (an archive written with -p is selected pair by pair: a range begins at a first mate)" : "");
         }
+        if (o.ovl) {
+            // the range: from the decoded text's first record whose archive number is even, whole pairs (-W: the library's own)
+            sfq_overlap rule = o.ovl_rule;
+            if (!o.window) {
+                uint64_t wrecs = 0;
+                for (uint32_t b = w0; b < w0 + wn; b++) wrecs += sb[b].n_records;
+                rule.first_record = (rec0 + sb[w0].first_record) & 1;
+                rule.n_records = (wrecs - rule.first_record) & ~1ull;
+            }
+            if (!o.window && !rule.n_records) { if (sfq_ctx_set_overlap(ctx, nullptr)) croak("%s", sfq_last_error(ctx)); }
+            else if (sfq_ctx_set_overlap(ctx, &rule)) croak("-o: %s", sfq_last_error(ctx));
+        }
         sfq_result res;
         int rc = 0;
         uint8_t* dst = nullptr;
@@ -871,6 +906,16 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             if (sfq_get_trim(ctx, &rep) != 1) croak("-c: the library did not trim");
             trim_recs += rep.n_records; trim_changed += rep.n_changed; trim_emptied += rep.n_emptied; trim_in += rep.bases_in; trim_out += rep.bases_out;
         }
+        if (o.ovl) {
+            sfq_overlap_report rep;
+            const int did = sfq_get_overlap(ctx, &rep);
+            if (did < 0) croak("-o: the library did not search the pairs");
+            if (did == 1) {
+                ovl_sum.n_pairs += rep.n_pairs; ovl_sum.n_skipped += rep.n_skipped; ovl_sum.n_overlap += rep.n_overlap; ovl_sum.n_cut += rep.n_cut;
+                ovl_sum.bases_in += rep.bases_in; ovl_sum.bases_out += rep.bases_out; ovl_sum.mismatches += rep.mismatches;
+                for (size_t i = 0; i <= 2 * SFQ_OVERLAP_MAX_LEN; i++) ovl_sum.insert_hist[i] += rep.insert_hist[i];
+            }
+        }
         if (o.range && !o.select) {                                    // the window's first and last block, cut to records: rec_lines lines each
             const uint64_t wrec0 = rec0 + (uint64_t)w0 * sb[0].n_records;
             const uint64_t lo = std::max(r_lo, wrec0), hi = std::min(r_hi, wrec0 + res.n_records);
@@ -901,6 +946,21 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     if (o.trim && !o.quiet)
         fprintf(stderr, "trimmed %llu of %llu records, %llu to nothing (%llu of %llu bases left)\n", (unsigned long long)trim_changed, (unsigned long long)trim_recs,
                 (unsigned long long)trim_emptied, (unsigned long long)trim_out, (unsigned long long)trim_in);
+    if (o.ovl && !o.ovl_hist.empty()) {
+        FILE* hf = fopen(o.ovl_hist.c_str(), "w");
+        if (!hf) croak("-o hist=%s: can't write the file", o.ovl_hist.c_str());
+        fprintf(hf, "insert\tpairs\n");
+        for (size_t i = 0; i <= 2 * SFQ_OVERLAP_MAX_LEN; i++)
+            if (ovl_sum.insert_hist[i]) fprintf(hf, "%zu\t%llu\n", i, (unsigned long long)ovl_sum.insert_hist[i]);
+        if (fclose(hf)) croak("-o hist=%s: error writing the file", o.ovl_hist.c_str());
+    }
+    if (o.ovl && !o.quiet) {
+        // the median insert of the pairs that overlap
+        uint64_t seen = 0; size_t median = 0;
+        for (size_t i = 1; i <= 2 * SFQ_OVERLAP_MAX_LEN && !median; i++) { seen += ovl_sum.insert_hist[i]; if (ovl_sum.n_overlap && 2 * seen >= ovl_sum.n_overlap) median = i; }
+        fprintf(stderr, "overlapped %llu of %llu pairs, cut %llu (%llu bases removed), median insert %zu\n", (unsigned long long)ovl_sum.n_overlap,
+                (unsigned long long)ovl_sum.n_pairs, (unsigned long long)ovl_sum.n_cut, (unsigned long long)(ovl_sum.bases_in - ovl_sum.bases_out), median);
+    }
     if (o.select && !o.quiet)
         fprintf(stderr, "kept %llu of %llu records (%llu of %llu bytes)\n", (unsigned long long)sel_kept, (unsigned long long)sel_seen,
                 (unsigned long long)sel_bytes, (unsigned long long)sel_text);
@@ -911,7 +971,7 @@ int main(int argc, char** argv) {
     Opts o;
     bool statistics = false;
     if (argc == 1) usage();
-    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKYM1234u:f:l:B:g:S:T:C:t:R:Q:p:W:x:k:c:")) != -1;) {
+    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKYM1234u:f:l:B:g:S:T:C:t:R:Q:p:W:x:k:c:o:")) != -1;) {
         switch (opt) {
         case 'u': g_usr = optarg; break;
         case 'f': fil = optarg; break;
@@ -952,6 +1012,7 @@ int main(int argc, char** argv) {
             break;
         case 'k': o.select = true; o.select_spec = optarg; break;
         case 'c': o.trim = true; o.trim_spec = optarg; break;
+        case 'o': o.ovl = true; o.ovl_spec = optarg; break;
         case 'C': o.chain_reads = strtol(optarg, 0, 0); break;
         case 't': o.io_threads = std::min(64, std::max(1, atoi(optarg))); break;
         case 'v': printf("Version %s\nInternal format version=%u (block format %u)\n", kUserVersion, kInternalVersion, kBlockVersion); exit(0);
@@ -1022,6 +1083,34 @@ int main(int argc, char** argv) {
         }
         if (g_encode || statistics) {
             fprintf(stderr, "slimfastq: -c (trimmed records) goes with -d: it trims the records a decode writes%s\n", statistics ? "; -s writes no text" : "");
+            return 1;
+        }
+    }
+
+    if (o.ovl) {
+        // hist=PATH is the CLI's own term: the library parses the others
+        std::string rest;
+        bool listed = false, others = false;
+        for (size_t at = 0; at <= o.ovl_spec.size(); ) {
+            const size_t comma = std::min(o.ovl_spec.find(',', at), o.ovl_spec.size());
+            const std::string term = o.ovl_spec.substr(at, comma - at);
+            at = comma + 1;
+            if (term.compare(0, 5, "hist=") == 0) { o.ovl_hist = term.substr(5); listed = true; continue; }
+            if (others) rest += ",";
+            rest += term; others = true;
+        }
+        if (listed && !others) rest = "default";                       // hist=PATH alone: the default rule
+        char err[256] = "";
+        if (listed && o.ovl_hist.empty()) snprintf(err, sizeof err, "hist=: names no file");
+        else if (sfq_overlap_parse(rest.c_str(), &o.ovl_rule, err, sizeof err) == 0) err[0] = 0;
+        else if (!err[0]) snprintf(err, sizeof err, "not a list of terms");
+        if (err[0]) {
+            fprintf(stderr, "slimfastq: -o %s: %s\n", o.ovl_spec.c_str(), err);
+            return 1;
+        }
+        if (g_encode || statistics || g_batch) {
+            fprintf(stderr, "slimfastq: -o (overlapping mates) goes with -d: it cuts the records a decode writes%s\n",
+                    statistics ? "; -s writes no text" : g_batch ? "; it does not go with -b" : "");
             return 1;
         }
     }

@@ -407,3 +407,34 @@ struct TrimArrays { u64* ls; u32* lead; u32* trail; u32* win; u32* ad; u64* se; 
 // t.starts is not used; info: zeroed by the caller.  out: job.out_cap bytes, of which info->copy.nout are written, and none unless
 // info->stop stays 0.
 void launch_trim(const PairText& t, const TrimArrays& A, const TrimJob& job, u8* out, TrimInfo* info, hipStream_t st);
+
+// Overlapping mates (ovl.hip): for every pair of a range of records the offset at which the first mate and the reverse complement of
+// the second agree (slimfastq_amd.h "overlapping mates"), the insert sizes' histogram, and with job.cut the text with what lies behind
+// the insert cut off lines 2 and 4 of both mates.  Like trim.hip the pass finds the lines itself, decides every refusal on the device and
+// copies with pick.hip's copy; *info tells the host, which synchronises once.
+constexpr u32 OVL_MAX_LEN = 512;            // SFQ_OVERLAP_MAX_LEN
+constexpr u32 OVL_SKIPPED = 0xFFFFFFFFu;    // ins[]: a pair with a mate above OVL_MAX_LEN
+enum OvlStatus : u32 {
+    OVL_OK = 0,
+    OVL_LINES,              // the text's lines are no multiple of four
+    OVL_RANGE,              // a range that ends behind the text's last record
+    OVL_ODD,                // an odd number of records in the range
+    OVL_CAP,                // more records than the arrays hold: info->recs says how many, nothing else was done
+    OVL_ROOM                // the result needs more than the output holds: info->copy.nout says how much
+};
+// copy, stop, bad_first, bad_off, toolong: as TrimInfo's (bad_first among the range's records alone); r0, nr: the range as the check
+// found it; hist[I]: the searched pairs whose insert is I, hist[0]: those without an accepted offset
+struct OvlInfo {
+    PickInfo copy; u64 lines, recs, r0, nr; u32 status, stop, toolong, pad; u64 bad_first, bad_off;
+    u64 n_pairs, n_skipped, n_overlap, n_cut, bases_in, bases_out, mismatches;
+    u64 hist[2 * OVL_MAX_LEN + 1];
+};
+// nr = ~0: to the text's last record; cut = 0: the searches and the counts alone, no copy (out is not touched)
+struct OvlJob { u64 r0, nr, out_cap; u32 min_ov, max_mm, max_pct, cut; };
+// ls[4 cap + 1] as SelArrays'; ins, mm[cap / 2 + 1]: per pair of the range its insert (0: no offset accepted, OVL_SKIPPED) and the
+// winner's mismatches; keep[cap]: what is left of the record's lines 2 and 4; cnt, at, rlen, rdst, tmp as TrimArrays';
+// from[3 cap], dst[3 cap]: the pieces' sources and destinations (a cut that begins at 0 leaves a record at most three pieces)
+struct OvlArrays { u64* ls; u32* ins; u32* mm; u32* keep; u32* cnt; u64* at; u32* rlen; u64* rdst; u64* from; u64* dst; u64* tmp; u64 cap; };
+// t.starts is not used; info: zeroed by the caller.  out: job.out_cap bytes, of which info->copy.nout are written, and none unless
+// info->stop stays 0 and job.cut is set.
+void launch_overlap(const PairText& t, const OvlArrays& A, const OvlJob& job, u8* out, OvlInfo* info, hipStream_t st);
