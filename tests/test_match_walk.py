@@ -6,8 +6,9 @@ records in "chn.idx", compares the base chains with the oracle's chain by chain,
 and the lane texts also go through sfq_encode_blocks / sfq_decode_blocks with the text at an odd offset between guards.  No GPU decoder is
 handed bytes that an encoder did not write.
 
-Not reached: the walk's instantiations for a stage of 4 GiB or more (gm_plan_line<false, u64>, k_gm_decode_c<TH, u64>) -- no test of seconds
-stages that much -- and gm_ld16's held address: no walk loads at or behind `cap` (match_mint.stage_end_lines says why).
+Not reached here: the walk's instantiations for a stage of 4 GiB or more (gm_plan_line<false, u64>, k_gm_decode_c<TH, u64>) -- no oracle codes
+a stage of that size in seconds; test_large_texts.py::test_match_model_walk_of_a_4_gib_stage takes them through a round trip, without a reference
+for the coded bytes -- and gm_ld16's held address: no walk loads at or behind `cap` (match_mint.stage_end_lines says why).
 
 Wall time on one MI355X, same machine and run: the GPU suite with this module 428 s (662 tests); this module alone 13.2 s (63 tests), 11.6 s of
 them the first device-entry case (the process's first use of torch on the device).  An encode, the comparison and a decode take 0.01 - 0.07 s a
