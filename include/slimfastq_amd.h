@@ -700,6 +700,75 @@ int sfq_ctx_set_overlap(sfq_ctx* ctx, const sfq_overlap* rule);
 /* 1: the last decode call searched its pairs, *out = what it found; 0: it did not (*out zeroed) */
 int sfq_get_overlap(const sfq_ctx* ctx, sfq_overlap_report* out);
 
+/* ---- merged mates ---------------------------------------------------------------------------------------------------------------
+ * What users of short-insert paired data do next: a pair whose mates overlap becomes ONE read, the fragment itself (fastp --merge,
+ * PEAR, FLASH, BBMerge).  The pass (mrg.hip) runs the search of "overlapping mates" above and writes, for every pair that has an
+ * accepted offset, one merged record; the other pairs follow whole.  Lines, records, pairs, a, b, b', offsets, acceptance and the
+ * winner d are exactly those of "overlapping mates"; SFQ_OVERLAP_MAX_LEN applies as well.
+ * Which pairs merge: a pair of the range merges if and only if it is searched and has an accepted offset.  Every other pair of the
+ *   range is unmerged, pairs that are not searched (a mate above SFQ_OVERLAP_MAX_LEN) included.
+ * The merged record of a pair (X, Y) with winner d, I = d + Lb: line 1 of X with its '\n'; I merged bases and a '\n'; line 3 of X with
+ *   its '\n'; I merged quality bytes and a '\n'.  It always ends in '\n', even where the text does not, and is never longer than
+ *   its pair: out_cap = n always suffices.
+ * The merged position p in [0, I), j = p - d: p lies in a when p < La, in b' when 0 <= j < Lb; at least one holds.
+ *   x = a[p], qx = line4X[p]; yb = b[Lb-1-j], qy = line4Y[Lb-1-j]; y = the upper-case complement of yb where yb is one of ACGTacgt
+ *   ("valid"), else y = yb unchanged.
+ *     in a only                             x (as it is, case included)   qx
+ *     in b' only                            y                             qy
+ *     both valid, upper(x) == y             x                             max(qx, qy)
+ *     both valid, they differ, qx >= qy     x                             qual_base + min(max(|qx - qy|, 2), 126 - qual_base)
+ *     both valid, they differ, qx <  qy     y                             the same
+ *     only x valid                          x                             qx
+ *     only yb valid                         y                             qy
+ *     neither valid                         x                             qx
+ *   The differ formula takes byte values as integers; it never yields '\n', because qual_base >= 33.
+ * The result is two parts in one buffer: d_out[0, *merged_bytes) holds the merged records in pair order, d_out[*merged_bytes,
+ *   *out_bytes) the unmerged pairs of the range, both records whole and unchanged, in order: an ordinary interleaved text.
+ * Range: as sfq_overlap's -- but records outside the range are DROPPED, where sfq_overlap_pairs copies them: copied, an odd
+ *   first_record would leave a lone record in front of the pairs of the second part. */
+typedef struct sfq_merge {
+    uint64_t first_record, n_records;   /* as sfq_overlap's; n_records = UINT64_MAX: to the last record */
+    uint32_t min_overlap, max_mm, max_mm_pct;   /* as sfq_overlap's */
+    uint32_t qual_base;                 /* 33 .. 124 */
+} sfq_merge;
+typedef struct sfq_merge_report {
+    uint64_t n_pairs, n_skipped, n_merged;   /* the range's pairs; not searched; merged */
+    uint64_t text_bytes, out_bytes, merged_bytes;
+    uint64_t bases_in, bases_merged;         /* line-2 bytes of the range's records; the sum of I over merged pairs */
+    uint64_t mismatches;                     /* sum of mm(d) of the winners, as sfq_overlap_report's */
+    uint64_t n_x_wins, n_y_wins;             /* merged positions of the two "differ" rows of the table above */
+    uint64_t insert_hist[2 * SFQ_OVERLAP_MAX_LEN + 1];   /* as sfq_overlap_report's */
+} sfq_merge_report;
+/* host only, no GPU: sfq_overlap_check's refusals, plus qual_base outside 33 .. 124 */
+int sfq_merge_check(const sfq_merge* rule);
+/* The pairs of d_text[0, n) merged into d_out as described above; *out_bytes = the bytes of the result (on SFQ_E_OVERFLOW: the size
+ * needed), *merged_bytes = those of its first part.  Refusals as sfq_overlap_pairs' with cut set, the messages begin "merged mates:".
+ * SFQ_E_ARG: a null pointer (report may be NULL), n == 0, a rule that sfq_merge_check refuses, a range that ends behind the last
+ * record.  SFQ_E_FORMAT: lines that are no multiple of four, an odd number of records in the range, or a record of the range whose
+ * lines 2 and 4 differ in length; sfq_last_error names the smallest such record and its byte offset.  SFQ_E_UNSUPPORTED: a line of
+ * 4 GiB or more.  SFQ_E_OVERFLOW: a result larger than out_cap (never with out_cap >= n).  Every refusal is decided on the device
+ * before anything is written: a refused call writes nothing.  A call that succeeds writes d_out[0, *out_bytes) and nothing else; the
+ * text is never written.  d_out must not overlap the text.  The call runs on the context's stream and synchronises once.  Like the
+ * other side passes, it may read the whole aligned 16-byte units that hold the text's first and last byte. */
+int sfq_merge_pairs(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, const sfq_merge* rule, uint8_t* d_out, uint64_t out_cap,
+                    uint64_t* out_bytes, uint64_t* merged_bytes, sfq_merge_report* report);
+/* rule != NULL: sfq_decode_blocks_host, sfq_decode_block_range_host and sfq_decode_pair_range_host merge the pairs of the text they
+ * decoded (the struct is copied; SFQ_E_ARG, and the setting stays, where sfq_merge_check refuses it); NULL: off (default).  Order:
+ * the trim, the selection, THE MERGE, the pair split of the unmerged part, the pick.  The selection judges the mates, not the merged
+ * read.  The CRCs stay those of the decoded text.  What comes back is [merged part | rest]: *out_bytes is the total, sfq_get_merge
+ * gives the merged part's size in the result as handed back; sfq_get_pair_split's *first_bytes and sfq_decode_pair_range_host's *split
+ * are offsets into the result as handed back and lie behind the merged part.  The split runs on the rest alone, when the pair-split
+ * switch is on or the entry is the pair window; the pick runs on the merged part and on the rest separately, into one buffer, and all
+ * boundaries reported are those in the picked result.  An empty part is skipped by the split and by the pick; a call with nothing left
+ * returns SFQ_OK and 0 bytes.  sfq_decode_pair_range_host supplies the range itself, the window's pairs; the struct's own range must
+ * then be (0, UINT64_MAX), else SFQ_E_ARG.  SFQ_E_ARG at the decode call too where the overlap switch is on as well, or a selection
+ * whose pairs is 0.  Costs one more device buffer of the text's size, held while the switch is on.  The device-pointer decode entries
+ * are not affected.  Default off: nothing is launched, allocated or copied that is not today. */
+int sfq_ctx_set_merge(sfq_ctx* ctx, const sfq_merge* rule);
+/* 1: the last decode call merged, *out = what it found, *merged_bytes (may be NULL) = the merged part's bytes in the result as
+ * handed back; 0: it did not (both zeroed) */
+int sfq_get_merge(const sfq_ctx* ctx, sfq_merge_report* out, uint64_t* merged_bytes);
+
 /* ---- the ".sfq" container (host only) ----------------------------------------------------------
  * Replaces FilerSave + the info page (filer.cpp:217-242, config.cpp:334-347) for hosts that assemble an archive
  * themselves: info_text is the info page ("key=value\n" lines), then n_streams named byte streams (names of at most

@@ -43,6 +43,7 @@ EXPORTS = [
     "sfq_select_check", "sfq_select_parse", "sfq_select_records", "sfq_ctx_set_select", "sfq_get_select",
     "sfq_trim_check", "sfq_trim_parse", "sfq_trim_records", "sfq_ctx_set_trim", "sfq_get_trim",
     "sfq_overlap_check", "sfq_overlap_parse", "sfq_overlap_pairs", "sfq_ctx_set_overlap", "sfq_get_overlap",
+    "sfq_merge_check", "sfq_merge_pairs", "sfq_ctx_set_merge", "sfq_get_merge",
 ]
 
 
@@ -214,6 +215,30 @@ def overlap_parse(spec: str):
     return rule
 
 
+class Merge(C.Structure):
+    """sfq_merge: the rule of the mates' merge (mrg.hip).  Merge() is the CLI's `default,merge=PATH`: Overlap()'s search, qualities from 33."""
+    _fields_ = [("first_record", C.c_uint64), ("n_records", C.c_uint64), ("min_overlap", C.c_uint32), ("max_mm", C.c_uint32),
+                ("max_mm_pct", C.c_uint32), ("qual_base", C.c_uint32)]
+
+    def __init__(self, first_record=0, n_records=None, min_overlap=30, max_mm=5, max_mm_pct=20, qual_base=33):
+        super().__init__()
+        self.first_record, self.n_records = first_record, SELECT_TO_END if n_records is None else n_records
+        self.min_overlap, self.max_mm, self.max_mm_pct, self.qual_base = min_overlap, max_mm, max_mm_pct, qual_base
+
+
+class MergeReport(C.Structure):
+    """sfq_merge_report: what the merge found."""
+    _fields_ = [("n_pairs", C.c_uint64), ("n_skipped", C.c_uint64), ("n_merged", C.c_uint64),
+                ("text_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("merged_bytes", C.c_uint64),
+                ("bases_in", C.c_uint64), ("bases_merged", C.c_uint64), ("mismatches", C.c_uint64),
+                ("n_x_wins", C.c_uint64), ("n_y_wins", C.c_uint64), ("insert_hist", C.c_uint64 * (2 * OVERLAP_MAX_LEN + 1))]
+
+
+def merge_check(rule) -> int:
+    """sfq_merge_check (no GPU): 0, or E_ARG for a rule the library refuses."""
+    return int(lib().sfq_merge_check(C.byref(rule)))
+
+
 class SfqError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("slimfastq_amd error %d: %s" % (code, msg))
@@ -351,6 +376,10 @@ def lib():
         L.sfq_overlap_pairs.argtypes = [vp, vp, u64, C.POINTER(Overlap), vp, u64, u64p, C.POINTER(OverlapReport)]
         L.sfq_ctx_set_overlap.argtypes = [vp, C.POINTER(Overlap)]
         L.sfq_get_overlap.argtypes = [vp, C.POINTER(OverlapReport)]
+        L.sfq_merge_check.argtypes = [C.POINTER(Merge)]
+        L.sfq_merge_pairs.argtypes = [vp, vp, u64, C.POINTER(Merge), vp, u64, u64p, u64p, C.POINTER(MergeReport)]
+        L.sfq_ctx_set_merge.argtypes = [vp, C.POINTER(Merge)]
+        L.sfq_get_merge.argtypes = [vp, C.POINTER(MergeReport), u64p]
         _lib = L
     return _lib
 
@@ -735,6 +764,34 @@ class Context:
         if rc < 0:
             self._check(rc)
         return rep if rc == 1 else None
+
+    def merge_pairs(self, d_text, nbytes, rule, d_out, out_cap):
+        """The pairs of the interleaved FASTQ text in the device buffer at d_text, merged by the Merge into the one at d_out: the merged
+        records, then the pairs that do not merge (sfq_merge_pairs); returns (bytes of the result, bytes of its merged part,
+        MergeReport).  An SfqError of code E_OVERFLOW carries the size needed as .needed."""
+        n, m, rep = C.c_uint64(), C.c_uint64(), MergeReport()
+        rc = lib().sfq_merge_pairs(self._h, C.c_void_p(d_text), int(nbytes), C.byref(rule), C.c_void_p(d_out), int(out_cap),
+                                   C.byref(n), C.byref(m), C.byref(rep))
+        try:
+            self._check(rc)
+        except SfqError as e:
+            e.needed = int(n.value)
+            raise
+        return int(n.value), int(m.value), rep
+
+    def set_merge(self, rule=None):
+        """A Merge: decode_host, decode_range_host and decode_pair_range_host merge the pairs of the text they decoded, behind the trim
+        and the selection and in front of the split and the pick; the result is [merged part | rest] (get_merge() says what was found
+        and where the rest begins); None: off."""
+        self._check(lib().sfq_ctx_set_merge(self._h, None if rule is None else C.byref(rule)))
+
+    def get_merge(self):
+        """(MergeReport, bytes of the merged part in the result as handed back) of the last decode call; None where it did not merge."""
+        rep, m = MergeReport(), C.c_uint64()
+        rc = lib().sfq_get_merge(self._h, C.byref(rep), C.byref(m))
+        if rc < 0:
+            self._check(rc)
+        return (rep, int(m.value)) if rc == 1 else None
 
     def set_block_checksums(self, crcs):
         """The expected CRCs of the next decode call's blocks (consumed by it)."""

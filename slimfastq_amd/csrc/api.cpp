@@ -215,6 +215,10 @@ struct sfq_ctx {
     bool ovl_on = false; sfq_overlap ovl{};           // sfq_ctx_set_overlap
     DevBuf ovl_out;                                   // the cut text of a decoded text (while the switch is on with cut set)
     bool ovl_done = false; sfq_overlap_report ovl_report{};   // the last decode call's
+    // merged mates (mrg.hip): works in pair_work and reports through pair_pin too; nothing of this exists until the switch is on
+    bool mrg_on = false; sfq_merge mrg{};             // sfq_ctx_set_merge
+    DevBuf mrg_out;                                   // [merged part | rest] of a decoded text (while the switch is on)
+    bool mrg_done = false; sfq_merge_report mrg_report{}; u64 mrg_first = 0;  // the last decode call's; mrg_first: the merged part as handed back
 };
 
 namespace {
@@ -977,7 +981,7 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
         &ctx->oflags, &ctx->okbytes, &ctx->ofpos, &ctx->okoff, &ctx->ofilt, &ctx->orecmap, &ctx->olist, &ctx->line_off_o, &ctx->ono, &ctx->opiece,
         &ctx->otxt[0], &ctx->otxt[1], &ctx->otxt[2], &ctx->osize_all, &ctx->oroff_all, &ctx->oroff_k, &ctx->ocnt,
         &ctx->crc_tab, &ctx->crc_tiles, &ctx->crc_grps, &ctx->crc_bounds, &ctx->crc_out, &ctx->stats_acc, &ctx->qmap_dev,
-        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out, &ctx->pick_out, &ctx->sel_out, &ctx->trim_out, &ctx->ovl_out };
+        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out, &ctx->pick_out, &ctx->sel_out, &ctx->trim_out, &ctx->ovl_out, &ctx->mrg_out };
     for (DevBuf* b : all) release(*b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->pin2) (void)hipHostFree(ctx->pin2);
@@ -2713,6 +2717,115 @@ int sfq_get_overlap(const sfq_ctx* ctx, sfq_overlap_report* out) {
     return 1;
 }
 
+// ---- merged mates (mrg.hip) -------------------------------------------------------------------------------------------------------
+int sfq_merge_check(const sfq_merge* m) {
+    if (!m) return SFQ_E_ARG;
+    const sfq_overlap o{ m->first_record, m->n_records, m->min_overlap, m->max_mm, m->max_mm_pct, 1 };
+    if (sfq_overlap_check(&o) || m->qual_base < 33 || m->qual_base > 124) return SFQ_E_ARG;
+    return SFQ_OK;
+}
+// overlap_run's shape: one pass on the context's stream, one synchronise, in pair_run's working buffers and with its sizing.  *rep:
+// what the device found (out_bytes on SFQ_E_OVERFLOW too).
+static int merge_run(sfq_ctx* ctx, const u8* text, u64 n, const sfq_merge& s, u8* out, u64 out_cap, sfq_merge_report* rep) {
+    int rc;
+    const size_t infos = std::max({ sizeof(PairInfo), sizeof(PickInfo), sizeof(SelInfo), sizeof(TrimInfo), sizeof(OvlInfo), sizeof(MrgInfo) });
+    if ((rc = reserve_pinned_buf(ctx, ctx->pair_pin, ctx->pair_pin_cap, infos))) return rc;
+    const MrgJob job{ s.first_record, s.n_records, out_cap, s.min_overlap, s.max_mm, s.max_mm_pct, s.qual_base };
+    MrgInfo& got = *(MrgInfo*)ctx->pair_pin;
+    for (int attempt = 0; ; attempt++) {
+        const u64 cap = std::max<u64>(ctx->pair_cap, n / 64 + 1024), P = cap / 2 + 1;
+        auto up = [](u64 v) { return (v + 15) & ~15ull; };
+        u64 at = up(infos);
+        const u64 sc = at; at += up(qmap_scratch(text, n).bytes);
+        const u64 ls = at; at += up((4 * cap + 1) * 8);
+        const u64 ins = at; at += up(P * 4);
+        const u64 mm = at; at += up(P * 4);
+        const u64 mlen = at; at += up(P * 4);
+        const u64 mdst = at; at += up((P + 1) * 8);
+        const u64 ulen = at; at += up(P * 4);
+        const u64 udst = at; at += up((P + 1) * 8);
+        const u64 flag = at; at += up(P * 4);
+        const u64 mpos = at; at += up((P + 1) * 8);
+        const u64 list = at; at += up(P * 8);
+        const u64 from = at; at += up((P + 1) * 8);
+        const u64 dst = at; at += up((P + 1) * 8);
+        const u64 tmp = at; at += up((P / 1024 + 2) * 8);
+        if ((rc = reserve(ctx, ctx->pair_work, (size_t)at))) return rc;
+        u8* w = (u8*)ctx->pair_work.p;
+        MrgInfo* info = (MrgInfo*)w;
+        HIPC(hipMemsetAsync(info, 0, sizeof(MrgInfo), ctx->st));
+        const PairText t{ text, n, w + sc, nullptr };
+        const MrgArrays A{ (u64*)(w + ls), (u32*)(w + ins), (u32*)(w + mm), (u32*)(w + mlen), (u64*)(w + mdst), (u32*)(w + ulen), (u64*)(w + udst),
+                           (u32*)(w + flag), (u64*)(w + mpos), (u64*)(w + list), (u64*)(w + from), (u64*)(w + dst), (u64*)(w + tmp), cap };
+        launch_merge(t, A, job, out, info, ctx->st);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(ctx->pair_pin, info, sizeof(MrgInfo), hipMemcpyDeviceToHost, ctx->st));
+        HIPC(hipStreamSynchronize(ctx->st));
+        if (got.o.status != OVL_CAP) break;
+        if (attempt) return fail(ctx, SFQ_E_HIP, "merged mates: the records did not fit twice");
+        ctx->pair_cap = got.o.recs;
+    }
+    memset(rep, 0, sizeof *rep);
+    rep->text_bytes = n;
+    const OvlInfo& o = got.o;
+    if (o.status == OVL_LINES) return fail(ctx, SFQ_E_FORMAT, "merged mates: the text holds %llu lines, not a multiple of four", (unsigned long long)o.lines);
+    if (o.status == OVL_RANGE)
+        return fail(ctx, SFQ_E_ARG, "merged mates: records %llu..+%llu: not a range of the text's %llu records", (unsigned long long)s.first_record,
+                    (unsigned long long)s.n_records, (unsigned long long)o.recs);
+    if (o.status == OVL_ODD)
+        return fail(ctx, SFQ_E_FORMAT, "merged mates: the range holds %llu records, an odd number is no pairs",
+                    (unsigned long long)(s.n_records == ~0ull ? o.recs - s.first_record : s.n_records));
+    if (o.status == OVL_OK && o.bad_first != ~0ull)
+        return fail(ctx, SFQ_E_FORMAT, "merged mates: record %llu (at byte %llu) has a base line and a quality line of different lengths",
+                    (unsigned long long)o.bad_first, (unsigned long long)o.bad_off);
+    if (o.status == OVL_OK && o.toolong) return fail(ctx, SFQ_E_UNSUPPORTED, "merged mates: a line of 4 GiB or more");
+    if (o.status == OVL_ROOM) {
+        rep->out_bytes = got.out_bytes;
+        return fail(ctx, SFQ_E_OVERFLOW, "merged mates: the result needs %llu bytes", (unsigned long long)got.out_bytes);
+    }
+    if (o.status != OVL_OK || o.stop) return fail(ctx, SFQ_E_HIP, "merged mates: status %u", o.status);
+    rep->n_pairs = o.n_pairs; rep->n_skipped = o.n_skipped; rep->n_merged = got.n_merged;
+    rep->out_bytes = got.out_bytes; rep->merged_bytes = got.merged_bytes;
+    rep->bases_in = o.bases_in; rep->bases_merged = got.bases_merged; rep->mismatches = o.mismatches;
+    rep->n_x_wins = got.n_x_wins; rep->n_y_wins = got.n_y_wins;
+    memcpy(rep->insert_hist, o.hist, sizeof rep->insert_hist);
+    return SFQ_OK;
+}
+int sfq_merge_pairs(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, const sfq_merge* rule, uint8_t* d_out, uint64_t out_cap,
+                    uint64_t* out_bytes, uint64_t* merged_bytes, sfq_merge_report* report) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!d_text || !out_bytes || !merged_bytes || !rule || !d_out) return fail(ctx, SFQ_E_ARG, "null argument");
+    *out_bytes = 0; *merged_bytes = 0;
+    if (report) memset(report, 0, sizeof *report);
+    if (!n) return fail(ctx, SFQ_E_ARG, "merged mates: an empty text");
+    if (sfq_merge_check(rule)) return fail(ctx, SFQ_E_ARG, "merged mates: a rule that sfq_merge_check refuses");
+    HIPC(hipSetDevice(ctx->dev));
+    Settle settle(ctx);
+    sfq_merge_report rep;
+    const int rc = merge_run(ctx, d_text, n, *rule, d_out, out_cap, &rep);
+    if (rc == SFQ_E_OVERFLOW) *out_bytes = rep.out_bytes;
+    if (rc) return rc;
+    *out_bytes = rep.out_bytes; *merged_bytes = rep.merged_bytes;
+    if (report) *report = rep;
+    settle.ok = true;
+    return SFQ_OK;
+}
+int sfq_ctx_set_merge(sfq_ctx* ctx, const sfq_merge* rule) {
+    if (!ctx) return SFQ_E_ARG;
+    if (rule && sfq_merge_check(rule)) return fail(ctx, SFQ_E_ARG, "merged mates: a rule that sfq_merge_check refuses");
+    ctx->mrg_on = rule != nullptr;
+    if (rule) ctx->mrg = *rule;
+    else release(ctx->mrg_out);
+    return SFQ_OK;
+}
+int sfq_get_merge(const sfq_ctx* ctx, sfq_merge_report* out, uint64_t* merged_bytes) {
+    if (!ctx || !out) return SFQ_E_ARG;
+    if (merged_bytes) *merged_bytes = ctx->mrg_done ? ctx->mrg_first : 0;
+    if (!ctx->mrg_done) { memset(out, 0, sizeof *out); return 0; }
+    *out = ctx->mrg_report;
+    return 1;
+}
+
 int sfq_get_block_index(sfq_ctx* ctx, sfq_block_info* h_blocks, uint32_t cap) {
     if (!ctx || !h_blocks) return SFQ_E_ARG;
     if (cap < ctx->index.size()) return fail(ctx, SFQ_E_ARG, "index has %zu blocks", ctx->index.size());
@@ -2793,7 +2906,7 @@ static int decode_device(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_inf
     Settle settle(ctx);
     drop_encode_blobs(ctx);                             // whatever an encode left behind is not this archive's
     ctx->crcs.clear(); ctx->text_crc = 0;
-    ctx->pair_split_done = false; ctx->pick_done = 0; ctx->sel_done = false; ctx->trim_done = false; ctx->ovl_done = false;
+    ctx->pair_split_done = false; ctx->pick_done = 0; ctx->sel_done = false; ctx->trim_done = false; ctx->ovl_done = false; ctx->mrg_done = false;
     if (w.ranged && ctx->pair_split_on && !w.pairs)
         return fail(ctx, SFQ_E_UNSUPPORTED, "a window of blocks may start at a second mate and is not split: sfq_ctx_set_pair_split(ctx, 0) comes first");
     const bool check = ex.set;
@@ -3544,6 +3657,12 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
     }
     if (ctx->ovl_on && w.pairs && (ctx->ovl.first_record || ctx->ovl.n_records != ~0ull))
         return fail(ctx, SFQ_E_ARG, "overlapping mates: a window of pairs is the range: the rule's own must be (0, UINT64_MAX)");
+    if (ctx->mrg_on) {
+        if (ctx->ovl_on) return fail(ctx, SFQ_E_ARG, "merged mates: the overlap switch is on as well: a pair is cut or merged, not both");
+        if (ctx->sel_on && !ctx->sel.pairs) return fail(ctx, SFQ_E_ARG, "merged mates: a selection in front keeps or drops pairs (pairs must not be 0): the mates would fall out of step");
+        if (w.pairs && (ctx->mrg.first_record || ctx->mrg.n_records != ~0ull))
+            return fail(ctx, SFQ_E_ARG, "merged mates: a window of pairs is the range: the rule's own must be (0, UINT64_MAX)");
+    }
     HIPC(hipSetDevice(ctx->dev));
     int rc;
     // the index is untrusted: every stream's blocks must lie inside the bytes handed over (the device entry point cannot
@@ -3624,6 +3743,59 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
         d_text = (const u8*)ctx->sel_out.p;
         *out_bytes = ctx->sel_report.kept_bytes;
         if (!*out_bytes) return SFQ_OK;                    // nothing kept: neither the split nor the pick takes an empty text
+    }
+    if (ctx->mrg_on) {
+        // behind the selection, which judges the mates: [merged part | rest] from here on, two texts side by side.  The split takes the
+        // rest alone, the pick either part; an empty part is skipped by both.
+        if (!*out_bytes) return fail(ctx, SFQ_E_FORMAT, "merged mates: an empty text");
+        sfq_merge m = ctx->mrg;
+        if (w.pairs && !selected) { m.first_record = rec0; m.n_records = 2 * w.n_pairs; }     // the window's pairs, cut here (a selection has cut already)
+        if ((rc = reserve(ctx, ctx->mrg_out, (size_t)*out_bytes + 16))) return rc;
+        {
+            Settle settle(ctx);
+            if ((rc = merge_run(ctx, d_text, *out_bytes, m, (u8*)ctx->mrg_out.p, *out_bytes, &ctx->mrg_report))) return rc;
+            settle.ok = true;
+        }
+        ctx->mrg_done = true;
+        const u8* part[2] = { (const u8*)ctx->mrg_out.p, (const u8*)ctx->mrg_out.p + ctx->mrg_report.merged_bytes };
+        u64 size[2] = { ctx->mrg_report.merged_bytes, ctx->mrg_report.out_bytes - ctx->mrg_report.merged_bytes };
+        u64 first = 0, npairs = 0;                         // of the rest, where it is split
+        const bool splits = w.pairs || ctx->pair_split_on;
+        if (splits && size[1]) {
+            if ((rc = reserve(ctx, ctx->pair_out, (size_t)size[1] + 16))) return rc;
+            Settle settle(ctx);
+            PairInfo got;
+            if ((rc = pair_run(ctx, part[1], size[1], nullptr, 0, (u8*)ctx->pair_out.p, &got))) return rc;
+            settle.ok = true;
+            part[1] = (const u8*)ctx->pair_out.p;
+            first = got.split; npairs = got.recs[0] >> 1;
+        }
+        if (ctx->pick_what && size[0] + size[1]) {
+            if ((rc = reserve(ctx, ctx->pick_out, (size_t)(size[0] + size[1]) + 16))) return rc;
+            Settle settle(ctx);
+            u64 at = 0, recs = 0;
+            ctx->pick_text = size[0] + size[1];
+            for (int i = 0; i < 2; i++) {
+                if (!size[i]) continue;
+                PickInfo got;
+                if ((rc = pick_run(ctx, part[i], size[i], ctx->pick_what, 0, ~0ull, (u8*)ctx->pick_out.p + at, size[i], i && splits ? npairs : 0, &got))) return rc;
+                if (i && splits) first = got.mark_off;
+                part[i] = (const u8*)ctx->pick_out.p + at;
+                size[i] = got.nout; at += got.nout; recs += got.pieces;
+            }
+            settle.ok = true;
+            ctx->pick_done = ctx->pick_what; ctx->pick_recs = recs;
+        }
+        ctx->mrg_first = size[0];
+        if (splits) {
+            ctx->pair_split_done = true; ctx->pair_first = size[0] + first; ctx->pair_n = npairs;
+            if (split) *split = ctx->pair_first;
+        }
+        *out_bytes = size[0] + size[1];
+        if (size[0]) HIPC(hipMemcpyAsync(h_out, part[0], (size_t)size[0], hipMemcpyDeviceToHost, ctx->st));
+        if (size[1]) HIPC(hipMemcpyAsync(h_out + size[0], part[1], (size_t)size[1], hipMemcpyDeviceToHost, ctx->st));
+        HIPC(hipStreamSynchronize(ctx->st));
+        return SFQ_OK;
     }
     if (w.pairs && selected) {                             // the selection cut to the window: a plain split of what it kept
         if ((rc = reserve(ctx, ctx->pair_out, (size_t)*out_bytes + 16))) return rc;

@@ -18,7 +18,8 @@
 //   -k terms  : with -d: the records that pass a filter only (length, N count, mean quality, a motif, a sample), chosen on the GPU
 //   -c terms  : with -d: every record trimmed on the GPU (crops, quality cuts from either end, a quality window, a 3' adapter), in front of -k
 //   -o terms  : with -d: the mates of every pair overlapped on the GPU, the read-through behind the insert cut, the insert sizes counted;
-//               behind -c, in front of -k
+//               behind -c, in front of -k; with the term merge=PATH instead: every pair whose mates overlap merged into ONE record on the
+//               GPU (consensus bases, combined qualities) and written to PATH, behind -k; the other pairs go where they go without it
 // All model / coder work happens in libslimfastq_amd.so on the GPU; this file parses arguments, reads and
 // writes files and fills the info page.
 #include <sys/stat.h>
@@ -134,6 +135,12 @@ static void usage() {
            "                   nocut (count only, the text stays) and hist=PATH (the insert sizes as 'insert<TAB>pairs' lines; insert 0: no\n"
            "                   overlap found), or the word default; no record is dropped; goes with -R, -W, -p, -x, -k, -c and -K, not\n"
            "                   with -s or -b; without -q one line on stderr says what was found\n"
+           "                   merge=PATH among the terms: instead of cutting, every pair that has such an overlap is merged into one record\n"
+           "                   -- read 1's name, the insert's bases (where the mates differ the base of the higher quality), the combined\n"
+           "                   qualities -- and appended to PATH; the pairs that do not merge go to -u (and -p) as without it; behind -c and\n"
+           "                   -k, which judges the mates; hist= and the line on stderr then speak of the merged pairs; goes with -W, -p, -x\n"
+           "                   (PATH too), -k, -c and -K, with -R where the range is whole pairs (an even first record and count: -W\n"
+           "                   says it in pairs), not with nocut\n"
            "-M               : with -p on a compress run: compare the names of every pair of mates on the GPU before it is coded (the\n"
            "                   header's first word, without a final /1 or /2); a pair that differs ends the run with its index and both\n"
            "                   names, and no archive is written\n"
@@ -177,6 +184,7 @@ struct Opts {
     sfq_select sel; bool sel_either = false;                           // ... parsed: the rule (its range and pairs are the decode's), `either`
     bool trim = false; std::string trim_spec; sfq_trim trim_rule;      // -c terms, and the rule they parse to
     bool ovl = false; std::string ovl_spec, ovl_hist; sfq_overlap ovl_rule;        // -o terms, the hist=PATH among them, and the rule the others parse to
+    std::string ovl_merge;                                             // ... and the merge=PATH: the pairs are merged, not cut
 };
 // "FIRST:COUNT", both decimal, COUNT > 0
 static bool parse_range(const char* t, uint64_t& first, uint64_t& count) {
@@ -735,6 +743,15 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     }
     FILE* of = stdout;
     FILE* of2 = nullptr;
+    FILE* of3 = nullptr;                                                // -o merge=PATH: the merged records of every segment
+    const bool merging = o.ovl && !o.ovl_merge.empty();
+    if (merging) {
+        if (!o.overwrite && access(o.ovl_merge.c_str(), F_OK) == 0) { fprintf(stderr, "Can't write file '%s': File exists\n", o.ovl_merge.c_str()); exit(1); }
+        if (!o.overwrite && !usr.empty() && access(usr.c_str(), F_OK) == 0) { fprintf(stderr, "Can't write file '%s': File exists\n", usr.c_str()); exit(1); }
+        if (!o.overwrite && paired && access(o.pair.c_str(), F_OK) == 0) { fprintf(stderr, "Can't write file '%s': File exists\n", o.pair.c_str()); exit(1); }
+        of3 = fopen(o.ovl_merge.c_str(), "wb");
+        if (!of3) { fprintf(stderr, "Can't write file '%s'\n", o.ovl_merge.c_str()); exit(1); }
+    }
     if (paired) {
         if (!o.overwrite && access(o.pair.c_str(), F_OK) == 0) { fprintf(stderr, "Can't write file '%s': File exists\n", o.pair.c_str()); exit(1); }
         if (!o.overwrite && access(usr.c_str(), F_OK) == 0) { fprintf(stderr, "Can't write file '%s': File exists\n", usr.c_str()); exit(1); }
@@ -764,6 +781,8 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     uint64_t trim_recs = 0, trim_changed = 0, trim_emptied = 0, trim_in = 0, trim_out = 0;
     if (sfq_ctx_set_overlap(ctx, nullptr)) croak("%s", sfq_last_error(ctx));      // (set per segment: the range is the segment's)
     sfq_overlap_report ovl_sum; memset(&ovl_sum, 0, sizeof ovl_sum);
+    if (sfq_ctx_set_merge(ctx, nullptr)) croak("%s", sfq_last_error(ctx));
+    uint64_t mrg_merged = 0, mrg_bases = 0;                             // (the rest of a merge's report is summed in ovl_sum)
     const uint64_t rec_lines = !o.pick ? 4 : o.pick == SFQ_PICK_FASTA ? 2 : 1;      // the lines of a record in what a call hands back
     // walk the segments: each one's blocks, its slice of every stream (streams are segment-major), its prior
     size_t b0 = 0, pri_off = 0, chn_off = 0, rpr_off = 0;
@@ -863,7 +882,21 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
                 rule.first_record = (rec0 + sb[w0].first_record) & 1;
                 rule.n_records = (wrecs - rule.first_record) & ~1ull;
             }
-            if (!o.window && !rule.n_records) { if (sfq_ctx_set_overlap(ctx, nullptr)) croak("%s", sfq_last_error(ctx)); }
+            if (merging) {
+                // records outside a merge's range are dropped: under -R the range is the segment's share of -R itself (whole pairs), and
+                // behind -k the text that -k kept
+                if (o.select) { rule.first_record = 0; rule.n_records = ~0ull; }
+                else if (o.range) {
+                    uint64_t wrecs = 0;
+                    for (uint32_t b = w0; b < w0 + wn; b++) wrecs += sb[b].n_records;
+                    const uint64_t text0 = rec0 + sb[w0].first_record, lo = std::max(r_lo, text0), hi = std::min(r_hi, text0 + wrecs);
+                    rule.first_record = lo - text0; rule.n_records = hi - lo;
+                }
+                const sfq_merge m{ rule.first_record, rule.n_records, rule.min_overlap, rule.max_mm, rule.max_mm_pct, 33 };
+                if (!o.window && !m.n_records) { if (sfq_ctx_set_merge(ctx, nullptr)) croak("%s", sfq_last_error(ctx)); }
+                else if (sfq_ctx_set_merge(ctx, &m)) croak("-o: %s", sfq_last_error(ctx));
+            }
+            else if (!o.window && !rule.n_records) { if (sfq_ctx_set_overlap(ctx, nullptr)) croak("%s", sfq_last_error(ctx)); }
             else if (sfq_ctx_set_overlap(ctx, &rule)) croak("-o: %s", sfq_last_error(ctx));
         }
         sfq_result res;
@@ -906,7 +939,16 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             if (sfq_get_trim(ctx, &rep) != 1) croak("-c: the library did not trim");
             trim_recs += rep.n_records; trim_changed += rep.n_changed; trim_emptied += rep.n_emptied; trim_in += rep.bases_in; trim_out += rep.bases_out;
         }
-        if (o.ovl) {
+        uint64_t mbytes = 0;                                           // -o merge=: the call handed back the merged records first
+        if (merging) {
+            static sfq_merge_report rep;
+            const int did = sfq_get_merge(ctx, &rep, &mbytes);
+            if (did < 0) croak("-o: the library did not merge the pairs");
+            if (did == 1) {
+                ovl_sum.n_pairs += rep.n_pairs; ovl_sum.n_skipped += rep.n_skipped; mrg_merged += rep.n_merged; mrg_bases += rep.bases_merged;
+                for (size_t i = 0; i <= 2 * SFQ_OVERLAP_MAX_LEN; i++) ovl_sum.insert_hist[i] += rep.insert_hist[i];
+            }
+        } else if (o.ovl) {
             sfq_overlap_report rep;
             const int did = sfq_get_overlap(ctx, &rep);
             if (did < 0) croak("-o: the library did not search the pairs");
@@ -916,7 +958,7 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
                 for (size_t i = 0; i <= 2 * SFQ_OVERLAP_MAX_LEN; i++) ovl_sum.insert_hist[i] += rep.insert_hist[i];
             }
         }
-        if (o.range && !o.select) {                                    // the window's first and last block, cut to records: rec_lines lines each
+        if (o.range && !o.select && !merging) {                        // the window's first and last block, cut to records: rec_lines lines each
             const uint64_t wrec0 = rec0 + (uint64_t)w0 * sb[0].n_records;
             const uint64_t lo = std::max(r_lo, wrec0), hi = std::min(r_hi, wrec0 + res.n_records);
             const size_t from = records_end(dst, (size_t)got, lo - wrec0, rec_lines);
@@ -926,8 +968,10 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         // -p: the call handed back the first mates, then (from `first` on) the second mates
         uint64_t first = got;
         if (paired && got && sfq_get_pair_split(ctx, &first, nullptr) != 1) croak("-p: the library did not split the text");
-        auto write_out = [dst, got, first, of, of2]() {
-            return fwrite(dst, 1, (size_t)first, of) == first && (got == first || fwrite(dst + first, 1, (size_t)(got - first), of2) == got - first);
+        if (first < mbytes) first = got;                               // (nothing was split: no rest, or nothing kept)
+        auto write_out = [dst, got, first, mbytes, of, of2, of3]() {
+            return (!mbytes || fwrite(dst, 1, (size_t)mbytes, of3) == mbytes) && fwrite(dst + mbytes, 1, (size_t)(first - mbytes), of) == first - mbytes &&
+                   (got == first || fwrite(dst + first, 1, (size_t)(got - first), of2) == got - first);
         };
         writer.join();
         if (wbad) croak("USR: Error writing output");
@@ -943,6 +987,7 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     if (wbad) croak("USR: Error writing output");
     if (of != stdout) fclose(of); else fflush(stdout);
     if (of2) fclose(of2);
+    if (of3 && fclose(of3)) croak("-o merge=%s: error writing the file", o.ovl_merge.c_str());
     if (o.trim && !o.quiet)
         fprintf(stderr, "trimmed %llu of %llu records, %llu to nothing (%llu of %llu bases left)\n", (unsigned long long)trim_changed, (unsigned long long)trim_recs,
                 (unsigned long long)trim_emptied, (unsigned long long)trim_out, (unsigned long long)trim_in);
@@ -954,7 +999,12 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             if (ovl_sum.insert_hist[i]) fprintf(hf, "%zu\t%llu\n", i, (unsigned long long)ovl_sum.insert_hist[i]);
         if (fclose(hf)) croak("-o hist=%s: error writing the file", o.ovl_hist.c_str());
     }
-    if (o.ovl && !o.quiet) {
+    if (merging && !o.quiet) {
+        uint64_t seen = 0; size_t median = 0;                           // the median insert of the pairs that merged
+        for (size_t i = 1; i <= 2 * SFQ_OVERLAP_MAX_LEN && !median; i++) { seen += ovl_sum.insert_hist[i]; if (mrg_merged && 2 * seen >= mrg_merged) median = i; }
+        fprintf(stderr, "merged %llu of %llu pairs (%llu bases), median insert %zu\n", (unsigned long long)mrg_merged, (unsigned long long)ovl_sum.n_pairs,
+                (unsigned long long)mrg_bases, median);
+    } else if (o.ovl && !o.quiet) {
         // the median insert of the pairs that overlap
         uint64_t seen = 0; size_t median = 0;
         for (size_t i = 1; i <= 2 * SFQ_OVERLAP_MAX_LEN && !median; i++) { seen += ovl_sum.insert_hist[i]; if (ovl_sum.n_overlap && 2 * seen >= ovl_sum.n_overlap) median = i; }
@@ -1090,22 +1140,33 @@ int main(int argc, char** argv) {
     if (o.ovl) {
         // hist=PATH is the CLI's own term: the library parses the others
         std::string rest;
-        bool listed = false, others = false;
+        bool listed = false, others = false, merges = false;
         for (size_t at = 0; at <= o.ovl_spec.size(); ) {
             const size_t comma = std::min(o.ovl_spec.find(',', at), o.ovl_spec.size());
             const std::string term = o.ovl_spec.substr(at, comma - at);
             at = comma + 1;
             if (term.compare(0, 5, "hist=") == 0) { o.ovl_hist = term.substr(5); listed = true; continue; }
+            if (term.compare(0, 6, "merge=") == 0) { o.ovl_merge = term.substr(6); merges = true; continue; }
             if (others) rest += ",";
             rest += term; others = true;
         }
-        if (listed && !others) rest = "default";                       // hist=PATH alone: the default rule
+        if ((listed || merges) && !others) rest = "default";           // hist=PATH, merge=PATH alone: the default rule
         char err[256] = "";
         if (listed && o.ovl_hist.empty()) snprintf(err, sizeof err, "hist=: names no file");
+        else if (merges && o.ovl_merge.empty()) snprintf(err, sizeof err, "merge=: names no file");
         else if (sfq_overlap_parse(rest.c_str(), &o.ovl_rule, err, sizeof err) == 0) err[0] = 0;
         else if (!err[0]) snprintf(err, sizeof err, "not a list of terms");
         if (err[0]) {
             fprintf(stderr, "slimfastq: -o %s: %s\n", o.ovl_spec.c_str(), err);
+            return 1;
+        }
+        if (merges && !o.ovl_rule.cut) {
+            fprintf(stderr, "slimfastq: -o %s: nocut does not go with merge=PATH: a pair is merged or left whole, nothing is cut\n", o.ovl_spec.c_str());
+            return 1;
+        }
+        if (merges && o.range && ((o.r_first | o.r_count) & 1)) {
+            fprintf(stderr, "slimfastq: -o merge= with -R %llu:%llu: pairs are merged, so a range is whole pairs (an even first record and an even count); "
+                            "-W F:N names pairs\n", (unsigned long long)o.r_first, (unsigned long long)o.r_count);
             return 1;
         }
         if (g_encode || statistics || g_batch) {

@@ -91,4 +91,14 @@ __device__ __forceinline__ u32 base_codes(const u32 (&w)[4]) {
     return c;
 }
 
+// text[off, off + 8) from the aligned 8-byte words that hold it; a word without a byte of the text is not read (zeros)
+__device__ __forceinline__ u64 load8(const u8* text, i64 off, u64 n) {
+    const uintptr_t t0 = (uintptr_t)text, t1 = t0 + n, p = t0 + (uintptr_t)off, q = p & ~(uintptr_t)7;
+    const u32 sh = 8 * (u32)(p & 7);
+    u64 lo = 0, hi = 0;
+    if (q + 8 > t0 && q < t1) lo = *reinterpret_cast<const u64*>(q);
+    if (sh && q + 16 > t0 && q + 8 < t1) hi = *reinterpret_cast<const u64*>(q + 8);
+    return sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
+}
+
 }  // namespace textspan

@@ -340,6 +340,8 @@ void launch_pick(const PairText& t, u64* to, u64 cap, const PickJob& job, u32* l
 // its copy alone, for the passes whose pieces are whole records (sel.hip): P = info->pieces pieces, piece k = text[from[info->r0 + k] ..) to
 // out + dst[k], dst[P] = info->nout; bound: what the output can hold at most (the grid).  Nothing runs where info->status is set.
 void launch_pick_copy(const u64* dst, const u64* from, const u8* text, u64 bound, u8* out, PickInfo* info, hipStream_t st);
+// the same into out + *shift, where only the device knows where the pieces' part of a result begins (mrg.hip)
+void launch_pick_copy_at(const u64* dst, const u64* from, const u8* text, u64 bound, u8* out, const u64* shift, PickInfo* info, hipStream_t st);
 
 // Selected records (sel.hip): the records of [r0, r0 + nr) that pass a filter on their content -- the base line's length, its N count,
 // the quality line's mean, a motif in the base line -- and a reproducible sample, whole and in order.  Like pick.hip the pass finds the
@@ -438,3 +440,24 @@ struct OvlArrays { u64* ls; u32* ins; u32* mm; u32* keep; u32* cnt; u64* at; u32
 // t.starts is not used; info: zeroed by the caller.  out: job.out_cap bytes, of which info->copy.nout are written, and none unless
 // info->stop stays 0 and job.cut is set.
 void launch_overlap(const PairText& t, const OvlArrays& A, const OvlJob& job, u8* out, OvlInfo* info, hipStream_t st);
+// its steps in front of the cut alone, for the passes that want the winners (mrg.hip): the line starts, the rules (info->status, stop,
+// bad_first, bad_off, toolong, r0, nr) and the search.  Of A it uses ls, ins, mm and cap.
+void launch_overlap_search(const PairText& t, const OvlArrays& A, const OvlJob& job, OvlInfo* info, hipStream_t st);
+
+// Merged mates (mrg.hip): every pair of a range of records that has an accepted offset as ONE record -- consensus bases, combined
+// qualities (slimfastq_amd.h "merged mates") -- then the range's other pairs whole.  The search is ovl.hip's; the merged records are
+// computed and written by k_mrg_write, the others copied with pick.hip's copy.  *info tells the host, which synchronises once.
+// o: the search's (status OVL_*, stop, bad_first, toolong; n_pairs, n_skipped, bases_in, mismatches, hist as the report's; copy: the
+// piece copy of the unmerged part, copy.status != 0 wherever there is nothing to copy); merged_bytes: where that part begins;
+// out_bytes: the whole result, on OVL_ROOM the size needed
+constexpr u32 MRG_NOTHING = 0x100;
+struct MrgInfo { OvlInfo o; u64 merged_bytes, out_bytes, n_merged, bases_merged, n_x_wins, n_y_wins; };
+struct MrgJob { u64 r0, nr, out_cap; u32 min_ov, max_mm, max_pct, qual_base; };
+// ls, ins, mm as OvlArrays'.  Per pair of the range, P = cap / 2 + 1 entries (the scans' results one more): mlen, mdst: the merged
+// record's bytes (0: the pair does not merge) and where it goes; ulen, udst: the unmerged pair's bytes and where they go, counted from
+// merged_bytes; flag, mpos: 1 where the pair merges, and the merged pairs in front of it; list: the merged pairs; from, dst: the
+// unmerged pairs' pieces; tmp as launch_scan_u32 wants it for P
+struct MrgArrays { u64* ls; u32* ins; u32* mm; u32* mlen; u64* mdst; u32* ulen; u64* udst; u32* flag; u64* mpos; u64* list; u64* from; u64* dst; u64* tmp; u64 cap; };
+// t.starts is not used; info: zeroed by the caller.  out: job.out_cap bytes, of which info->out_bytes are written, and none unless
+// info->o.stop stays 0.
+void launch_merge(const PairText& t, const MrgArrays& A, const MrgJob& job, u8* out, MrgInfo* info, hipStream_t st);

@@ -79,15 +79,6 @@ __global__ __launch_bounds__(256) void k_ovl_lens(OvlInfo* info, const u64* __re
 // same of b', word j at index j + 1 between two guard words that hold no base
 struct PairBases { u64 a[WORDS], av[WORDS], b[WORDS + 2], bv[WORDS + 2]; };
 
-// text[off, off + 8) from the aligned 8-byte words that hold it; a word without a byte of the text is not read (zeros)
-__device__ __forceinline__ u64 load8(const u8* text, i64 off, u64 n) {
-    const uintptr_t t0 = (uintptr_t)text, t1 = t0 + n, p = t0 + (uintptr_t)off, q = p & ~(uintptr_t)7;
-    const u32 sh = 8 * (u32)(p & 7);
-    u64 lo = 0, hi = 0;
-    if (q + 8 > t0 && q < t1) lo = *reinterpret_cast<const u64*>(q);
-    if (sh && q + 16 > t0 && q + 8 < t1) hi = *reinterpret_cast<const u64*>(q + 8);
-    return sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
-}
 // (byte >> 1) & 3 of the eight bytes, byte j at bits 2 j (dev_lines.h base_codes, a word at a time)
 __device__ __forceinline__ u32 codes8(u64 w) {
     const u32 x[2] = { (u32)w, (u32)(w >> 32) };
@@ -288,7 +279,7 @@ __global__ void k_ovl_room(OvlInfo* info, OvlArrays A, u64 out_cap) {
 
 }  // namespace
 
-void launch_overlap(const PairText& t, const OvlArrays& A, const OvlJob& job, u8* out, OvlInfo* info, hipStream_t st) {
+void launch_overlap_search(const PairText& t, const OvlArrays& A, const OvlJob& job, OvlInfo* info, hipStream_t st) {
     const QmapScratch q = qmap_scratch(t.d, t.n);
     const u64* before = reinterpret_cast<const u64*>(t.scratch + q.before_off);
     const dim3 per_rec((u32)((A.cap + 255) / 256)), per_pair((u32)((A.cap / 2 + 4) / 4));
@@ -297,6 +288,10 @@ void launch_overlap(const PairText& t, const OvlArrays& A, const OvlJob& job, u8
     hipLaunchKernelGGL(k_ovl_lens, per_rec, dim3(256), 0, st, info, (const u64*)A.ls);
     hipLaunchKernelGGL(k_ovl_bad, dim3(1), dim3(64), 0, st, info, (const u64*)A.ls);
     hipLaunchKernelGGL(k_ovl_search, dim3(per_pair.x < 16 * MAX_WG ? per_pair.x : 16 * MAX_WG), dim3(256), 0, st, (const OvlInfo*)info, t.d, t.n, job, A);
+}
+void launch_overlap(const PairText& t, const OvlArrays& A, const OvlJob& job, u8* out, OvlInfo* info, hipStream_t st) {
+    const dim3 per_rec((u32)((A.cap + 255) / 256));
+    launch_overlap_search(t, A, job, info, st);
     hipLaunchKernelGGL(k_ovl_cut, dim3(per_rec.x < MAX_WG ? per_rec.x : MAX_WG), dim3(256), 0, st, info, job, A, t.n);
     if (!job.cut) return;
     launch_scan_u32(A.cnt, A.at, A.cap, A.tmp, st);

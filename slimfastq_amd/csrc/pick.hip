@@ -207,8 +207,10 @@ __device__ __forceinline__ void copy_units(u8* obase, u64 pos, u32 nun, u64 lo_o
 }
 // nspans: laid over an upper bound of the output's bytes; the real end is k_pick_room's
 template <bool GT>
-__global__ __launch_bounds__(256) void k_pick_copy(CopyJob J, PickInfo* info, u8* obase /* 16-byte aligned */, u32 mis /* the output starts at obase + mis */, u64 nspans) {
+__global__ __launch_bounds__(256) void k_pick_copy(CopyJob J, PickInfo* info, u8* obase /* 16-byte aligned */, u32 mis /* the output starts at obase + mis */, u64 nspans,
+                                                   const u64* shift /* may be null: ... and *shift bytes further */) {
     if (info->status) return;
+    if (shift) { const uintptr_t o = (uintptr_t)obase + mis + *shift; obase = reinterpret_cast<u8*>(o & ~(uintptr_t)15); mis = (u32)(o & 15); }
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const u64 P = info->pieces;
     J.nout = info->nout; J.from += info->r0;
@@ -249,13 +251,16 @@ PickLines pick_lines_of(u32 what, u64* from, u64* to, u64 cap) {
 }  // namespace
 
 // the copy's grid: over what the output can hold of the text
-static void launch_pick_copy(const u64* dst, const u64* from, const u8* text, u64 bound, u8* out, PickInfo* info, hipStream_t st, bool gt) {
+static void launch_pick_copy(const u64* dst, const u64* from, const u8* text, u64 bound, u8* out, PickInfo* info, hipStream_t st, bool gt, const u64* shift = nullptr) {
     const u32 omis = (u32)((uintptr_t)out & 15);
-    const u64 ospans = (omis + bound + SPAN - 1) / SPAN, otiles = ospans ? (ospans + 3) / 4 : 1;
+    const u64 ospans = ((shift ? 15 : omis) + bound + SPAN - 1) / SPAN, otiles = ospans ? (ospans + 3) / 4 : 1;
     const CopyJob J{ dst, from, (u64)(uintptr_t)text, bound };
     const dim3 grid((u32)(otiles < MAX_WG ? otiles : MAX_WG));
-    if (gt) hipLaunchKernelGGL(k_pick_copy<true>, grid, dim3(256), 0, st, J, info, out - omis, omis, ospans);
-    else hipLaunchKernelGGL(k_pick_copy<false>, grid, dim3(256), 0, st, J, info, out - omis, omis, ospans);
+    if (gt) hipLaunchKernelGGL(k_pick_copy<true>, grid, dim3(256), 0, st, J, info, out - omis, omis, ospans, shift);
+    else hipLaunchKernelGGL(k_pick_copy<false>, grid, dim3(256), 0, st, J, info, out - omis, omis, ospans, shift);
+}
+void launch_pick_copy_at(const u64* dst, const u64* from, const u8* text, u64 bound, u8* out, const u64* shift, PickInfo* info, hipStream_t st) {
+    launch_pick_copy(dst, from, text, bound, out, info, st, false, shift);
 }
 void launch_pick_copy(const u64* dst, const u64* from, const u8* text, u64 bound, u8* out, PickInfo* info, hipStream_t st) {
     launch_pick_copy(dst, from, text, bound, out, info, st, false);
