@@ -769,6 +769,81 @@ int sfq_ctx_set_merge(sfq_ctx* ctx, const sfq_merge* rule);
  * handed back; 0: it did not (both zeroed) */
 int sfq_get_merge(const sfq_ctx* ctx, sfq_merge_report* out, uint64_t* merged_bytes);
 
+/* ---- distinct records ---------------------------------------------------------------------------------------------------------
+ * The one step of read preparation in which a record's verdict depends on every other record: duplicates dropped, while the text
+ * is on the device (dd.hip).  Text to text like the selected records, whose line starts and copy the pass uses; no stream, coder or
+ * block format knows of it.  A lock-free hash set in device memory finds the candidates; the keys themselves decide.
+ * Lines and records: they are sfq_pick_lines' own.  A line ends at '\n'; a text without a final '\n' still ends in a line; '\r' is a
+ *   byte like any other.  Line lengths exclude the '\n'.
+ * Key of a record: the bytes of line 2 with 'a'..'z' replaced by 'A'..'Z'.  Every other byte stands as it is ('N', '.', '\r'); an
+ *   empty line 2 is a key like any other.  Names and qualities play no part.
+ * Units: with pairs == 0 a unit is a record.  With pairs != 0 a unit is the pair (record first_record + 2k, record first_record +
+ *   2k + 1) and its key the ORDERED pair (key X, key Y): two pair keys are equal only if X equals X and Y equals Y, lengths included
+ *   -- ("AC","G") is not ("A","CG"), and (X,Y) is not (Y,X).
+ * Duplicate: a unit of the range is a duplicate if an earlier unit of the same call's range (a smaller record number) has an equal
+ *   key, or, with use_set, a unit KEPT by an earlier successful call since the set was created or cleared has an equal key.
+ * Equality is byte equality of the keys, decided by comparing the keys, never by a hash alone: a distinct read is never dropped.
+ * Result: the units of the range that are no duplicates, whole (four lines a record), in order, with nothing between them.  Records
+ *   outside the range are dropped and never enter the set.  The FIRST occurrence is kept, whatever its qualities.  The result is
+ *   never larger than the text: out_cap = n always suffices.  Without a set a range always keeps something; with a set that knows
+ *   every key nothing is kept: SFQ_OK with *out_bytes = 0 and nothing written.
+ * Determinism: the result is a function of the text, the rule and the set's contents, not of scheduling. */
+typedef struct sfq_dedup {
+    uint64_t first_record, n_records;   /* n_records = UINT64_MAX: to the last record */
+    uint32_t pairs;                     /* 0: records stand alone; 1: records first_record + 2k, + 2k + 1 are one unit */
+    uint32_t use_set;                   /* != 0: the context's set counts too, and takes the keys of the units kept */
+} sfq_dedup;
+typedef struct sfq_dedup_report {
+    uint64_t n_in_range, n_units, n_kept;   /* n_in_range counts records; n_units and n_kept count units */
+    uint64_t n_dup_set;                     /* units whose key an earlier call left in the set */
+    uint64_t n_dup_call;                    /* the other duplicates; n_kept + n_dup_set + n_dup_call == n_units */
+    uint64_t text_bytes, kept_bytes;
+    uint64_t set_keys, set_key_bytes;       /* set contents after the call (0 without a set) */
+} sfq_dedup_report;
+/* host only, no GPU: SFQ_OK, or SFQ_E_ARG for a null pointer, n_records == 0, pairs > 1, or an odd first_record with pairs */
+int sfq_dedup_check(const sfq_dedup* rule);
+/* The distinct units of d_text[0, n) into d_out; *out_bytes = the bytes of the result (on SFQ_E_OVERFLOW: the size needed).
+ * SFQ_E_ARG: a null pointer (report may be NULL), n == 0, a rule that sfq_dedup_check refuses, a range that ends behind the last
+ * record, use_set without a set, or a set whose pairs differs from the rule's.  SFQ_E_FORMAT: lines that are no multiple of four;
+ * with pairs, an odd record count in the range.  SFQ_E_UNSUPPORTED: a record of 4 GiB or more, or with pairs a pair whose two keys hold as
+ * much together (decided before such a key is read).  SFQ_E_OVERFLOW: a result larger than
+ * out_cap.  SFQ_E_NOMEM: with use_set, the new keys do not fit the set's room; sfq_last_error names keys and bytes, needed and free.
+ * Every refusal is decided on the device before the copy and before the set is written: a refused call writes nothing and leaves
+ * the set exactly as it was.  A call that succeeds writes d_out[0, *out_bytes) and nothing else; the text is never written.  d_out
+ * must not overlap the text.  The call runs on the context's stream and synchronises once.  Like the other side passes, it may read
+ * the whole aligned 16-byte units that hold the text's first and last byte.  Working memory: like the other side passes the call
+ * lays its arrays out BEFORE the records are counted, for one record per 64 bytes of text (or the most records an earlier call on
+ * the context met; a text with more runs twice): about 97 bytes of arrays and 16 to 32 bytes of the call's own hash table per such
+ * record, which is 1.8 to 2.0 times the text's size in the context's working buffer (the selection's pass takes 1.3 times), kept
+ * until the context goes.  The kernels' grids are laid over those arrays; what lies behind the range's units returns at once. */
+int sfq_dedup_records(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, const sfq_dedup* rule,
+                      uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_dedup_report* report);
+/* The ONE set a context holds: room for max_keys keys whose bytes sum to at most max_key_bytes (a pair key's bytes are both mates'),
+ * fixed for its life: a slot table of the power of two of at least 2 max_keys 8-byte slots, 8 bytes (pairs: 12) a key and the key
+ * bytes, all in device memory.  pairs: the kind of rule that may use it.  SFQ_E_ARG if a set exists already, a capacity is 0,
+ * max_keys is 2^39 or more, max_key_bytes 2^46 (64 TiB) or more, or pairs > 1; SFQ_E_NOMEM from the allocator (no set then). */
+int sfq_dedup_set_create(sfq_ctx* ctx, uint64_t max_keys, uint64_t max_key_bytes, uint32_t pairs);
+/* empties the set and keeps its memory; SFQ_E_ARG without a set */
+int sfq_dedup_set_clear(sfq_ctx* ctx);
+/* destroys the set (SFQ_OK without one); sfq_ctx_destroy does it too */
+int sfq_dedup_set_destroy(sfq_ctx* ctx);
+/* 1 and the set's contents and capacities (every pointer may be NULL), or 0 where there is no set (all zeroed) */
+int sfq_dedup_set_info(const sfq_ctx* ctx, uint64_t* keys, uint64_t* key_bytes, uint64_t* max_keys, uint64_t* max_key_bytes);
+/* rule != NULL: sfq_decode_blocks_host, sfq_decode_block_range_host and sfq_decode_pair_range_host hand back the distinct units of
+ * the text they decoded (the struct is copied; SFQ_E_ARG, and the setting stays, where sfq_dedup_check refuses it); NULL: off
+ * (default).  Order: the trim, the overlap, the selection, THE DEDUP, the merge, the pair split or the window's cut, the pick.  The
+ * dedup judges what the selection kept, at its trimmed or cut length; the merge and the split then see an ordinary text.  The CRCs
+ * stay those of the decoded text.  out_cap keeps sizing the DECODED text.  Costs one more device buffer of the text's size, held
+ * while the switch is on, and sfq_dedup_records' working memory (above) in the buffer the passes share.  With use_set the calls share the context's set: duplicates are found across calls (segments).
+ * SFQ_E_ARG at the decode call while the pair split, the merge or a pair window is on and pairs == 0: the mates would fall out of
+ * step.  sfq_decode_pair_range_host supplies the range itself, the window's pairs, exactly as it does for the merge; the rule's own
+ * range must then be (0, UINT64_MAX), else SFQ_E_ARG.  Where a selection ran in front, it has cut the range already.  With
+ * nothing kept (only with a set) the _host entries return SFQ_OK and 0 bytes, and the passes behind are skipped.  The
+ * device-pointer decode entries are not affected.  Default off: nothing is launched, allocated or copied that is not today. */
+int sfq_ctx_set_dedup(sfq_ctx* ctx, const sfq_dedup* rule);
+/* 1: the last decode call dropped duplicates, *out = what it found; 0: it did not (*out zeroed) */
+int sfq_get_dedup(const sfq_ctx* ctx, sfq_dedup_report* out);
+
 /* ---- the ".sfq" container (host only) ----------------------------------------------------------
  * Replaces FilerSave + the info page (filer.cpp:217-242, config.cpp:334-347) for hosts that assemble an archive
  * themselves: info_text is the info page ("key=value\n" lines), then n_streams named byte streams (names of at most

@@ -44,6 +44,8 @@ EXPORTS = [
     "sfq_trim_check", "sfq_trim_parse", "sfq_trim_records", "sfq_ctx_set_trim", "sfq_get_trim",
     "sfq_overlap_check", "sfq_overlap_parse", "sfq_overlap_pairs", "sfq_ctx_set_overlap", "sfq_get_overlap",
     "sfq_merge_check", "sfq_merge_pairs", "sfq_ctx_set_merge", "sfq_get_merge",
+    "sfq_dedup_check", "sfq_dedup_records", "sfq_dedup_set_create", "sfq_dedup_set_clear", "sfq_dedup_set_destroy", "sfq_dedup_set_info",
+    "sfq_ctx_set_dedup", "sfq_get_dedup",
 ]
 
 
@@ -142,6 +144,28 @@ def select_parse(spec: str):
     if lib().sfq_select_parse(spec.encode(), C.byref(sel), C.byref(either), err, 256):
         raise ValueError(err.value.decode("latin1"))
     return sel, bool(either.value)
+
+
+class Dedup(C.Structure):
+    """sfq_dedup: the rule of a dedup (dd.hip).  Dedup() judges every record of the text by itself, without the context's set."""
+    _fields_ = [("first_record", C.c_uint64), ("n_records", C.c_uint64), ("pairs", C.c_uint32), ("use_set", C.c_uint32)]
+
+    def __init__(self, first_record=0, n_records=None, pairs=0, use_set=False):
+        super().__init__()
+        self.first_record, self.n_records = first_record, SELECT_TO_END if n_records is None else n_records
+        self.pairs, self.use_set = int(pairs), int(use_set)
+
+
+class DedupReport(C.Structure):
+    """sfq_dedup_report: what a dedup found."""
+    _fields_ = [("n_in_range", C.c_uint64), ("n_units", C.c_uint64), ("n_kept", C.c_uint64), ("n_dup_set", C.c_uint64),
+                ("n_dup_call", C.c_uint64), ("text_bytes", C.c_uint64), ("kept_bytes", C.c_uint64), ("set_keys", C.c_uint64),
+                ("set_key_bytes", C.c_uint64)]
+
+
+def dedup_check(rule) -> int:
+    """sfq_dedup_check (no GPU): 0, or E_ARG for a rule the library refuses."""
+    return int(lib().sfq_dedup_check(C.byref(rule)))
 
 
 class Trim(C.Structure):
@@ -380,6 +404,14 @@ def lib():
         L.sfq_merge_pairs.argtypes = [vp, vp, u64, C.POINTER(Merge), vp, u64, u64p, u64p, C.POINTER(MergeReport)]
         L.sfq_ctx_set_merge.argtypes = [vp, C.POINTER(Merge)]
         L.sfq_get_merge.argtypes = [vp, C.POINTER(MergeReport), u64p]
+        L.sfq_dedup_check.argtypes = [C.POINTER(Dedup)]
+        L.sfq_dedup_records.argtypes = [vp, vp, u64, C.POINTER(Dedup), vp, u64, u64p, C.POINTER(DedupReport)]
+        L.sfq_dedup_set_create.argtypes = [vp, u64, u64, C.c_uint32]
+        L.sfq_dedup_set_clear.argtypes = [vp]
+        L.sfq_dedup_set_destroy.argtypes = [vp]
+        L.sfq_dedup_set_info.argtypes = [vp, u64p, u64p, u64p, u64p]
+        L.sfq_ctx_set_dedup.argtypes = [vp, C.POINTER(Dedup)]
+        L.sfq_get_dedup.argtypes = [vp, C.POINTER(DedupReport)]
         _lib = L
     return _lib
 
@@ -792,6 +824,53 @@ class Context:
         if rc < 0:
             self._check(rc)
         return (rep, int(m.value)) if rc == 1 else None
+
+    def dedup_records(self, d_text, nbytes, rule, d_out, out_cap):
+        """The units (records, or pairs) of the FASTQ text in the device buffer at d_text whose base lines no earlier unit has --
+        nor, with rule.use_set, a unit an earlier call kept --, whole and in order, into the one at d_out (sfq_dedup_records);
+        returns (bytes written, DedupReport).  An SfqError of code E_OVERFLOW carries the size needed as .needed."""
+        n, rep = C.c_uint64(), DedupReport()
+        rc = lib().sfq_dedup_records(self._h, C.c_void_p(d_text), int(nbytes), C.byref(rule), C.c_void_p(d_out), int(out_cap),
+                                     C.byref(n), C.byref(rep))
+        try:
+            self._check(rc)
+        except SfqError as e:
+            e.needed = int(n.value)
+            raise
+        return int(n.value), rep
+
+    def dedup_set_create(self, max_keys, max_key_bytes, pairs=0):
+        """The context's one set of keys, of fixed capacity, that calls with use_set share (sfq_dedup_set_create)."""
+        self._check(lib().sfq_dedup_set_create(self._h, int(max_keys), int(max_key_bytes), int(pairs)))
+
+    def dedup_set_clear(self):
+        """Empties the set and keeps its memory."""
+        self._check(lib().sfq_dedup_set_clear(self._h))
+
+    def dedup_set_destroy(self):
+        """Destroys the set; nothing to do where there is none."""
+        self._check(lib().sfq_dedup_set_destroy(self._h))
+
+    def dedup_set_info(self):
+        """(keys, key bytes, max_keys, max_key_bytes) of the set; None where there is none."""
+        v = [C.c_uint64() for _ in range(4)]
+        rc = lib().sfq_dedup_set_info(self._h, *[C.byref(x) for x in v])
+        if rc < 0:
+            self._check(rc)
+        return tuple(int(x.value) for x in v) if rc == 1 else None
+
+    def set_dedup(self, rule=None):
+        """A Dedup: decode_host, decode_range_host and decode_pair_range_host return the distinct units of the text they decoded,
+        behind the selection and in front of the merge, the split and the pick (get_dedup() says what was found); None: off."""
+        self._check(lib().sfq_ctx_set_dedup(self._h, None if rule is None else C.byref(rule)))
+
+    def get_dedup(self):
+        """The DedupReport of the last decode call; None where it dropped no duplicates."""
+        rep = DedupReport()
+        rc = lib().sfq_get_dedup(self._h, C.byref(rep))
+        if rc < 0:
+            self._check(rc)
+        return rep if rc == 1 else None
 
     def set_block_checksums(self, crcs):
         """The expected CRCs of the next decode call's blocks (consumed by it)."""

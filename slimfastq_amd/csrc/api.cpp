@@ -219,6 +219,13 @@ struct sfq_ctx {
     bool mrg_on = false; sfq_merge mrg{};             // sfq_ctx_set_merge
     DevBuf mrg_out;                                   // [merged part | rest] of a decoded text (while the switch is on)
     bool mrg_done = false; sfq_merge_report mrg_report{}; u64 mrg_first = 0;  // the last decode call's; mrg_first: the merged part as handed back
+    // distinct records (dd.hip): works in pair_work and reports through pair_pin too; nothing of this exists until the switch is on or a set is created
+    bool dd_on = false; sfq_dedup dd{};               // sfq_ctx_set_dedup
+    DevBuf dd_out;                                    // the distinct records of a decoded text (while the switch is on)
+    bool dd_done = false; sfq_dedup_report dd_report{};       // the last decode call's
+    bool dset_on = false; u32 dset_pairs = 0;         // sfq_dedup_set_create: the one set, its slot table, per key its offset and lengths, the key bytes
+    DevBuf dset_slots, dset_koff, dset_klen, dset_arena;
+    u64 dset_nslots = 0, dset_max_keys = 0, dset_max_bytes = 0, dset_keys = 0, dset_bytes = 0;
 };
 
 namespace {
@@ -981,8 +988,9 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
         &ctx->oflags, &ctx->okbytes, &ctx->ofpos, &ctx->okoff, &ctx->ofilt, &ctx->orecmap, &ctx->olist, &ctx->line_off_o, &ctx->ono, &ctx->opiece,
         &ctx->otxt[0], &ctx->otxt[1], &ctx->otxt[2], &ctx->osize_all, &ctx->oroff_all, &ctx->oroff_k, &ctx->ocnt,
         &ctx->crc_tab, &ctx->crc_tiles, &ctx->crc_grps, &ctx->crc_bounds, &ctx->crc_out, &ctx->stats_acc, &ctx->qmap_dev,
-        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out, &ctx->pick_out, &ctx->sel_out, &ctx->trim_out, &ctx->ovl_out, &ctx->mrg_out };
+        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out, &ctx->pick_out, &ctx->sel_out, &ctx->trim_out, &ctx->ovl_out, &ctx->mrg_out, &ctx->dd_out };
     for (DevBuf* b : all) release(*b);
+    (void)sfq_dedup_set_destroy(ctx);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->pin2) (void)hipHostFree(ctx->pin2);
     if (ctx->crc_pin) (void)hipHostFree(ctx->crc_pin);
@@ -2826,6 +2834,173 @@ int sfq_get_merge(const sfq_ctx* ctx, sfq_merge_report* out, uint64_t* merged_by
     return 1;
 }
 
+// ---- distinct records (dd.hip) -----------------------------------------------------------------------------------------------------
+int sfq_dedup_check(const sfq_dedup* d) {
+    if (!d) return SFQ_E_ARG;
+    if (!d->n_records || d->pairs > 1 || (d->pairs && (d->first_record & 1))) return SFQ_E_ARG;
+    return SFQ_OK;
+}
+int sfq_dedup_set_create(sfq_ctx* ctx, uint64_t max_keys, uint64_t max_key_bytes, uint32_t pairs) {
+    if (!ctx) return SFQ_E_ARG;
+    if (ctx->dset_on) return fail(ctx, SFQ_E_ARG, "distinct records: the context holds a set already");
+    if (!max_keys || !max_key_bytes || pairs > 1 || max_keys >> 39 || max_key_bytes >> 46)       // (the arena's size and the arrays' products stay far inside 64 bits)
+        return fail(ctx, SFQ_E_ARG, "distinct records: a set of %llu keys and %llu key bytes, pairs %u", (unsigned long long)max_keys, (unsigned long long)max_key_bytes, pairs);
+    HIPC(hipSetDevice(ctx->dev));
+    u64 slots = 2;
+    while (slots < 2 * max_keys) slots <<= 1;
+    int rc;
+    if ((rc = reserve(ctx, ctx->dset_slots, (size_t)slots * 8)) || (rc = reserve(ctx, ctx->dset_koff, (size_t)max_keys * 8)) ||
+        (rc = reserve(ctx, ctx->dset_klen, (size_t)max_keys * 4 * (pairs ? 2 : 1))) || (rc = reserve(ctx, ctx->dset_arena, (size_t)((max_key_bytes + 31) & ~15ull)))) {
+        (void)hipGetLastError();
+        release(ctx->dset_slots); release(ctx->dset_koff); release(ctx->dset_klen); release(ctx->dset_arena);
+        return rc;
+    }
+    HIPC(hipMemsetAsync(ctx->dset_slots.p, 0, (size_t)slots * 8, ctx->st));
+    HIPC(hipStreamSynchronize(ctx->st));
+    ctx->dset_on = true; ctx->dset_pairs = pairs; ctx->dset_nslots = slots;
+    ctx->dset_max_keys = max_keys; ctx->dset_max_bytes = max_key_bytes; ctx->dset_keys = 0; ctx->dset_bytes = 0;
+    return SFQ_OK;
+}
+int sfq_dedup_set_clear(sfq_ctx* ctx) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!ctx->dset_on) return fail(ctx, SFQ_E_ARG, "distinct records: the context holds no set");
+    HIPC(hipSetDevice(ctx->dev));
+    HIPC(hipMemsetAsync(ctx->dset_slots.p, 0, (size_t)ctx->dset_nslots * 8, ctx->st));
+    HIPC(hipStreamSynchronize(ctx->st));
+    ctx->dset_keys = 0; ctx->dset_bytes = 0;
+    return SFQ_OK;
+}
+int sfq_dedup_set_destroy(sfq_ctx* ctx) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!ctx->dset_on) return SFQ_OK;
+    (void)hipSetDevice(ctx->dev);
+    release(ctx->dset_slots); release(ctx->dset_koff); release(ctx->dset_klen); release(ctx->dset_arena);
+    ctx->dset_on = false; ctx->dset_nslots = ctx->dset_max_keys = ctx->dset_max_bytes = ctx->dset_keys = ctx->dset_bytes = 0;
+    return SFQ_OK;
+}
+int sfq_dedup_set_info(const sfq_ctx* ctx, uint64_t* keys, uint64_t* key_bytes, uint64_t* max_keys, uint64_t* max_key_bytes) {
+    if (!ctx) return SFQ_E_ARG;
+    const bool on = ctx->dset_on;
+    if (keys) *keys = on ? ctx->dset_keys : 0;
+    if (key_bytes) *key_bytes = on ? ctx->dset_bytes : 0;
+    if (max_keys) *max_keys = on ? ctx->dset_max_keys : 0;
+    if (max_key_bytes) *max_key_bytes = on ? ctx->dset_max_bytes : 0;
+    return on ? 1 : 0;
+}
+// select_run's shape: one pass on the context's stream, one synchronise, in pair_run's working buffers and with its sizing; only a
+// text with more records than the arrays were laid out for runs twice.  *rep: what the device found (kept_bytes on SFQ_E_OVERFLOW too).
+static int dedup_run(sfq_ctx* ctx, const u8* text, u64 n, const sfq_dedup& d, u8* out, u64 out_cap, sfq_dedup_report* rep) {
+    int rc;
+    memset(rep, 0, sizeof *rep);
+    if (d.use_set && !ctx->dset_on) return fail(ctx, SFQ_E_ARG, "distinct records: use_set, and the context holds no set (sfq_dedup_set_create)");
+    if (d.use_set && ctx->dset_pairs != d.pairs) return fail(ctx, SFQ_E_ARG, "distinct records: the set was created with pairs %u, the rule says %u", ctx->dset_pairs, d.pairs);
+    const size_t info_bytes = std::max({ sizeof(PairInfo), sizeof(PickInfo), sizeof(SelInfo), sizeof(DdInfo) });
+    if ((rc = reserve_pinned_buf(ctx, ctx->pair_pin, ctx->pair_pin_cap, info_bytes))) return rc;
+    const DdJob job{ d.first_record, d.n_records, out_cap, d.pairs, d.use_set ? 1u : 0u };
+    DdSetDev S{};
+    if (d.use_set)
+        S = DdSetDev{ (u64*)ctx->dset_slots.p, ctx->dset_nslots - 1, (u64*)ctx->dset_koff.p, (u32*)ctx->dset_klen.p, (u8*)ctx->dset_arena.p,
+                      ctx->dset_max_keys, ctx->dset_max_bytes, ctx->dset_keys, ctx->dset_bytes };
+    DdInfo got;
+    for (int attempt = 0; ; attempt++) {
+        const u64 cap = std::max<u64>(ctx->pair_cap, n / 64 + 1024);
+        const u64 nlens = std::min(d.n_records, cap);
+        const u64 ucap = d.pairs ? (nlens + 1) / 2 : nlens;
+        u64 tcap = 2;
+        while (tcap < 2 * ucap) tcap <<= 1;
+        auto up = [](u64 v) { return (v + 15) & ~15ull; };
+        u64 at = up(info_bytes);
+        const u64 sc = at; at += up(qmap_scratch(text, n).bytes);
+        const u64 ls = at; at += up((4 * cap + 1) * 8);
+        const u64 hash = at; at += up(ucap * 8);
+        const u64 slot = at; at += up(ucap * 8);
+        const u64 inset = at; at += up(ucap);
+        const u64 kb = at; at += up(ucap * 4);
+        const u64 koffs = at; at += up((ucap + 1) * 8);
+        const u64 table = at; at += up(tcap * 8);
+        const u64 keep = at; at += up(nlens * 4);
+        const u64 rlen = at; at += up(nlens * 4);
+        const u64 pos = at; at += up((nlens + 1) * 8);
+        const u64 lens = at; at += up(nlens * 4);
+        const u64 from = at; at += up(nlens * 8);
+        const u64 dst = at; at += up((nlens + 1) * 8);
+        const u64 tmp = at; at += up((nlens / 1024 + 2) * 8);
+        if ((rc = reserve(ctx, ctx->pair_work, (size_t)at))) return rc;
+        u8* w = (u8*)ctx->pair_work.p;
+        DdInfo* info = (DdInfo*)w;
+        HIPC(hipMemsetAsync(info, 0, sizeof(DdInfo), ctx->st));
+        const PairText t{ text, n, w + sc, nullptr };
+        const DdArrays A{ (u64*)(w + ls), (u64*)(w + hash), (u64*)(w + slot), w + inset, (u32*)(w + kb), (u64*)(w + koffs), (u64*)(w + table),
+                          (u32*)(w + keep), (u32*)(w + rlen), (u64*)(w + pos), (u32*)(w + lens), (u64*)(w + from), (u64*)(w + dst), (u64*)(w + tmp),
+                          cap, nlens, ucap, tcap };
+        launch_dedup(t, A, job, S, out, info, ctx->st);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(ctx->pair_pin, info, sizeof(DdInfo), hipMemcpyDeviceToHost, ctx->st));
+        HIPC(hipStreamSynchronize(ctx->st));
+        memcpy(&got, ctx->pair_pin, sizeof(DdInfo));
+        if (got.status != DD_CAP) break;
+        if (attempt) return fail(ctx, SFQ_E_HIP, "distinct records: the records did not fit twice");
+        ctx->pair_cap = got.recs;
+    }
+    rep->text_bytes = n;
+    const unsigned long long r0 = d.first_record, nr = d.n_records, recs = got.recs;
+    switch (got.status) {
+    case DD_OK: break;
+    case DD_LINES: return fail(ctx, SFQ_E_FORMAT, "distinct records: the text holds %llu lines, not a multiple of four", (unsigned long long)got.lines);
+    case DD_RANGE:
+        if (d.n_records == ~0ull) return fail(ctx, SFQ_E_ARG, "distinct records: record %llu lies behind the text's %llu records", r0, recs);
+        return fail(ctx, SFQ_E_ARG, "distinct records: records %llu..+%llu end behind the text's %llu records", r0, nr, recs);
+    case DD_ODD: return fail(ctx, SFQ_E_FORMAT, "distinct records: the range holds an odd number of records, which are no pairs (records %llu.. of %llu)", r0, recs);
+    case DD_LONG: return fail(ctx, SFQ_E_UNSUPPORTED, "distinct records: a record of 4 GiB or more (or a pair whose base lines hold as much together)");
+    case DD_ROOM:
+        rep->kept_bytes = got.copy.nout;
+        return fail(ctx, SFQ_E_OVERFLOW, "distinct records: the result needs %llu bytes", (unsigned long long)got.copy.nout);
+    case DD_NOMEM:
+        return fail(ctx, SFQ_E_NOMEM, "distinct records: the set has no room: the call adds %llu keys of %llu bytes, %llu keys and %llu bytes are free",
+                    (unsigned long long)got.new_keys, (unsigned long long)got.new_bytes, (unsigned long long)(ctx->dset_max_keys - ctx->dset_keys),
+                    (unsigned long long)(ctx->dset_max_bytes - ctx->dset_bytes));
+    default: return fail(ctx, SFQ_E_HIP, "distinct records: status %u", got.status);
+    }
+    if (d.use_set) { ctx->dset_keys += got.new_keys; ctx->dset_bytes += got.new_bytes; }
+    rep->n_in_range = got.nr; rep->n_units = got.units; rep->n_kept = got.new_keys;
+    rep->n_dup_set = got.n_dup_set; rep->n_dup_call = got.n_dup_call; rep->kept_bytes = got.copy.nout;
+    if (d.use_set) { rep->set_keys = ctx->dset_keys; rep->set_key_bytes = ctx->dset_bytes; }
+    return SFQ_OK;
+}
+int sfq_dedup_records(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, const sfq_dedup* rule,
+                      uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_dedup_report* report) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!d_text || !d_out || !out_bytes || !rule) return fail(ctx, SFQ_E_ARG, "null argument");
+    *out_bytes = 0;
+    if (report) memset(report, 0, sizeof *report);
+    if (!n) return fail(ctx, SFQ_E_ARG, "distinct records: an empty text");
+    if (sfq_dedup_check(rule)) return fail(ctx, SFQ_E_ARG, "distinct records: a rule that sfq_dedup_check refuses");
+    HIPC(hipSetDevice(ctx->dev));
+    Settle settle(ctx);
+    sfq_dedup_report rep;
+    const int rc = dedup_run(ctx, d_text, n, *rule, d_out, out_cap, &rep);
+    if (rc == SFQ_E_OVERFLOW) *out_bytes = rep.kept_bytes;
+    if (rc) return rc;
+    *out_bytes = rep.kept_bytes;
+    if (report) *report = rep;
+    settle.ok = true;
+    return SFQ_OK;
+}
+int sfq_ctx_set_dedup(sfq_ctx* ctx, const sfq_dedup* rule) {
+    if (!ctx) return SFQ_E_ARG;
+    if (rule && sfq_dedup_check(rule)) return fail(ctx, SFQ_E_ARG, "distinct records: a rule that sfq_dedup_check refuses");
+    ctx->dd_on = rule != nullptr;
+    if (rule) ctx->dd = *rule;
+    else release(ctx->dd_out);
+    return SFQ_OK;
+}
+int sfq_get_dedup(const sfq_ctx* ctx, sfq_dedup_report* out) {
+    if (!ctx || !out) return SFQ_E_ARG;
+    if (!ctx->dd_done) { memset(out, 0, sizeof *out); return 0; }
+    *out = ctx->dd_report;
+    return 1;
+}
+
 int sfq_get_block_index(sfq_ctx* ctx, sfq_block_info* h_blocks, uint32_t cap) {
     if (!ctx || !h_blocks) return SFQ_E_ARG;
     if (cap < ctx->index.size()) return fail(ctx, SFQ_E_ARG, "index has %zu blocks", ctx->index.size());
@@ -2906,7 +3081,7 @@ static int decode_device(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_inf
     Settle settle(ctx);
     drop_encode_blobs(ctx);                             // whatever an encode left behind is not this archive's
     ctx->crcs.clear(); ctx->text_crc = 0;
-    ctx->pair_split_done = false; ctx->pick_done = 0; ctx->sel_done = false; ctx->trim_done = false; ctx->ovl_done = false; ctx->mrg_done = false;
+    ctx->pair_split_done = false; ctx->pick_done = 0; ctx->sel_done = false; ctx->trim_done = false; ctx->ovl_done = false; ctx->mrg_done = false; ctx->dd_done = false;
     if (w.ranged && ctx->pair_split_on && !w.pairs)
         return fail(ctx, SFQ_E_UNSUPPORTED, "a window of blocks may start at a second mate and is not split: sfq_ctx_set_pair_split(ctx, 0) comes first");
     const bool check = ex.set;
@@ -3663,6 +3838,13 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
         if (w.pairs && (ctx->mrg.first_record || ctx->mrg.n_records != ~0ull))
             return fail(ctx, SFQ_E_ARG, "merged mates: a window of pairs is the range: the rule's own must be (0, UINT64_MAX)");
     }
+    if (ctx->dd_on) {
+        if (!ctx->dd.pairs && (ctx->pair_split_on || ctx->mrg_on || w.pairs))
+            return fail(ctx, SFQ_E_ARG, "distinct records: while the pair split%s is on duplicates are pairs (pairs must not be 0): the mates would fall out of step",
+                        w.pairs ? " of a window of pairs" : ctx->mrg_on ? " or the merge" : "");
+        if (w.pairs && (ctx->dd.first_record || ctx->dd.n_records != ~0ull))
+            return fail(ctx, SFQ_E_ARG, "distinct records: a window of pairs is the range: the rule's own must be (0, UINT64_MAX)");
+    }
     HIPC(hipSetDevice(ctx->dev));
     int rc;
     // the index is untrusted: every stream's blocks must lie inside the bytes handed over (the device entry point cannot
@@ -3744,12 +3926,27 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
         *out_bytes = ctx->sel_report.kept_bytes;
         if (!*out_bytes) return SFQ_OK;                    // nothing kept: neither the split nor the pick takes an empty text
     }
+    const bool distinct = ctx->dd_on;
+    if (distinct) {                                        // behind the selection, whose kept records it judges; the merge, the split and the pick see what it kept
+        if (!*out_bytes) return fail(ctx, SFQ_E_FORMAT, "distinct records: an empty text");
+        if ((rc = reserve(ctx, ctx->dd_out, (size_t)*out_bytes + 16))) return rc;
+        Settle settle(ctx);
+        sfq_dedup d = ctx->dd;
+        if (w.pairs && !selected) { d.first_record = rec0; d.n_records = 2 * w.n_pairs; }     // the window's pairs, cut here (a selection has cut already)
+        if ((rc = dedup_run(ctx, d_text, *out_bytes, d, (u8*)ctx->dd_out.p, *out_bytes, &ctx->dd_report))) return rc;
+        settle.ok = true;
+        ctx->dd_done = true;
+        d_text = (const u8*)ctx->dd_out.p;
+        *out_bytes = ctx->dd_report.kept_bytes;
+        if (!*out_bytes) return SFQ_OK;                    // nothing kept (the set knew every key): as behind a selection that keeps nothing
+    }
+    const bool cut = selected || distinct;                 // a pass in front has cut the text to a window's pairs
     if (ctx->mrg_on) {
         // behind the selection, which judges the mates: [merged part | rest] from here on, two texts side by side.  The split takes the
         // rest alone, the pick either part; an empty part is skipped by both.
         if (!*out_bytes) return fail(ctx, SFQ_E_FORMAT, "merged mates: an empty text");
         sfq_merge m = ctx->mrg;
-        if (w.pairs && !selected) { m.first_record = rec0; m.n_records = 2 * w.n_pairs; }     // the window's pairs, cut here (a selection has cut already)
+        if (w.pairs && !cut) { m.first_record = rec0; m.n_records = 2 * w.n_pairs; }          // the window's pairs, cut here (a selection or the dedup has cut already)
         if ((rc = reserve(ctx, ctx->mrg_out, (size_t)*out_bytes + 16))) return rc;
         {
             Settle settle(ctx);
@@ -3797,7 +3994,7 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
         HIPC(hipStreamSynchronize(ctx->st));
         return SFQ_OK;
     }
-    if (w.pairs && selected) {                             // the selection cut to the window: a plain split of what it kept
+    if (w.pairs && cut) {                                  // the selection (or the dedup) cut to the window: a plain split of what it kept
         if ((rc = reserve(ctx, ctx->pair_out, (size_t)*out_bytes + 16))) return rc;
         Settle settle(ctx);
         PairInfo got;

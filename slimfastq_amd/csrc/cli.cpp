@@ -20,6 +20,8 @@
 //   -o terms  : with -d: the mates of every pair overlapped on the GPU, the read-through behind the insert cut, the insert sizes counted;
 //               behind -c, in front of -k; with the term merge=PATH instead: every pair whose mates overlap merged into ONE record on the
 //               GPU (consensus bases, combined qualities) and written to PATH, behind -k; the other pairs go where they go without it
+//   -D        : with -d: duplicates dropped on the GPU -- the first record (pair) of every base line (pair of base lines) only, over the
+//               whole archive: one set of keys in device memory lasts the run; behind -k, in front of merge=, -p and -x
 // All model / coder work happens in libslimfastq_amd.so on the GPU; this file parses arguments, reads and
 // writes files and fills the info page.
 #include <sys/stat.h>
@@ -141,6 +143,12 @@ static void usage() {
            "                   -k, which judges the mates; hist= and the line on stderr then speak of the merged pairs; goes with -W, -p, -x\n"
            "                   (PATH too), -k, -c and -K, with -R where the range is whole pairs (an even first record and count: -W\n"
            "                   says it in pairs), not with nocut\n"
+           "-D               : with -d: write only the first record of every base line (letter case aside; names and qualities play no\n"
+           "                   part), duplicates dropped on the GPU before the text comes back, over the whole archive: one hash set in\n"
+           "                   device memory lasts the run; of an archive written with -p, or with -p / -W: the first pair of every pair\n"
+           "                   of base lines; behind -c, -o and -k, in front of merge=, -p and -x; under -R / -W only the window's records\n"
+           "                   count; goes with -R, -p, -W, -x, -k, -c, -o and -K, not with -s or -b; without -q the last line on stderr\n"
+           "                   says what was kept\n"
            "-M               : with -p on a compress run: compare the names of every pair of mates on the GPU before it is coded (the\n"
            "                   header's first word, without a final /1 or /2); a pair that differs ends the run with its index and both\n"
            "                   names, and no archive is written\n"
@@ -185,6 +193,7 @@ struct Opts {
     bool trim = false; std::string trim_spec; sfq_trim trim_rule;      // -c terms, and the rule they parse to
     bool ovl = false; std::string ovl_spec, ovl_hist; sfq_overlap ovl_rule;        // -o terms, the hist=PATH among them, and the rule the others parse to
     std::string ovl_merge;                                             // ... and the merge=PATH: the pairs are merged, not cut
+    bool dedup = false;                                                // -D
 };
 // "FIRST:COUNT", both decimal, COUNT > 0
 static bool parse_range(const char* t, uint64_t& first, uint64_t& count) {
@@ -783,6 +792,25 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     sfq_overlap_report ovl_sum; memset(&ovl_sum, 0, sizeof ovl_sum);
     if (sfq_ctx_set_merge(ctx, nullptr)) croak("%s", sfq_last_error(ctx));
     uint64_t mrg_merged = 0, mrg_bases = 0;                             // (the rest of a merge's report is summed in ovl_sum)
+    // -D: one set for the whole run, so that duplicates are found across segments.  Keys: the archive's records (the range's; pairs:
+    // half); key bytes: the segments' text, a bound that is loose by about 2x (a key is the base line of a record of four lines)
+    const bool dd_pairs = o.dedup && (paired || o.window || merging || a.get_long("usr.pair", 0) == 1);      // (merge= wants pairs behind it)
+    uint64_t dd_units = 0, dd_kept = 0;
+    if (sfq_ctx_set_dedup(ctx, nullptr) || sfq_dedup_set_destroy(ctx)) croak("%s", sfq_last_error(ctx));       // (set per segment: the range is the segment's)
+    if (o.dedup) {
+        uint64_t keys = ranged ? r_hi - r_lo : blocks.back().first_record + blocks.back().n_records, bytes = 0;
+        if (dd_pairs) keys = (keys + 1) / 2;
+        size_t at = 0;
+        for (const sfqc::Segment& g : segs) {
+            if (g.nblocks == 0 || g.nblocks > blocks.size() - at) croak("bad segment index");
+            uint64_t coded = 0;                                         // (a segment without raw_bytes: the size its decode reserves)
+            for (size_t b = at; b < at + g.nblocks; b++) for (int s = 0; s < SFQ_NSTREAMS; s++) coded += blocks[b].size[s];
+            bytes += g.raw_bytes ? g.raw_bytes : coded * 8 + (1 << 20);
+            at += g.nblocks;
+        }
+        if (sfq_dedup_set_create(ctx, std::max<uint64_t>(keys, 1), std::max<uint64_t>(bytes, 1), dd_pairs ? 1 : 0)) croak("-D: %s", sfq_last_error(ctx));
+        tick("sfq_dedup_set_create");
+    }
     const uint64_t rec_lines = !o.pick ? 4 : o.pick == SFQ_PICK_FASTA ? 2 : 1;      // the lines of a record in what a call hands back
     // walk the segments: each one's blocks, its slice of every stream (streams are segment-major), its prior
     size_t b0 = 0, pri_off = 0, chn_off = 0, rpr_off = 0;
@@ -884,8 +912,8 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             }
             if (merging) {
                 // records outside a merge's range are dropped: under -R the range is the segment's share of -R itself (whole pairs), and
-                // behind -k the text that -k kept
-                if (o.select) { rule.first_record = 0; rule.n_records = ~0ull; }
+                // behind -k or -D the text that they kept (either has cut to the range already)
+                if (o.select || o.dedup) { rule.first_record = 0; rule.n_records = ~0ull; }
                 else if (o.range) {
                     uint64_t wrecs = 0;
                     for (uint32_t b = w0; b < w0 + wn; b++) wrecs += sb[b].n_records;
@@ -898,6 +926,24 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             }
             else if (!o.window && !rule.n_records) { if (sfq_ctx_set_overlap(ctx, nullptr)) croak("%s", sfq_last_error(ctx)); }
             else if (sfq_ctx_set_overlap(ctx, &rule)) croak("-o: %s", sfq_last_error(ctx));
+        }
+        if (o.dedup) {
+            // the range: the segment's share of -R, as -k's (behind -k the text that -k kept; -W: the library cuts to the window's pairs itself)
+            sfq_dedup rule{ 0, ~0ull, dd_pairs ? 1u : 0u, 1u };
+            const uint64_t text0 = rec0 + sb[w0].first_record;
+            if (o.range && !o.select) {
+                uint64_t wrecs = 0;
+                for (uint32_t b = w0; b < w0 + wn; b++) wrecs += sb[b].n_records;
+                const uint64_t lo = std::max(r_lo, text0), hi = std::min(r_hi, text0 + wrecs);
+                rule.first_record = lo - text0; rule.n_records = hi - lo;
+            }
+            if (dd_pairs && !o.window && !o.select) {
+                if (text0 & 1) croak("-D: the blocks of %s hold odd numbers of records, so that a decoded text begins at a second mate (record %llu): "
+                                     "duplicates of pairs are dropped from archives written with an even -B", fil.c_str(), (unsigned long long)text0);
+                if (rule.first_record & 1) croak("-D: -R begins at record %llu, a second mate: duplicates of an archive written from paired files are pairs, "
+                                                 "and a range begins at a first mate (-W F:N names pairs)", (unsigned long long)(text0 + rule.first_record));
+            }
+            if (sfq_ctx_set_dedup(ctx, &rule)) croak("-D: %s", sfq_last_error(ctx));
         }
         sfq_result res;
         int rc = 0;
@@ -934,6 +980,12 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             if (sfq_get_select(ctx, &rep) != 1) croak("-k: the library did not select");
             sel_kept += rep.n_kept; sel_seen += rep.n_in_range; sel_bytes += rep.kept_bytes; sel_text += rep.text_bytes;
         }
+        if (o.dedup) {
+            sfq_dedup_report rep;
+            const int did = sfq_get_dedup(ctx, &rep);                  // (0: a selection in front kept nothing)
+            if (did < 0) croak("-D: the library did not look for duplicates");
+            if (did == 1) { dd_units += rep.n_units; dd_kept += rep.n_kept; }
+        }
         if (o.trim) {
             sfq_trim_report rep;
             if (sfq_get_trim(ctx, &rep) != 1) croak("-c: the library did not trim");
@@ -958,7 +1010,7 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
                 for (size_t i = 0; i <= 2 * SFQ_OVERLAP_MAX_LEN; i++) ovl_sum.insert_hist[i] += rep.insert_hist[i];
             }
         }
-        if (o.range && !o.select && !merging) {                        // the window's first and last block, cut to records: rec_lines lines each
+        if (o.range && !o.select && !merging && !o.dedup) {                        // the window's first and last block, cut to records: rec_lines lines each
             const uint64_t wrec0 = rec0 + (uint64_t)w0 * sb[0].n_records;
             const uint64_t lo = std::max(r_lo, wrec0), hi = std::min(r_hi, wrec0 + res.n_records);
             const size_t from = records_end(dst, (size_t)got, lo - wrec0, rec_lines);
@@ -1014,6 +1066,12 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     if (o.select && !o.quiet)
         fprintf(stderr, "kept %llu of %llu records (%llu of %llu bytes)\n", (unsigned long long)sel_kept, (unsigned long long)sel_seen,
                 (unsigned long long)sel_bytes, (unsigned long long)sel_text);
+    if (o.dedup) {
+        if (sfq_ctx_set_dedup(ctx, nullptr) || sfq_dedup_set_destroy(ctx)) croak("%s", sfq_last_error(ctx));
+        if (!o.quiet)
+            fprintf(stderr, "kept %llu of %llu %s (%llu duplicates, %.2f %%)\n", (unsigned long long)dd_kept, (unsigned long long)dd_units, dd_pairs ? "pairs" : "reads",
+                    (unsigned long long)(dd_units - dd_kept), dd_units ? 100.0 * (double)(dd_units - dd_kept) / (double)dd_units : 0.0);
+    }
 }
 
 int main(int argc, char** argv) {
@@ -1021,7 +1079,7 @@ int main(int argc, char** argv) {
     Opts o;
     bool statistics = false;
     if (argc == 1) usage();
-    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKYM1234u:f:l:B:g:S:T:C:t:R:Q:p:W:x:k:c:o:")) != -1;) {
+    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKYMD1234u:f:l:B:g:S:T:C:t:R:Q:p:W:x:k:c:o:")) != -1;) {
         switch (opt) {
         case 'u': g_usr = optarg; break;
         case 'f': fil = optarg; break;
@@ -1063,6 +1121,7 @@ int main(int argc, char** argv) {
         case 'k': o.select = true; o.select_spec = optarg; break;
         case 'c': o.trim = true; o.trim_spec = optarg; break;
         case 'o': o.ovl = true; o.ovl_spec = optarg; break;
+        case 'D': o.dedup = true; break;
         case 'C': o.chain_reads = strtol(optarg, 0, 0); break;
         case 't': o.io_threads = std::min(64, std::max(1, atoi(optarg))); break;
         case 'v': printf("Version %s\nInternal format version=%u (block format %u)\n", kUserVersion, kInternalVersion, kBlockVersion); exit(0);
@@ -1174,6 +1233,12 @@ int main(int argc, char** argv) {
                     statistics ? "; -s writes no text" : g_batch ? "; it does not go with -b" : "");
             return 1;
         }
+    }
+
+    if (o.dedup && (g_encode || statistics || g_batch)) {
+        fprintf(stderr, "slimfastq: -D (distinct records) goes with -d: it drops the duplicates of what a decode writes%s\n",
+                statistics ? "; -s writes no text" : g_batch ? "; it does not go with -b" : "");
+        return 1;
     }
 
     if (!o.pair.empty() && g_batch) {

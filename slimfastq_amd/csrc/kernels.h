@@ -461,3 +461,39 @@ struct MrgArrays { u64* ls; u32* ins; u32* mm; u32* mlen; u64* mdst; u32* ulen; 
 // t.starts is not used; info: zeroed by the caller.  out: job.out_cap bytes, of which info->out_bytes are written, and none unless
 // info->o.stop stays 0.
 void launch_merge(const PairText& t, const MrgArrays& A, const MrgJob& job, u8* out, MrgInfo* info, hipStream_t st);
+
+// Distinct records (dd.hip): the units (records; under pairs, pairs) of [r0, r0 + nr) whose key -- line 2 with 'a'..'z' folded, under
+// pairs both mates' in order -- no earlier unit of the range has and, with a set, no unit an earlier call kept; whole and in order.
+// Like sel.hip the pass finds the lines itself, decides every refusal on the device and copies with pick.hip's copy.
+enum DdStatus : u32 {
+    DD_OK = 0,
+    DD_LINES,               // the text's lines are no multiple of four
+    DD_RANGE,               // records that end behind the text's last record
+    DD_CAP,                 // more records than the arrays hold: info->recs says how many, nothing else was done
+    DD_LONG,                // a record of 4 GiB or more, or a pair whose keys hold as much together
+    DD_ODD,                 // pairs: an odd number of records in the range
+    DD_ROOM,                // the kept records need more than the output holds: info->copy.nout says how much
+    DD_NOMEM,               // the set has no room for the new keys: info->new_keys, new_bytes say what the call adds
+    DD_PROBE                // a probe sequence found no slot (cannot be: a table holds twice its keys)
+};
+constexpr u32 DD_NOTHING = 0x100;                              // copy.status where no unit is kept (status stays DD_OK), as SEL_NOTHING
+// copy: what k_pick_copy reads, as SelInfo's.  units: the range's; tmask: the call's table's slots - 1; new_keys, new_bytes: the kept
+// units and (with a set) their keys' bytes
+struct DdInfo { PickInfo copy; u64 lines, recs, r0, nr; u32 status, pad; u64 units, tmask, n_dup_set, n_dup_call, new_keys, new_bytes; };
+struct DdJob { u64 r0, nr, out_cap; u32 pairs, use_set; };
+// The set of a context, on the device: slots[smask + 1] (a power of two of at least 2 max_keys): 0, or bit 63 | a 23-bit fingerprint of
+// the key's hash | the key's number k; koff[k]: where key k begins in the arena, klen[k] (pairs: klen[2 k], klen[2 k + 1]): its
+// lines' lengths, one behind the other there; arena: max_bytes bytes (allocated to a multiple of 16).  keys, bytes: what it holds
+// BEFORE the call -- the host keeps the counts and adds info->new_keys, new_bytes after a call that succeeds.
+struct DdSetDev { u64* slots; u64 smask; u64* koff; u32* klen; u8* arena; u64 max_keys, max_bytes, keys, bytes; };
+// ls[4 cap + 1] as SelArrays'; per unit, ucap = (nlens + G - 1) / G entries (G = 2 under pairs): hash, slot (the unit's slot in the
+// call's table), inset (the key is in the set; written for the earliest unit of a key alone), kb (the key bytes a kept unit adds),
+// koffs[ucap + 1] their scan; table[tcap]: the call's table, tcap a power of two of at least 2 ucap; keep, rlen, lens, from: nlens
+// entries, pos, dst: nlens + 1, tmp as launch_scan_u32 wants it for nlens; nlens = min(nr, cap)
+struct DdArrays {
+    u64* ls; u64* hash; u64* slot; u8* inset; u32* kb; u64* koffs; u64* table; u32* keep; u32* rlen; u64* pos; u32* lens; u64* from; u64* dst; u64* tmp;
+    u64 cap, nlens, ucap, tcap;
+};
+// t.starts is not used; info: zeroed by the caller; S: all zero without job.use_set.  out: job.out_cap bytes, of which info->copy.nout
+// are written, and none unless info->status and info->copy.status stay 0.  The set is written only where info->status stays 0.
+void launch_dedup(const PairText& t, const DdArrays& A, const DdJob& job, const DdSetDev& S, u8* out, DdInfo* info, hipStream_t st);
