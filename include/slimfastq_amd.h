@@ -844,6 +844,102 @@ int sfq_ctx_set_dedup(sfq_ctx* ctx, const sfq_dedup* rule);
 /* 1: the last decode call dropped duplicates, *out = what it found; 0: it did not (*out zeroed) */
 int sfq_get_dedup(const sfq_ctx* ctx, sfq_dedup_report* out);
 
+/* ---- screened records ---------------------------------------------------------------------------------------------------------
+ * Reads screened against reference sequences while the text is on the device (scr.hip): the reads that share k-mers with phiX, an
+ * adapter, rRNA or a host genome dropped -- or, the other way round, only the reads that hit a bait kept.  Text to text like the
+ * distinct records, whose line starts and copy the pass uses; no stream, coder or block format knows of it.
+ * Lines and records: they are sfq_pick_lines' own.  A line ends at '\n'; a text without a final '\n' still ends in a line; '\r' is a
+ *   byte like any other.
+ * Codes: 'A' 'a' 0, 'C' 'c' 1, 'G' 'g' 2, 'T' 't' 3.  Every other byte is a BREAK: 'N', '.', '\r', '\n', '>', and so on.
+ * Window: k consecutive bytes of one sequence, none of them a break, 4 <= k <= 31.  Its forward value is the sum of
+ *   code(b[j]) * 4^(k-1-j); its reverse-complement value that of the reversed window with the codes 3 - c; its CANONICAL value the
+ *   smaller of the two.  A palindromic window has both equal: it is one window and one k-mer.
+ * Sequence text (what a reference is to the library): any bytes.  Its windows are all runs of k bytes without a break; a '\n' or any
+ *   other break separates sequences.  Nothing else is parsed (sfq_fasta_sequences makes one of a FASTA file).
+ * Set: the canonical values of all windows of all sequence texts added since it was created or cleared.  It is a set: a k-mer added
+ *   twice is in it once.  Membership is exact: the whole value is stored, no fingerprint, and there are no false positives.
+ * Read: for a record, W is the number of windows of line 2 and H the number of them whose canonical value is in the set.  H counts by
+ *   position: a k-mer of the set that occurs three times in the read counts three.  Headers, '+' lines and qualities play no part; a
+ *   window never crosses a line end.
+ * Matched: a record is matched when H >= min_hits AND 100 * H >= min_pct * W, in 64-bit arithmetic.  min_hits >= 1: a read without a
+ *   window is never matched.
+ * Units: pairs == 0: a unit is a record, matched when the record is.  pairs == 1: a unit is the records first_record + 2k and
+ *   + 2k + 1 together, matched when EITHER mate is; pairs == 2: the same two records, matched when BOTH mates are.
+ * Kept: a unit of the range is kept when (matched) == (keep_matched != 0): keep_matched = 0 decontaminates, 1 baits.
+ * Result: the kept units whole (four lines a record), in order, with nothing between them; records outside the range are dropped.
+ *   The result is never larger than the text: out_cap = n always suffices.  With nothing kept: SFQ_OK, *out_bytes = 0, nothing written.
+ * Determinism: the result is a function of the text, the rule and the set's contents AS A SET, never of scheduling or slot order. */
+typedef struct sfq_screen {
+    uint64_t first_record, n_records;   /* n_records = UINT64_MAX: to the last record */
+    uint32_t pairs;                     /* 0, 1 (either mate), 2 (both mates) */
+    uint32_t min_hits;                  /* >= 1 */
+    uint32_t min_pct;                   /* 0 .. 100 */
+    uint32_t keep_matched;              /* 0: drop the matched units; else keep only them */
+} sfq_screen;
+typedef struct sfq_screen_report {
+    uint64_t n_in_range, n_units, n_kept;   /* n_in_range counts records; n_units and n_kept count units */
+    uint64_t n_matched_records;             /* the range's records that are matched, each by itself whatever pairs says */
+    uint64_t n_windows, n_hits;             /* the sums of W and H over the range's records */
+    uint64_t text_bytes, kept_bytes, set_kmers;
+} sfq_screen_report;
+/* host only, no GPU: SFQ_OK, or SFQ_E_ARG for a null pointer, n_records == 0, pairs > 2, an odd first_record with pairs, min_hits == 0
+ * or min_pct > 100 */
+int sfq_screen_check(const sfq_screen* rule);
+/* host only: a rule and k from the terms of the CLI's -G: "k=N" (4 .. 31, default 27), "hits=N" (default 1), "pct=N" (0 .. 100, default
+ * 0), "keep" (keep_matched = 1), "both" (pairs = 2), "either" (pairs = 1), separated by commas; a term "ref=..." is the CLI's own and is
+ * skipped.  Without "both" and "either" pairs stays 0: the caller knows whether records are pairs.  The range is (0, UINT64_MAX).
+ * SFQ_OK, or SFQ_E_ARG with a message in err[0, err_cap) (err may be NULL). */
+int sfq_screen_parse(const char* spec, sfq_screen* rule, uint32_t* k, char* err, uint64_t err_cap);
+/* host only: a FASTA file's bytes as a sequence text.  A line whose first byte is '>' becomes a single '\n', the break between two
+ * records; every other line is copied without its '\n' and without a '\r' in front of it, so that k-mers run across the wrapped lines
+ * of one record and never across two records.  Returns the size of the result, never larger than n; out == NULL: the size only;
+ * SFQ_E_OVERFLOW where it is larger than cap (nothing is written then), SFQ_E_ARG for fasta == NULL with n != 0. */
+int64_t sfq_fasta_sequences(const uint8_t* fasta, uint64_t n, uint8_t* out, uint64_t cap);
+/* The ONE set of k-mers a context holds: a table of the power of two of at least 2 max_kmers 8-byte slots in device memory, fixed for
+ * its life.  A slot is 0 or 2^63 | the canonical value; a k-mer's home slot is (canonical * 0x9E3779B97F4A7C15 mod 2^64) >> (64 -
+ * log2(slots)), probing is linear.  SFQ_E_ARG if a set exists already, k is outside 4 .. 31, max_kmers is 0 or 2^39 or more;
+ * SFQ_E_NOMEM from the allocator (no set then). */
+int sfq_screen_set_create(sfq_ctx* ctx, uint32_t k, uint64_t max_kmers);
+/* Adds the windows of the sequence text h_seq[0, n), HOST bytes.  The library copies them up in pieces of 4 MiB that overlap by k - 1
+ * bytes: the windows are those of the whole text however it is cut.  Windows never span two CALLS: a call's text ends in a break.
+ * SFQ_E_ARG: no set, h_seq == NULL, n == 0.  SFQ_E_NOMEM: the set would hold more than max_kmers k-mers (or a probe found no slot);
+ * the library then CLEARS the set: a refused add leaves the set EMPTY, not half-filled. */
+int sfq_screen_set_add(sfq_ctx* ctx, const uint8_t* h_seq, uint64_t n);
+/* empties the set and keeps its memory; SFQ_E_ARG without a set */
+int sfq_screen_set_clear(sfq_ctx* ctx);
+/* destroys the set (SFQ_OK without one); sfq_ctx_destroy does it too */
+int sfq_screen_set_destroy(sfq_ctx* ctx);
+/* 1 and the set's k, contents and capacity (every pointer may be NULL), or 0 where there is no set (all zeroed) */
+int sfq_screen_set_info(const sfq_ctx* ctx, uint32_t* k, uint64_t* kmers, uint64_t* max_kmers);
+/* The kept units of d_text[0, n) into d_out; *out_bytes = the bytes of the result (on SFQ_E_OVERFLOW: the size needed).
+ * SFQ_E_ARG: a null pointer (report may be NULL), n == 0, a rule that sfq_screen_check refuses, a range that ends behind the last
+ * record, no set.  SFQ_E_FORMAT: lines that are no multiple of four; with pairs, an odd record count in the range.
+ * SFQ_E_UNSUPPORTED: a record of 4 GiB or more (decided before its line is walked).  SFQ_E_OVERFLOW: a result larger than out_cap.
+ * Every refusal is decided on the device before the copy: a refused call writes nothing.  A call that succeeds writes
+ * d_out[0, *out_bytes) and nothing else; the text is never written and the set is never written by a screening call.  d_out must not
+ * overlap the text.  The call runs on the context's stream and synchronises once.  Like the other side passes, it may read the whole
+ * aligned 16-byte units that hold the text's first and last byte.  Working memory: like the other side passes the call lays its arrays
+ * out BEFORE the records are counted, for one record per 64 bytes of text (or the most records an earlier call on the context met; a
+ * text with more runs twice): 76 bytes of arrays per such record, which with the line counts' scratch is 1.2 to 1.3 times the text's size in the context's
+ * working buffer (the selection's pass takes 1.3 times), kept until the context goes.  The kernels' grids are laid over those arrays; what lies behind
+ * the range's records returns at once. */
+int sfq_screen_records(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, const sfq_screen* rule,
+                       uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_screen_report* report);
+/* rule != NULL: sfq_decode_blocks_host, sfq_decode_block_range_host and sfq_decode_pair_range_host hand back the kept units of the text
+ * they decoded (the struct is copied; SFQ_E_ARG, and the setting stays, where sfq_screen_check refuses it); NULL: off (default).
+ * Order: the trim, the overlap, the selection, THE SCREEN, the dedup, the merge, the pair split or the window's cut, the pick.  The
+ * screen judges what the selection kept, at its trimmed or cut length; a contaminant never enters the dedup's set.  The CRCs stay
+ * those of the decoded text.  out_cap keeps sizing the DECODED text.  Costs one more device buffer of the text's size, held while the
+ * switch is on, and sfq_screen_records' working memory (above) in the buffer the passes share.  SFQ_E_ARG at the decode call where the
+ * context holds no set, and while the pair split, the merge or a pair window is on and pairs == 0: the mates would fall out of step.
+ * sfq_decode_pair_range_host supplies the range itself, the window's pairs; the rule's own range must then be (0, UINT64_MAX), else
+ * SFQ_E_ARG.  Where a selection ran in front, it has cut the range already.  With nothing kept the _host entries return SFQ_OK and 0
+ * bytes, and the passes behind are skipped.  The device-pointer decode entries are not affected.  Default off: nothing is launched,
+ * allocated or copied that is not today. */
+int sfq_ctx_set_screen(sfq_ctx* ctx, const sfq_screen* rule);
+/* 1: the last decode call screened, *out = what it found; 0: it did not (*out zeroed) */
+int sfq_get_screen(const sfq_ctx* ctx, sfq_screen_report* out);
+
 /* ---- the ".sfq" container (host only) ----------------------------------------------------------
  * Replaces FilerSave + the info page (filer.cpp:217-242, config.cpp:334-347) for hosts that assemble an archive
  * themselves: info_text is the info page ("key=value\n" lines), then n_streams named byte streams (names of at most

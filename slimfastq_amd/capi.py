@@ -46,6 +46,8 @@ EXPORTS = [
     "sfq_merge_check", "sfq_merge_pairs", "sfq_ctx_set_merge", "sfq_get_merge",
     "sfq_dedup_check", "sfq_dedup_records", "sfq_dedup_set_create", "sfq_dedup_set_clear", "sfq_dedup_set_destroy", "sfq_dedup_set_info",
     "sfq_ctx_set_dedup", "sfq_get_dedup",
+    "sfq_screen_check", "sfq_screen_parse", "sfq_fasta_sequences", "sfq_screen_set_create", "sfq_screen_set_add", "sfq_screen_set_clear",
+    "sfq_screen_set_destroy", "sfq_screen_set_info", "sfq_screen_records", "sfq_ctx_set_screen", "sfq_get_screen",
 ]
 
 
@@ -166,6 +168,53 @@ class DedupReport(C.Structure):
 def dedup_check(rule) -> int:
     """sfq_dedup_check (no GPU): 0, or E_ARG for a rule the library refuses."""
     return int(lib().sfq_dedup_check(C.byref(rule)))
+
+
+class Screen(C.Structure):
+    """sfq_screen: the rule of a screen (scr.hip).  Screen() drops every record of the text that shares one k-mer with the context's set."""
+    _fields_ = [("first_record", C.c_uint64), ("n_records", C.c_uint64), ("pairs", C.c_uint32), ("min_hits", C.c_uint32),
+                ("min_pct", C.c_uint32), ("keep_matched", C.c_uint32)]
+
+    def __init__(self, first_record=0, n_records=None, pairs=0, min_hits=1, min_pct=0, keep_matched=False):
+        super().__init__()
+        self.first_record, self.n_records = first_record, SELECT_TO_END if n_records is None else n_records
+        self.pairs, self.min_hits, self.min_pct, self.keep_matched = int(pairs), int(min_hits), int(min_pct), int(keep_matched)
+
+
+class ScreenReport(C.Structure):
+    """sfq_screen_report: what a screen found."""
+    _fields_ = [("n_in_range", C.c_uint64), ("n_units", C.c_uint64), ("n_kept", C.c_uint64), ("n_matched_records", C.c_uint64),
+                ("n_windows", C.c_uint64), ("n_hits", C.c_uint64), ("text_bytes", C.c_uint64), ("kept_bytes", C.c_uint64),
+                ("set_kmers", C.c_uint64)]
+
+
+def screen_check(rule) -> int:
+    """sfq_screen_check (no GPU): 0, or E_ARG for a rule the library refuses."""
+    return int(lib().sfq_screen_check(C.byref(rule)))
+
+
+def screen_parse(spec: str):
+    """sfq_screen_parse (no GPU): (Screen, k) of the terms of the CLI's -G; a ValueError carries the library's message."""
+    rule, k, err = Screen(), C.c_uint32(), C.create_string_buffer(256)
+    if lib().sfq_screen_parse(spec.encode(), C.byref(rule), C.byref(k), err, len(err)):
+        raise ValueError(err.value.decode())
+    return rule, int(k.value)
+
+
+def fasta_sequences(fasta: bytes, cap=None, size_only=False):
+    """sfq_fasta_sequences (no GPU): a FASTA file's bytes as a sequence text; cap: the room given (default: what it needs);
+    size_only: the result's size alone, an int.  An SfqError of code E_OVERFLOW where cap is too small."""
+    n = int(lib().sfq_fasta_sequences(fasta, len(fasta), None, 0))
+    if n < 0:
+        raise SfqError(n, "sfq_fasta_sequences")
+    if size_only:
+        return n
+    room = n if cap is None else int(cap)
+    out = C.create_string_buffer(room + 1)
+    m = int(lib().sfq_fasta_sequences(fasta, len(fasta), C.cast(out, C.c_void_p), room))
+    if m < 0:
+        raise SfqError(m, "sfq_fasta_sequences: the result needs %d bytes" % n)
+    return out.raw[:m]
 
 
 class Trim(C.Structure):
@@ -412,6 +461,18 @@ def lib():
         L.sfq_dedup_set_info.argtypes = [vp, u64p, u64p, u64p, u64p]
         L.sfq_ctx_set_dedup.argtypes = [vp, C.POINTER(Dedup)]
         L.sfq_get_dedup.argtypes = [vp, C.POINTER(DedupReport)]
+        L.sfq_screen_check.argtypes = [C.POINTER(Screen)]
+        L.sfq_screen_parse.argtypes = [C.c_char_p, C.POINTER(Screen), C.POINTER(C.c_uint32), C.c_char_p, u64]
+        L.sfq_fasta_sequences.argtypes = [C.c_char_p, u64, vp, u64]
+        L.sfq_fasta_sequences.restype = C.c_int64
+        L.sfq_screen_set_create.argtypes = [vp, C.c_uint32, u64]
+        L.sfq_screen_set_add.argtypes = [vp, C.c_char_p, u64]
+        L.sfq_screen_set_clear.argtypes = [vp]
+        L.sfq_screen_set_destroy.argtypes = [vp]
+        L.sfq_screen_set_info.argtypes = [vp, C.POINTER(C.c_uint32), u64p, u64p]
+        L.sfq_screen_records.argtypes = [vp, vp, u64, C.POINTER(Screen), vp, u64, u64p, C.POINTER(ScreenReport)]
+        L.sfq_ctx_set_screen.argtypes = [vp, C.POINTER(Screen)]
+        L.sfq_get_screen.argtypes = [vp, C.POINTER(ScreenReport)]
         _lib = L
     return _lib
 
@@ -868,6 +929,60 @@ class Context:
         """The DedupReport of the last decode call; None where it dropped no duplicates."""
         rep = DedupReport()
         rc = lib().sfq_get_dedup(self._h, C.byref(rep))
+        if rc < 0:
+            self._check(rc)
+        return rep if rc == 1 else None
+
+    def screen_records(self, d_text, nbytes, rule, d_out, out_cap):
+        """The units (records, or pairs) of the FASTQ text in the device buffer at d_text that the rule keeps -- those whose base
+        lines share too few k-mers with the context's set, or with rule.keep_matched only the others --, whole and in order, into
+        the one at d_out (sfq_screen_records); returns (bytes written, ScreenReport).  An SfqError of code E_OVERFLOW carries the
+        size needed as .needed."""
+        n, rep = C.c_uint64(), ScreenReport()
+        rc = lib().sfq_screen_records(self._h, C.c_void_p(d_text), int(nbytes), C.byref(rule), C.c_void_p(d_out), int(out_cap),
+                                      C.byref(n), C.byref(rep))
+        try:
+            self._check(rc)
+        except SfqError as e:
+            e.needed = int(n.value)
+            raise
+        return int(n.value), rep
+
+    def screen_set_create(self, k, max_kmers):
+        """The context's one set of reference k-mers, of fixed capacity (sfq_screen_set_create)."""
+        self._check(lib().sfq_screen_set_create(self._h, int(k), int(max_kmers)))
+
+    def screen_set_add(self, seq: bytes):
+        """The k-mers of a sequence text (host bytes; any byte but ACGTacgt separates sequences) into the set; E_NOMEM where they do
+        not fit, and the set is empty then."""
+        self._check(lib().sfq_screen_set_add(self._h, seq, len(seq)))
+
+    def screen_set_clear(self):
+        """Empties the set and keeps its memory."""
+        self._check(lib().sfq_screen_set_clear(self._h))
+
+    def screen_set_destroy(self):
+        """Destroys the set; nothing to do where there is none."""
+        self._check(lib().sfq_screen_set_destroy(self._h))
+
+    def screen_set_info(self):
+        """(k, k-mers, max_kmers) of the set; None where there is none."""
+        k, v = C.c_uint32(), [C.c_uint64() for _ in range(2)]
+        rc = lib().sfq_screen_set_info(self._h, C.byref(k), *[C.byref(x) for x in v])
+        if rc < 0:
+            self._check(rc)
+        return (int(k.value),) + tuple(int(x.value) for x in v) if rc == 1 else None
+
+    def set_screen(self, rule=None):
+        """A Screen: decode_host, decode_range_host and decode_pair_range_host return the units of the text they decoded that the
+        rule keeps, behind the selection and in front of the dedup, the merge, the split and the pick (get_screen() says what was
+        found); None: off."""
+        self._check(lib().sfq_ctx_set_screen(self._h, None if rule is None else C.byref(rule)))
+
+    def get_screen(self):
+        """The ScreenReport of the last decode call; None where it did not screen."""
+        rep = ScreenReport()
+        rc = lib().sfq_get_screen(self._h, C.byref(rep))
         if rc < 0:
             self._check(rc)
         return rep if rc == 1 else None

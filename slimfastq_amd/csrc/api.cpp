@@ -226,6 +226,14 @@ struct sfq_ctx {
     bool dset_on = false; u32 dset_pairs = 0;         // sfq_dedup_set_create: the one set, its slot table, per key its offset and lengths, the key bytes
     DevBuf dset_slots, dset_koff, dset_klen, dset_arena;
     u64 dset_nslots = 0, dset_max_keys = 0, dset_max_bytes = 0, dset_keys = 0, dset_bytes = 0;
+    // screened records (scr.hip): works in pair_work and reports through pair_pin too; nothing of this exists until the switch is on or a set is created
+    bool scr_on = false; sfq_screen scr{};            // sfq_ctx_set_screen
+    DevBuf scr_out;                                   // the kept records of a decoded text (while the switch is on)
+    bool scr_done = false; sfq_screen_report scr_report{};    // the last decode call's
+    bool sset_on = false; u32 sset_k = 0;             // sfq_screen_set_create: the one set of k-mers: its slot table, its counter, the piece of a sequence text on its way up
+    DevBuf sset_slots, sset_info, sset_stage;
+    u64 sset_nslots = 0, sset_max = 0, sset_kmers = 0;
+    u32 scr_lanes = 8;                                // k_scr_count's lanes a record (SFQ_SCR_LANES: profiles/screen_pass.py's layout comparison)
 };
 
 namespace {
@@ -988,9 +996,10 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
         &ctx->oflags, &ctx->okbytes, &ctx->ofpos, &ctx->okoff, &ctx->ofilt, &ctx->orecmap, &ctx->olist, &ctx->line_off_o, &ctx->ono, &ctx->opiece,
         &ctx->otxt[0], &ctx->otxt[1], &ctx->otxt[2], &ctx->osize_all, &ctx->oroff_all, &ctx->oroff_k, &ctx->ocnt,
         &ctx->crc_tab, &ctx->crc_tiles, &ctx->crc_grps, &ctx->crc_bounds, &ctx->crc_out, &ctx->stats_acc, &ctx->qmap_dev,
-        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out, &ctx->pick_out, &ctx->sel_out, &ctx->trim_out, &ctx->ovl_out, &ctx->mrg_out, &ctx->dd_out };
+        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out, &ctx->pick_out, &ctx->sel_out, &ctx->trim_out, &ctx->ovl_out, &ctx->mrg_out, &ctx->dd_out, &ctx->scr_out };
     for (DevBuf* b : all) release(*b);
     (void)sfq_dedup_set_destroy(ctx);
+    (void)sfq_screen_set_destroy(ctx);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->pin2) (void)hipHostFree(ctx->pin2);
     if (ctx->crc_pin) (void)hipHostFree(ctx->crc_pin);
@@ -3001,6 +3010,244 @@ int sfq_get_dedup(const sfq_ctx* ctx, sfq_dedup_report* out) {
     return 1;
 }
 
+// ---- screened records (scr.hip) ----------------------------------------------------------------------------------------------------
+constexpr u64 SCR_PIECE = 4ull << 20;                      // the bytes of a sequence text that go up at a time (slimfastq_amd.h says so)
+int sfq_screen_check(const sfq_screen* g) {
+    if (!g) return SFQ_E_ARG;
+    if (!g->n_records || g->pairs > 2 || (g->pairs && (g->first_record & 1)) || !g->min_hits || g->min_pct > 100) return SFQ_E_ARG;
+    return SFQ_OK;
+}
+// "term,term,...": see slimfastq_amd.h
+int sfq_screen_parse(const char* spec, sfq_screen* rule, uint32_t* k, char* err, uint64_t err_cap) {
+    auto bad = [&](const char* fmt, const std::string& what) {
+        if (err && err_cap) snprintf(err, (size_t)err_cap, fmt, what.c_str());
+        return SFQ_E_ARG;
+    };
+    if (!spec || !rule || !k) return SFQ_E_ARG;
+    memset(rule, 0, sizeof *rule);
+    rule->n_records = ~0ull; rule->min_hits = 1;
+    *k = 27;
+    const std::string all = spec;
+    if (all.empty()) return bad("an empty list of terms%s", "");
+    for (size_t at = 0; at <= all.size(); ) {
+        const size_t comma = std::min(all.find(',', at), all.size());
+        const std::string term = all.substr(at, comma - at);
+        at = comma + 1;
+        const size_t eq = term.find('=');
+        const std::string key = term.substr(0, eq), val = eq == std::string::npos ? "" : term.substr(eq + 1);
+        const bool has = eq != std::string::npos;
+        u64 v = 0;
+        if (key == "ref" && has) { if (val.empty()) return bad("ref=%s: the name of a FASTA file", val); }
+        else if (key == "k" && has) { if (!number(val, 31, &v) || v < 4) return bad("k=%s: a k-mer length of 4 to 31", val); *k = (u32)v; }
+        else if (key == "hits" && has) { if (!number(val, 0xFFFFFFFFull, &v) || !v) return bad("hits=%s: a number of k-mer hits, 1 at least", val); rule->min_hits = (u32)v; }
+        else if (key == "pct" && has) { if (!number(val, 100, &v)) return bad("pct=%s: a percentage of 0 to 100", val); rule->min_pct = (u32)v; }
+        else if (term == "keep") rule->keep_matched = 1;
+        else if (term == "both") rule->pairs = 2;
+        else if (term == "either") rule->pairs = 1;
+        else return bad("%s: no such term (ref= k= hits= pct= keep both either)", term);
+    }
+    return SFQ_OK;
+}
+int64_t sfq_fasta_sequences(const uint8_t* fasta, uint64_t n, uint8_t* out, uint64_t cap) {
+    if (!fasta && n) return SFQ_E_ARG;
+    for (int pass = out ? 0 : 1; pass < 2; pass++) {       // pass 0 sizes the result, so that a cap too small writes nothing
+        const bool write = out && pass == 1;
+        u64 m = 0;
+        for (u64 at = 0; at < n; ) {
+            const u8* nl = (const u8*)memchr(fasta + at, '\n', (size_t)(n - at));
+            const u64 end = nl ? (u64)(nl - fasta) : n;
+            if (fasta[at] == '>') { if (write) out[m] = '\n'; m++; }
+            else {
+                const u64 len = end - at - (nl && end > at && fasta[end - 1] == '\r' ? 1 : 0);
+                if (write) memcpy(out + m, fasta + at, (size_t)len);
+                m += len;
+            }
+            at = end + 1;
+        }
+        if (!out || pass == 1) return (int64_t)m;
+        if (m > cap) return SFQ_E_OVERFLOW;
+    }
+    return 0;
+}
+int sfq_screen_set_create(sfq_ctx* ctx, uint32_t k, uint64_t max_kmers) {
+    if (!ctx) return SFQ_E_ARG;
+    if (ctx->sset_on) return fail(ctx, SFQ_E_ARG, "screened records: the context holds a set already");
+    if (k < 4 || k > 31 || !max_kmers || max_kmers >> 39)
+        return fail(ctx, SFQ_E_ARG, "screened records: a set of %llu k-mers of %u bases (k: 4 to 31, k-mers: 1 to 2^39 - 1)", (unsigned long long)max_kmers, k);
+    HIPC(hipSetDevice(ctx->dev));
+    u64 slots = 2;
+    while (slots < 2 * max_kmers) slots <<= 1;
+    int rc;
+    if ((rc = reserve(ctx, ctx->sset_slots, (size_t)slots * 8)) || (rc = reserve(ctx, ctx->sset_info, sizeof(ScrAddInfo))) ||
+        (rc = reserve(ctx, ctx->sset_stage, (size_t)SCR_PIECE + 64))) {
+        (void)hipGetLastError();
+        release(ctx->sset_slots); release(ctx->sset_info); release(ctx->sset_stage);
+        return rc;
+    }
+    HIPC(hipMemsetAsync(ctx->sset_slots.p, 0, (size_t)slots * 8, ctx->st));
+    HIPC(hipMemsetAsync(ctx->sset_info.p, 0, sizeof(ScrAddInfo), ctx->st));
+    HIPC(hipStreamSynchronize(ctx->st));
+    ctx->sset_on = true; ctx->sset_k = k; ctx->sset_nslots = slots; ctx->sset_max = max_kmers; ctx->sset_kmers = 0;
+    const char* lanes = getenv("SFQ_SCR_LANES");           // (the layout comparison of DESIGN.md 4.21: 1, 4, 8 or 16 lanes a record; results do not depend on it)
+    ctx->scr_lanes = lanes ? (u32)atoi(lanes) : 8;
+    return SFQ_OK;
+}
+int sfq_screen_set_clear(sfq_ctx* ctx) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!ctx->sset_on) return fail(ctx, SFQ_E_ARG, "screened records: the context holds no set");
+    HIPC(hipSetDevice(ctx->dev));
+    HIPC(hipMemsetAsync(ctx->sset_slots.p, 0, (size_t)ctx->sset_nslots * 8, ctx->st));
+    HIPC(hipMemsetAsync(ctx->sset_info.p, 0, sizeof(ScrAddInfo), ctx->st));
+    HIPC(hipStreamSynchronize(ctx->st));
+    ctx->sset_kmers = 0;
+    return SFQ_OK;
+}
+int sfq_screen_set_destroy(sfq_ctx* ctx) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!ctx->sset_on) return SFQ_OK;
+    (void)hipSetDevice(ctx->dev);
+    release(ctx->sset_slots); release(ctx->sset_info); release(ctx->sset_stage);
+    ctx->sset_on = false; ctx->sset_k = 0; ctx->sset_nslots = ctx->sset_max = ctx->sset_kmers = 0;
+    return SFQ_OK;
+}
+int sfq_screen_set_info(const sfq_ctx* ctx, uint32_t* k, uint64_t* kmers, uint64_t* max_kmers) {
+    if (!ctx) return SFQ_E_ARG;
+    const bool on = ctx->sset_on;
+    if (k) *k = on ? ctx->sset_k : 0;
+    if (kmers) *kmers = on ? ctx->sset_kmers : 0;
+    if (max_kmers) *max_kmers = on ? ctx->sset_max : 0;
+    return on ? 1 : 0;
+}
+static ScrSetDev screen_set_dev(const sfq_ctx* ctx) {
+    u32 shift = 64;
+    for (u64 s = ctx->sset_nslots; s > 1; s >>= 1) shift--;
+    return ScrSetDev{ (u64*)ctx->sset_slots.p, ctx->sset_nslots - 1, ctx->sset_k, shift };
+}
+int sfq_screen_set_add(sfq_ctx* ctx, const uint8_t* h_seq, uint64_t n) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!ctx->sset_on) return fail(ctx, SFQ_E_ARG, "screened records: the context holds no set (sfq_screen_set_create)");
+    if (!h_seq || !n) return fail(ctx, SFQ_E_ARG, "screened records: an empty sequence text");
+    HIPC(hipSetDevice(ctx->dev));
+    Settle settle(ctx);
+    const ScrSetDev S = screen_set_dev(ctx);
+    const u64 k = ctx->sset_k;
+    ScrAddInfo got{};
+    // pieces overlap by k - 1 bytes: a piece's windows are those that end in it, and those that began in the piece before are whole
+    for (u64 at = 0; at < n; ) {
+        const u64 from = at >= k - 1 ? at - (k - 1) : 0, to = std::min(n, from + SCR_PIECE);
+        HIPC(hipMemcpyAsync(ctx->sset_stage.p, h_seq + from, (size_t)(to - from), hipMemcpyHostToDevice, ctx->st));
+        launch_screen_add((const u8*)ctx->sset_stage.p, to - from, S, ctx->sset_max, (ScrAddInfo*)ctx->sset_info.p, ctx->st);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(&got, ctx->sset_info.p, sizeof got, hipMemcpyDeviceToHost, ctx->st));
+        HIPC(hipStreamSynchronize(ctx->st));               // (the piece's buffer is free again, and a set that is full already takes no more)
+        if (got.full || got.kmers > ctx->sset_max) {
+            int rc = sfq_screen_set_clear(ctx);
+            if (rc) return rc;
+            settle.ok = true;
+            return fail(ctx, SFQ_E_NOMEM, "screened records: the sequence text holds more k-mers than the set's %llu: the set was cleared", (unsigned long long)ctx->sset_max);
+        }
+        at = to;
+    }
+    ctx->sset_kmers = got.kmers;
+    settle.ok = true;
+    return SFQ_OK;
+}
+// dedup_run's shape: one pass on the context's stream, one synchronise, in pair_run's working buffers and with its sizing; only a
+// text with more records than the arrays were laid out for runs twice.  *rep: what the device found (kept_bytes on SFQ_E_OVERFLOW too).
+static int screen_run(sfq_ctx* ctx, const u8* text, u64 n, const sfq_screen& g, u8* out, u64 out_cap, sfq_screen_report* rep) {
+    int rc;
+    memset(rep, 0, sizeof *rep);
+    if (!ctx->sset_on) return fail(ctx, SFQ_E_ARG, "screened records: the context holds no set (sfq_screen_set_create)");
+    const size_t info_bytes = std::max({ sizeof(PairInfo), sizeof(PickInfo), sizeof(SelInfo), sizeof(DdInfo), sizeof(ScrInfo) });
+    if ((rc = reserve_pinned_buf(ctx, ctx->pair_pin, ctx->pair_pin_cap, info_bytes))) return rc;
+    const ScrJob job{ g.first_record, g.n_records, out_cap, g.pairs, g.min_hits, g.min_pct, g.keep_matched ? 1u : 0u };
+    const ScrSetDev S = screen_set_dev(ctx);
+    ScrInfo got;
+    for (int attempt = 0; ; attempt++) {
+        const u64 cap = std::max<u64>(ctx->pair_cap, n / 64 + 1024);
+        const u64 nlens = std::min(g.n_records, cap);
+        auto up = [](u64 v) { return (v + 15) & ~15ull; };
+        u64 at = up(info_bytes);
+        const u64 sc = at; at += up(qmap_scratch(text, n).bytes);
+        const u64 ls = at; at += up((4 * cap + 1) * 8);
+        const u64 hits = at; at += up(nlens * 4);
+        const u64 wins = at; at += up(nlens * 4);
+        const u64 keep = at; at += up((nlens + 1) * 4);
+        const u64 rlen = at; at += up((nlens + 1) * 4);
+        const u64 pos = at; at += up((nlens + 1) * 8);
+        const u64 lens = at; at += up(nlens * 4);
+        const u64 from = at; at += up(nlens * 8);
+        const u64 dst = at; at += up((nlens + 1) * 8);
+        const u64 tmp = at; at += up((nlens / 1024 + 2) * 8);
+        if ((rc = reserve(ctx, ctx->pair_work, (size_t)at))) return rc;
+        u8* w = (u8*)ctx->pair_work.p;
+        ScrInfo* info = (ScrInfo*)w;
+        HIPC(hipMemsetAsync(info, 0, sizeof(ScrInfo), ctx->st));
+        const PairText t{ text, n, w + sc, nullptr };
+        const ScrArrays A{ (u64*)(w + ls), (u32*)(w + hits), (u32*)(w + wins), (u32*)(w + keep), (u32*)(w + rlen), (u64*)(w + pos), (u32*)(w + lens),
+                           (u64*)(w + from), (u64*)(w + dst), (u64*)(w + tmp), cap, nlens };
+        launch_screen(t, A, job, S, ctx->scr_lanes, out, info, ctx->st);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(ctx->pair_pin, info, sizeof(ScrInfo), hipMemcpyDeviceToHost, ctx->st));
+        HIPC(hipStreamSynchronize(ctx->st));
+        memcpy(&got, ctx->pair_pin, sizeof(ScrInfo));
+        if (got.status != SCR_CAP) break;
+        if (attempt) return fail(ctx, SFQ_E_HIP, "screened records: the records did not fit twice");
+        ctx->pair_cap = got.recs;
+    }
+    rep->text_bytes = n;
+    const unsigned long long r0 = g.first_record, nr = g.n_records, recs = got.recs;
+    switch (got.status) {
+    case SCR_OK: break;
+    case SCR_LINES: return fail(ctx, SFQ_E_FORMAT, "screened records: the text holds %llu lines, not a multiple of four", (unsigned long long)got.lines);
+    case SCR_RANGE:
+        if (g.n_records == ~0ull) return fail(ctx, SFQ_E_ARG, "screened records: record %llu lies behind the text's %llu records", r0, recs);
+        return fail(ctx, SFQ_E_ARG, "screened records: records %llu..+%llu end behind the text's %llu records", r0, nr, recs);
+    case SCR_ODD: return fail(ctx, SFQ_E_FORMAT, "screened records: the range holds an odd number of records, which are no pairs (records %llu.. of %llu)", r0, recs);
+    case SCR_LONG: return fail(ctx, SFQ_E_UNSUPPORTED, "screened records: a record of 4 GiB or more");
+    case SCR_ROOM:
+        rep->kept_bytes = got.copy.nout;
+        return fail(ctx, SFQ_E_OVERFLOW, "screened records: the result needs %llu bytes", (unsigned long long)got.copy.nout);
+    default: return fail(ctx, SFQ_E_HIP, "screened records: status %u", got.status);
+    }
+    rep->n_in_range = got.nr; rep->n_units = got.units; rep->n_kept = got.kept; rep->n_matched_records = got.matched;
+    rep->n_windows = got.windows; rep->n_hits = got.hits; rep->kept_bytes = got.copy.nout; rep->set_kmers = ctx->sset_kmers;
+    return SFQ_OK;
+}
+int sfq_screen_records(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, const sfq_screen* rule,
+                       uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, sfq_screen_report* report) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!d_text || !d_out || !out_bytes || !rule) return fail(ctx, SFQ_E_ARG, "null argument");
+    *out_bytes = 0;
+    if (report) memset(report, 0, sizeof *report);
+    if (!n) return fail(ctx, SFQ_E_ARG, "screened records: an empty text");
+    if (sfq_screen_check(rule)) return fail(ctx, SFQ_E_ARG, "screened records: a rule that sfq_screen_check refuses");
+    HIPC(hipSetDevice(ctx->dev));
+    Settle settle(ctx);
+    sfq_screen_report rep;
+    const int rc = screen_run(ctx, d_text, n, *rule, d_out, out_cap, &rep);
+    if (rc == SFQ_E_OVERFLOW) *out_bytes = rep.kept_bytes;
+    if (rc) return rc;
+    *out_bytes = rep.kept_bytes;
+    if (report) *report = rep;
+    settle.ok = true;
+    return SFQ_OK;
+}
+int sfq_ctx_set_screen(sfq_ctx* ctx, const sfq_screen* rule) {
+    if (!ctx) return SFQ_E_ARG;
+    if (rule && sfq_screen_check(rule)) return fail(ctx, SFQ_E_ARG, "screened records: a rule that sfq_screen_check refuses");
+    ctx->scr_on = rule != nullptr;
+    if (rule) ctx->scr = *rule;
+    else release(ctx->scr_out);
+    return SFQ_OK;
+}
+int sfq_get_screen(const sfq_ctx* ctx, sfq_screen_report* out) {
+    if (!ctx || !out) return SFQ_E_ARG;
+    if (!ctx->scr_done) { memset(out, 0, sizeof *out); return 0; }
+    *out = ctx->scr_report;
+    return 1;
+}
+
 int sfq_get_block_index(sfq_ctx* ctx, sfq_block_info* h_blocks, uint32_t cap) {
     if (!ctx || !h_blocks) return SFQ_E_ARG;
     if (cap < ctx->index.size()) return fail(ctx, SFQ_E_ARG, "index has %zu blocks", ctx->index.size());
@@ -3081,7 +3328,7 @@ static int decode_device(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_inf
     Settle settle(ctx);
     drop_encode_blobs(ctx);                             // whatever an encode left behind is not this archive's
     ctx->crcs.clear(); ctx->text_crc = 0;
-    ctx->pair_split_done = false; ctx->pick_done = 0; ctx->sel_done = false; ctx->trim_done = false; ctx->ovl_done = false; ctx->mrg_done = false; ctx->dd_done = false;
+    ctx->pair_split_done = false; ctx->pick_done = 0; ctx->sel_done = false; ctx->trim_done = false; ctx->ovl_done = false; ctx->mrg_done = false; ctx->dd_done = false; ctx->scr_done = false;
     if (w.ranged && ctx->pair_split_on && !w.pairs)
         return fail(ctx, SFQ_E_UNSUPPORTED, "a window of blocks may start at a second mate and is not split: sfq_ctx_set_pair_split(ctx, 0) comes first");
     const bool check = ex.set;
@@ -3838,6 +4085,14 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
         if (w.pairs && (ctx->mrg.first_record || ctx->mrg.n_records != ~0ull))
             return fail(ctx, SFQ_E_ARG, "merged mates: a window of pairs is the range: the rule's own must be (0, UINT64_MAX)");
     }
+    if (ctx->scr_on) {
+        if (!ctx->sset_on) return fail(ctx, SFQ_E_ARG, "screened records: the context holds no set (sfq_screen_set_create)");
+        if (!ctx->scr.pairs && (ctx->pair_split_on || ctx->mrg_on || w.pairs))
+            return fail(ctx, SFQ_E_ARG, "screened records: while the pair split%s is on units are pairs (pairs must not be 0): the mates would fall out of step",
+                        w.pairs ? " of a window of pairs" : ctx->mrg_on ? " or the merge" : "");
+        if (w.pairs && (ctx->scr.first_record || ctx->scr.n_records != ~0ull))
+            return fail(ctx, SFQ_E_ARG, "screened records: a window of pairs is the range: the rule's own must be (0, UINT64_MAX)");
+    }
     if (ctx->dd_on) {
         if (!ctx->dd.pairs && (ctx->pair_split_on || ctx->mrg_on || w.pairs))
             return fail(ctx, SFQ_E_ARG, "distinct records: while the pair split%s is on duplicates are pairs (pairs must not be 0): the mates would fall out of step",
@@ -3926,13 +4181,27 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
         *out_bytes = ctx->sel_report.kept_bytes;
         if (!*out_bytes) return SFQ_OK;                    // nothing kept: neither the split nor the pick takes an empty text
     }
+    const bool screened = ctx->scr_on;
+    if (screened) {                                        // behind the selection, in front of the dedup: a contaminant never enters the dedup's set
+        if (!*out_bytes) return fail(ctx, SFQ_E_FORMAT, "screened records: an empty text");
+        if ((rc = reserve(ctx, ctx->scr_out, (size_t)*out_bytes + 16))) return rc;
+        Settle settle(ctx);
+        sfq_screen g = ctx->scr;
+        if (w.pairs && !selected) { g.first_record = rec0; g.n_records = 2 * w.n_pairs; }     // the window's pairs, cut here (a selection has cut already)
+        if ((rc = screen_run(ctx, d_text, *out_bytes, g, (u8*)ctx->scr_out.p, *out_bytes, &ctx->scr_report))) return rc;
+        settle.ok = true;
+        ctx->scr_done = true;
+        d_text = (const u8*)ctx->scr_out.p;
+        *out_bytes = ctx->scr_report.kept_bytes;
+        if (!*out_bytes) return SFQ_OK;                    // nothing kept: as behind a selection that keeps nothing
+    }
     const bool distinct = ctx->dd_on;
     if (distinct) {                                        // behind the selection, whose kept records it judges; the merge, the split and the pick see what it kept
         if (!*out_bytes) return fail(ctx, SFQ_E_FORMAT, "distinct records: an empty text");
         if ((rc = reserve(ctx, ctx->dd_out, (size_t)*out_bytes + 16))) return rc;
         Settle settle(ctx);
         sfq_dedup d = ctx->dd;
-        if (w.pairs && !selected) { d.first_record = rec0; d.n_records = 2 * w.n_pairs; }     // the window's pairs, cut here (a selection has cut already)
+        if (w.pairs && !selected && !screened) { d.first_record = rec0; d.n_records = 2 * w.n_pairs; }   // the window's pairs, cut here (a selection or the screen has cut already)
         if ((rc = dedup_run(ctx, d_text, *out_bytes, d, (u8*)ctx->dd_out.p, *out_bytes, &ctx->dd_report))) return rc;
         settle.ok = true;
         ctx->dd_done = true;
@@ -3940,7 +4209,7 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
         *out_bytes = ctx->dd_report.kept_bytes;
         if (!*out_bytes) return SFQ_OK;                    // nothing kept (the set knew every key): as behind a selection that keeps nothing
     }
-    const bool cut = selected || distinct;                 // a pass in front has cut the text to a window's pairs
+    const bool cut = selected || screened || distinct;     // a pass in front has cut the text to a window's pairs
     if (ctx->mrg_on) {
         // behind the selection, which judges the mates: [merged part | rest] from here on, two texts side by side.  The split takes the
         // rest alone, the pick either part; an empty part is skipped by both.

@@ -22,6 +22,9 @@
 //               GPU (consensus bases, combined qualities) and written to PATH, behind -k; the other pairs go where they go without it
 //   -D        : with -d: duplicates dropped on the GPU -- the first record (pair) of every base line (pair of base lines) only, over the
 //               whole archive: one set of keys in device memory lasts the run; behind -k, in front of merge=, -p and -x
+//   -G terms  : with -d: the reads screened against reference sequences on the GPU -- those that share k-mers with the FASTA files
+//               named by ref=PATH dropped (phiX, adapters, rRNA, a host genome), or with the term keep only those kept (baits); one
+//               set of k-mers in device memory lasts the run; behind -k, in front of -D, merge=, -p and -x
 // All model / coder work happens in libslimfastq_amd.so on the GPU; this file parses arguments, reads and
 // writes files and fills the info page.
 #include <sys/stat.h>
@@ -149,6 +152,15 @@ static void usage() {
            "                   of base lines; behind -c, -o and -k, in front of merge=, -p and -x; under -R / -W only the window's records\n"
            "                   count; goes with -R, -p, -W, -x, -k, -c, -o and -K, not with -s or -b; without -q the last line on stderr\n"
            "                   says what was kept\n"
+           "-G terms         : with -d: screen the reads against reference sequences on the GPU before the text comes back: ref=PATH (a\n"
+           "                   FASTA file; the term may be repeated) names the references, whose k-mers of either strand go into one set\n"
+           "                   in device memory that lasts the run; k=N (4 .. 31, default 27) their length; a read is MATCHED when at\n"
+           "                   least hits=N (default 1) of its k-mers, and at least pct=N percent of them (default 0), are in the set.\n"
+           "                   Matched reads are dropped (phiX, adapters, rRNA, a host genome); with the term keep only they are written\n"
+           "                   (baits).  Of an archive written with -p, or with -p / -W, a pair is matched when either mate is; with the\n"
+           "                   term both, when both mates are.  Behind -c, -o and -k, in front of -D, merge=, -p and -x; under -R / -W only\n"
+           "                   the window's records count; goes with -R, -p, -W, -x, -k, -c, -o, -D and -K, not with -s or -b; without\n"
+           "                   -q the last line on stderr says what was matched and kept\n"
            "-M               : with -p on a compress run: compare the names of every pair of mates on the GPU before it is coded (the\n"
            "                   header's first word, without a final /1 or /2); a pair that differs ends the run with its index and both\n"
            "                   names, and no archive is written\n"
@@ -194,6 +206,8 @@ struct Opts {
     bool ovl = false; std::string ovl_spec, ovl_hist; sfq_overlap ovl_rule;        // -o terms, the hist=PATH among them, and the rule the others parse to
     std::string ovl_merge;                                             // ... and the merge=PATH: the pairs are merged, not cut
     bool dedup = false;                                                // -D
+    bool screen = false; std::string screen_spec; sfq_screen screen_rule; uint32_t screen_k = 27;       // -G terms, and the rule and k they parse to
+    std::vector<std::vector<uint8_t>> screen_seqs;                     // ... and the sequence text of every ref=PATH, read before anything is decoded
 };
 // "FIRST:COUNT", both decimal, COUNT > 0
 static bool parse_range(const char* t, uint64_t& first, uint64_t& count) {
@@ -811,6 +825,19 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         if (sfq_dedup_set_create(ctx, std::max<uint64_t>(keys, 1), std::max<uint64_t>(bytes, 1), dd_pairs ? 1 : 0)) croak("-D: %s", sfq_last_error(ctx));
         tick("sfq_dedup_set_create");
     }
+    // -G: one set of k-mers for the whole run: at most one k-mer a byte of the flattened references.  Records are pairs where -D's are.
+    const bool scr_pairs = o.screen && (paired || o.window || merging || a.get_long("usr.pair", 0) == 1);
+    uint64_t scr_units = 0, scr_kept = 0, scr_kmers = 0;
+    if (sfq_ctx_set_screen(ctx, nullptr) || sfq_screen_set_destroy(ctx)) croak("%s", sfq_last_error(ctx));     // (set per segment: the range is the segment's)
+    if (o.screen) {
+        if (o.screen_rule.pairs == 2 && !scr_pairs) croak("-G both: the records of %s stand alone: it was not written from paired files, and neither -p nor -W is given", fil.c_str());
+        uint64_t total = 0;
+        for (const auto& q : o.screen_seqs) total += q.size();
+        if (sfq_screen_set_create(ctx, o.screen_k, std::max<uint64_t>(total, 1))) croak("-G: %s", sfq_last_error(ctx));
+        for (const auto& q : o.screen_seqs) if (sfq_screen_set_add(ctx, q.data(), q.size())) croak("-G: %s", sfq_last_error(ctx));
+        if (sfq_screen_set_info(ctx, nullptr, &scr_kmers, nullptr) != 1) croak("-G: the library holds no set");
+        tick("sfq_screen_set_add");
+    }
     const uint64_t rec_lines = !o.pick ? 4 : o.pick == SFQ_PICK_FASTA ? 2 : 1;      // the lines of a record in what a call hands back
     // walk the segments: each one's blocks, its slice of every stream (streams are segment-major), its prior
     size_t b0 = 0, pri_off = 0, chn_off = 0, rpr_off = 0;
@@ -912,8 +939,8 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             }
             if (merging) {
                 // records outside a merge's range are dropped: under -R the range is the segment's share of -R itself (whole pairs), and
-                // behind -k or -D the text that they kept (either has cut to the range already)
-                if (o.select || o.dedup) { rule.first_record = 0; rule.n_records = ~0ull; }
+                // behind -k, -G or -D the text that they kept (each has cut to the range already)
+                if (o.select || o.dedup || o.screen) { rule.first_record = 0; rule.n_records = ~0ull; }
                 else if (o.range) {
                     uint64_t wrecs = 0;
                     for (uint32_t b = w0; b < w0 + wn; b++) wrecs += sb[b].n_records;
@@ -927,9 +954,10 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             else if (!o.window && !rule.n_records) { if (sfq_ctx_set_overlap(ctx, nullptr)) croak("%s", sfq_last_error(ctx)); }
             else if (sfq_ctx_set_overlap(ctx, &rule)) croak("-o: %s", sfq_last_error(ctx));
         }
-        if (o.dedup) {
+        if (o.screen) {
             // the range: the segment's share of -R, as -k's (behind -k the text that -k kept; -W: the library cuts to the window's pairs itself)
-            sfq_dedup rule{ 0, ~0ull, dd_pairs ? 1u : 0u, 1u };
+            sfq_screen rule = o.screen_rule;
+            rule.pairs = !scr_pairs ? 0u : rule.pairs == 2 ? 2u : 1u;
             const uint64_t text0 = rec0 + sb[w0].first_record;
             if (o.range && !o.select) {
                 uint64_t wrecs = 0;
@@ -937,7 +965,25 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
                 const uint64_t lo = std::max(r_lo, text0), hi = std::min(r_hi, text0 + wrecs);
                 rule.first_record = lo - text0; rule.n_records = hi - lo;
             }
-            if (dd_pairs && !o.window && !o.select) {
+            if (scr_pairs && !o.window && !o.select) {
+                if (text0 & 1) croak("-G: the blocks of %s hold odd numbers of records, so that a decoded text begins at a second mate (record %llu): "
+                                     "pairs are screened in archives written with an even -B", fil.c_str(), (unsigned long long)text0);
+                if (rule.first_record & 1) croak("-G: -R begins at record %llu, a second mate: the reads of an archive written from paired files are screened "
+                                                 "as pairs, and a range begins at a first mate (-W F:N names pairs)", (unsigned long long)(text0 + rule.first_record));
+            }
+            if (sfq_ctx_set_screen(ctx, &rule)) croak("-G: %s", sfq_last_error(ctx));
+        }
+        if (o.dedup) {
+            // the range: the segment's share of -R, as -k's (behind -k or -G the text that they kept; -W: the library cuts to the window's pairs itself)
+            sfq_dedup rule{ 0, ~0ull, dd_pairs ? 1u : 0u, 1u };
+            const uint64_t text0 = rec0 + sb[w0].first_record;
+            if (o.range && !o.select && !o.screen) {
+                uint64_t wrecs = 0;
+                for (uint32_t b = w0; b < w0 + wn; b++) wrecs += sb[b].n_records;
+                const uint64_t lo = std::max(r_lo, text0), hi = std::min(r_hi, text0 + wrecs);
+                rule.first_record = lo - text0; rule.n_records = hi - lo;
+            }
+            if (dd_pairs && !o.window && !o.select && !o.screen) {
                 if (text0 & 1) croak("-D: the blocks of %s hold odd numbers of records, so that a decoded text begins at a second mate (record %llu): "
                                      "duplicates of pairs are dropped from archives written with an even -B", fil.c_str(), (unsigned long long)text0);
                 if (rule.first_record & 1) croak("-D: -R begins at record %llu, a second mate: duplicates of an archive written from paired files are pairs, "
@@ -980,6 +1026,12 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             if (sfq_get_select(ctx, &rep) != 1) croak("-k: the library did not select");
             sel_kept += rep.n_kept; sel_seen += rep.n_in_range; sel_bytes += rep.kept_bytes; sel_text += rep.text_bytes;
         }
+        if (o.screen) {
+            sfq_screen_report rep;
+            const int did = sfq_get_screen(ctx, &rep);                 // (0: a selection in front kept nothing)
+            if (did < 0) croak("-G: the library did not screen");
+            if (did == 1) { scr_units += rep.n_units; scr_kept += rep.n_kept; }
+        }
         if (o.dedup) {
             sfq_dedup_report rep;
             const int did = sfq_get_dedup(ctx, &rep);                  // (0: a selection in front kept nothing)
@@ -1010,7 +1062,7 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
                 for (size_t i = 0; i <= 2 * SFQ_OVERLAP_MAX_LEN; i++) ovl_sum.insert_hist[i] += rep.insert_hist[i];
             }
         }
-        if (o.range && !o.select && !merging && !o.dedup) {                        // the window's first and last block, cut to records: rec_lines lines each
+        if (o.range && !o.select && !merging && !o.dedup && !o.screen) {                        // the window's first and last block, cut to records: rec_lines lines each
             const uint64_t wrec0 = rec0 + (uint64_t)w0 * sb[0].n_records;
             const uint64_t lo = std::max(r_lo, wrec0), hi = std::min(r_hi, wrec0 + res.n_records);
             const size_t from = records_end(dst, (size_t)got, lo - wrec0, rec_lines);
@@ -1066,6 +1118,14 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     if (o.select && !o.quiet)
         fprintf(stderr, "kept %llu of %llu records (%llu of %llu bytes)\n", (unsigned long long)sel_kept, (unsigned long long)sel_seen,
                 (unsigned long long)sel_bytes, (unsigned long long)sel_text);
+    if (o.screen) {
+        if (sfq_ctx_set_screen(ctx, nullptr) || sfq_screen_set_destroy(ctx)) croak("%s", sfq_last_error(ctx));
+        const uint64_t matched = o.screen_rule.keep_matched ? scr_kept : scr_units - scr_kept;
+        if (!o.quiet)
+            fprintf(stderr, "screened %llu %s: %llu matched (%.2f %%), %llu kept (%llu k-mers of %u bases in the set)\n", (unsigned long long)scr_units,
+                    scr_pairs ? "pairs" : "reads", (unsigned long long)matched, scr_units ? 100.0 * (double)matched / (double)scr_units : 0.0,
+                    (unsigned long long)scr_kept, (unsigned long long)scr_kmers, o.screen_k);
+    }
     if (o.dedup) {
         if (sfq_ctx_set_dedup(ctx, nullptr) || sfq_dedup_set_destroy(ctx)) croak("%s", sfq_last_error(ctx));
         if (!o.quiet)
@@ -1079,7 +1139,7 @@ int main(int argc, char** argv) {
     Opts o;
     bool statistics = false;
     if (argc == 1) usage();
-    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKYMD1234u:f:l:B:g:S:T:C:t:R:Q:p:W:x:k:c:o:")) != -1;) {
+    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKYMD1234u:f:l:B:g:S:T:C:t:R:Q:p:W:x:k:c:o:G:")) != -1;) {
         switch (opt) {
         case 'u': g_usr = optarg; break;
         case 'f': fil = optarg; break;
@@ -1122,6 +1182,7 @@ int main(int argc, char** argv) {
         case 'c': o.trim = true; o.trim_spec = optarg; break;
         case 'o': o.ovl = true; o.ovl_spec = optarg; break;
         case 'D': o.dedup = true; break;
+        case 'G': o.screen = true; o.screen_spec = optarg; break;
         case 'C': o.chain_reads = strtol(optarg, 0, 0); break;
         case 't': o.io_threads = std::min(64, std::max(1, atoi(optarg))); break;
         case 'v': printf("Version %s\nInternal format version=%u (block format %u)\n", kUserVersion, kInternalVersion, kBlockVersion); exit(0);
@@ -1231,6 +1292,48 @@ int main(int argc, char** argv) {
         if (g_encode || statistics || g_batch) {
             fprintf(stderr, "slimfastq: -o (overlapping mates) goes with -d: it cuts the records a decode writes%s\n",
                     statistics ? "; -s writes no text" : g_batch ? "; it does not go with -b" : "");
+            return 1;
+        }
+    }
+
+    if (o.screen) {
+        // ref=PATH is the CLI's own term: the library checks the others (and skips these)
+        char err[256] = "";
+        if (sfq_screen_parse(o.screen_spec.c_str(), &o.screen_rule, &o.screen_k, err, sizeof err)) {
+            fprintf(stderr, "slimfastq: -G %s: %s\n", o.screen_spec.c_str(), err[0] ? err : "not a list of terms");
+            return 1;
+        }
+        if (g_encode || statistics || g_batch) {
+            fprintf(stderr, "slimfastq: -G (screened records) goes with -d: it screens the records a decode writes%s\n",
+                    statistics ? "; -s writes no text" : g_batch ? "; it does not go with -b" : "");
+            return 1;
+        }
+        // the references are read and flattened here: an unreadable or empty one ends the run before anything is decoded
+        for (size_t at = 0; at <= o.screen_spec.size(); ) {
+            const size_t comma = std::min(o.screen_spec.find(',', at), o.screen_spec.size());
+            const std::string term = o.screen_spec.substr(at, comma - at);
+            at = comma + 1;
+            if (term.compare(0, 4, "ref=") != 0) continue;
+            const std::string path = term.substr(4);
+            FILE* rf = fopen(path.c_str(), "rb");
+            if (!rf) { fprintf(stderr, "slimfastq: -G: can't read the reference '%s'\n", path.c_str()); return 1; }
+            std::vector<uint8_t> fa;
+            uint8_t buf[1 << 16];
+            for (size_t got; (got = fread(buf, 1, sizeof buf, rf)) > 0; ) fa.insert(fa.end(), buf, buf + got);
+            const bool bad = ferror(rf) != 0;
+            fclose(rf);
+            if (bad) { fprintf(stderr, "slimfastq: -G: can't read the reference '%s'\n", path.c_str()); return 1; }
+            const int64_t need = sfq_fasta_sequences(fa.data(), fa.size(), nullptr, 0);
+            std::vector<uint8_t> seq((size_t)std::max<int64_t>(need, 0));
+            if (need <= 0 || sfq_fasta_sequences(fa.data(), fa.size(), seq.data(), seq.size()) != need ||
+                std::all_of(seq.begin(), seq.end(), [](uint8_t c) { return c == '\n'; })) {    // (nothing but names)
+                fprintf(stderr, "slimfastq: -G: the reference '%s' holds no sequence\n", path.c_str());
+                return 1;
+            }
+            o.screen_seqs.push_back(std::move(seq));
+        }
+        if (o.screen_seqs.empty()) {
+            fprintf(stderr, "slimfastq: -G %s: names no reference (ref=PATH, a FASTA file)\n", o.screen_spec.c_str());
             return 1;
         }
     }

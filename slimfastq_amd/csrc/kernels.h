@@ -497,3 +497,37 @@ struct DdArrays {
 // t.starts is not used; info: zeroed by the caller; S: all zero without job.use_set.  out: job.out_cap bytes, of which info->copy.nout
 // are written, and none unless info->status and info->copy.status stay 0.  The set is written only where info->status stays 0.
 void launch_dedup(const PairText& t, const DdArrays& A, const DdJob& job, const DdSetDev& S, u8* out, DdInfo* info, hipStream_t st);
+
+// Screened records (scr.hip): the units (records; under pairs, pairs) of [r0, r0 + nr) whose line 2 shares enough k-mers with a set of
+// reference k-mers -- or, with keep_matched, only those.  A k-mer's canonical value (the smaller of its 2-bit value and its reverse
+// complement's) is what the set holds, whole: membership is exact.  Like dd.hip the pass finds the lines itself, decides every refusal
+// on the device and copies with pick.hip's copy; the set is only read.
+enum ScrStatus : u32 {
+    SCR_OK = 0,
+    SCR_LINES,              // the text's lines are no multiple of four
+    SCR_RANGE,              // records that end behind the text's last record
+    SCR_CAP,                // more records than the arrays hold: info->recs says how many, nothing else was done
+    SCR_LONG,               // a record of 4 GiB or more
+    SCR_ODD,                // pairs: an odd number of records in the range
+    SCR_ROOM                // the kept records need more than the output holds: info->copy.nout says how much
+};
+constexpr u32 SCR_NOTHING = 0x100;                             // copy.status where no unit is kept (status stays SCR_OK), as SEL_NOTHING
+constexpr u64 SCR_OCC = 1ull << 63;                            // a slot: 0 (empty) or SCR_OCC | the canonical value (k <= 31: below 2^62)
+// the set on the device: slots[smask + 1], a power of two of at least 2 max_kmers; a k-mer's home slot is the top bits of
+// canonical * 0x9E3779B97F4A7C15, that is the product >> shift with shift = 64 - log2(slots); probing is linear from there
+struct ScrSetDev { u64* slots; u64 smask; u32 k, shift; };
+// copy: what k_pick_copy reads, as SelInfo's.  units, kept: the range's and the kept ones; matched, windows, hits: sums over the range's records
+struct ScrInfo { PickInfo copy; u64 lines, recs, r0, nr; u32 status, pad; u64 units, kept, matched, windows, hits; };
+struct ScrJob { u64 r0, nr, out_cap; u32 pairs, min_hits, min_pct, keep_matched; };
+// ls[4 cap + 1] as SelArrays'; hits, wins: H and W per record of the range; keep, rlen, lens, from: nlens entries, pos, dst: nlens + 1,
+// tmp as launch_scan_u32 wants it for nlens; nlens = min(nr, cap)
+struct ScrArrays { u64* ls; u32* hits; u32* wins; u32* keep; u32* rlen; u64* pos; u32* lens; u64* from; u64* dst; u64* tmp; u64 cap, nlens; };
+// what sfq_screen_set_add reads back: kmers = the slots claimed since the set was emptied; full: a probe sequence found no empty slot
+struct ScrAddInfo { u64 kmers; u32 full, pad; };
+// the windows of the sequence text seq[0, n) (device memory) into the set; max_kmers: where the lanes stop inserting (the host refuses
+// the call and empties the set).  info is NOT zeroed by the caller between the adds of one set: kmers runs on.
+void launch_screen_add(const u8* seq, u64 n, const ScrSetDev& S, u64 max_kmers, ScrAddInfo* info, hipStream_t st);
+// lanes: the lanes that share a record in k_scr_count, 8 unless a measurement asks for 1, 4 or 16 (profiles/screen_pass.py).
+// t.starts is not used; info: zeroed by the caller.  out: job.out_cap bytes, of which info->copy.nout are written, and none unless
+// info->status and info->copy.status stay 0.  The set is never written.
+void launch_screen(const PairText& t, const ScrArrays& A, const ScrJob& job, const ScrSetDev& S, u32 lanes, u8* out, ScrInfo* info, hipStream_t st);
