@@ -89,7 +89,7 @@ enum {                     // ---- encode
                            // the phase of model stream m (mst[m] in encode_body): ev_model_begin(ctx, m) / ev_model_end(ctx, m)
     EE_PACK_BEGIN, EE_PACK_END,                    // SFQ_T_PACK
     EE_FRAME_K_BEGIN,      // in front of the framing kernel (its end: EE_FRAME_K_END)
-    EE_TEXT_FORK,          // frozen tables: behind the quality sample's histogram; everything that reads only the text forks here
+    EE_TEXT_FORK,          // frozen tables: directly behind the quality sample's histogram; what reads only the text and would crowd the histogram forks here (the match model's verdict: EE_BLOCKS_READY)
     EE_QLT_CODE_BEGIN, EE_QLT_CODE_END,            // frozen tables: the chain coders alone, for sfq_result.coder_ms
     EE_GEN_CODE_BEGIN, EE_GEN_CODE_END,
     EE_REC_CODE_BEGIN,     // (also: the header prior's passes are through; the quality chains of short records wait for it)
@@ -100,6 +100,10 @@ enum {                     // ---- encode
     EE_FRAME_K_END,
     EE_REC_FREQS_HOME,     // the header prior's frequencies are in page-locked memory (rec_prior_copy_back records, rec_prior_blob_now waits)
     EE_REC_CODE_END,       // behind the headers' token step (chains.hip launch_rec_encode_c records it), or behind the general kernel
+    EE_BLOCKS_READY,       // behind k_block_prepare, in front of the quality sample's histogram: the match model's verdict forks here
+    EE_GEN_SIZES_CLEAR,    // the base chains' size lists are cleared (on the exception pass's stream; the base chains' stream waits)
+    EE_SIZES_SET,          // behind k_block_stream_offsets: the block descriptors are final, their copy home forks here
+    EE_SIDE_END,           // the tail's side work (the "chn.idx" bytes, the descriptors' copy) is through; the context's stream joins it in front of EE_PACK_END
     EE_COUNT
 };
 enum {                     // ---- decode
@@ -143,6 +147,7 @@ struct sfq_ctx {
     DevBuf gm_T, gm_slen, gm_boff, gm_soff, gm_scan, gm_stage, gm_tok, gm_csz, gm_idx;     // bases under the match model (gm.hip): index, stage, tokens
     DevBuf qrows, qdec, qesc, qw, csz, coff, gcnt, grows, glog, gcost, gbins, gfill, hcnt, hfreq, rrows, rdec, rmap, rflags, rtok, excf, cflags;
     DevBuf chn_len, chn_off, chn_out;      // "chn.idx": the size lists as bytes (chains.hip launch_chain_index_bytes)
+    DevBuf side_scan;                      // the scans of the passes that run beside the chains and the packing (first headers, "chn.idx"): scan_tmp is the packing's
     DevBuf pslot, plist;                   // the quality prior's listed rows, back to back (prior.hip launch_prior_list)
     DevBuf segn, segoff, segrec;           // chains that are segments of one record (long reads): segments per record, their scan, a chain's record
     // format 6's oversize records (frame.hip): flags, kept bytes, their scans, the text without them, kept record -> file number, the list;
@@ -816,9 +821,11 @@ int gm_begin(sfq_ctx* ctx, const ChainArgs& ca, u32 nblocks, u64 nrec, u32 max_l
     if ((rc = reserve(ctx, ctx->gm_scan, ((size_t)nrec / 1024 + 4) * 8 + 65536))) return rc;
     if ((rc = reserve(ctx, ctx->gm_stage, (size_t)gp.cap + 64))) return rc;
     if ((rc = reserve(ctx, ctx->gcost, 64))) return rc;
+    // (the stage first: it runs beside the quality sample's histogram, where a fill of the index's 128 MiB crawls -- 0.15 ms against 0.02
+    //  behind it --, and needs nothing of the index)
+    if ((rc = gm_stage_upto(ctx, ca, gp.r2, 0, st))) return rc;
     HIPC(hipMemsetAsync(ctx->gm_T.p, 0xFF, (size_t)8 << gp.tb, st));
     HIPC(hipMemsetAsync(ctx->gcost.p, 0, 64, st));
-    if ((rc = gm_stage_upto(ctx, ca, gp.r2, 0, st))) return rc;
     gp.cg = ca;
     gp.cg.st_buf = (const u8*)ctx->gm_stage.p; gp.cg.st_bytes = gp.cap; gp.cg.st_off = (const u64*)ctx->gm_soff.p; gp.cg.st_len = (const u32*)ctx->gm_slen.p;
     auto recs = [&](u32 b0, u32 b1) { return (u64)(b1 - b0) * br; };
@@ -992,7 +999,7 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
         &ctx->slen, &ctx->qlen, &ctx->pfg, &ctx->pfq, &ctx->soff, &ctx->qoff, &ctx->seq_stage, &ctx->qual_stage,
         &ctx->hdr_stage, &ctx->hlen, &ctx->hoff, &ctx->hso, &ctx->hsc, &ctx->rsize, &ctx->roff, &ctx->d_first,
         &ctx->hist, &ctx->rows66, &ctx->prior_w, &ctx->prior_wovf, &ctx->prior_ls, &ctx->prior_lh, &ctx->tickets,
-        &ctx->hcnt, &ctx->hfreq, &ctx->rrows, &ctx->rdec, &ctx->rmap, &ctx->rflags, &ctx->rtok, &ctx->ptmp, &ctx->qrows, &ctx->qdec, &ctx->qesc, &ctx->qw, &ctx->csz, &ctx->coff, &ctx->gcnt, &ctx->grows, &ctx->glog, &ctx->gcost, &ctx->gbins, &ctx->gfill, &ctx->gm_T, &ctx->gm_slen, &ctx->gm_boff, &ctx->gm_soff, &ctx->gm_scan, &ctx->gm_stage, &ctx->gm_tok, &ctx->gm_csz, &ctx->gm_idx, &ctx->excf, &ctx->cflags, &ctx->segn, &ctx->segoff, &ctx->segrec, &ctx->pslot, &ctx->plist, &ctx->chn_len, &ctx->chn_off, &ctx->chn_out,
+        &ctx->hcnt, &ctx->hfreq, &ctx->rrows, &ctx->rdec, &ctx->rmap, &ctx->rflags, &ctx->rtok, &ctx->ptmp, &ctx->qrows, &ctx->qdec, &ctx->qesc, &ctx->qw, &ctx->csz, &ctx->coff, &ctx->gcnt, &ctx->grows, &ctx->glog, &ctx->gcost, &ctx->gbins, &ctx->gfill, &ctx->gm_T, &ctx->gm_slen, &ctx->gm_boff, &ctx->gm_soff, &ctx->gm_scan, &ctx->gm_stage, &ctx->gm_tok, &ctx->gm_csz, &ctx->gm_idx, &ctx->excf, &ctx->cflags, &ctx->segn, &ctx->segoff, &ctx->segrec, &ctx->pslot, &ctx->plist, &ctx->chn_len, &ctx->chn_off, &ctx->chn_out, &ctx->side_scan,
         &ctx->oflags, &ctx->okbytes, &ctx->ofpos, &ctx->okoff, &ctx->ofilt, &ctx->orecmap, &ctx->olist, &ctx->line_off_o, &ctx->ono, &ctx->opiece,
         &ctx->otxt[0], &ctx->otxt[1], &ctx->otxt[2], &ctx->osize_all, &ctx->oroff_all, &ctx->oroff_k, &ctx->ocnt,
         &ctx->crc_tab, &ctx->crc_tiles, &ctx->crc_grps, &ctx->crc_bounds, &ctx->crc_out, &ctx->stats_acc, &ctx->qmap_dev,
@@ -1248,6 +1255,7 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     if (g_bits < 2 || g_bits > 26 ) return fail(ctx, SFQ_E_ARG, "gen_bits %d out of range", g_bits);
     if ((rc = reserve(ctx, ctx->blocks, (size_t)nblocks * sizeof(BlockDesc)))) return rc;
     launch_block_prepare(d_fastq, (const u64*)ctx->line_off.p, nrec, block_reads, (BlockDesc*)ctx->blocks.p, nblocks, nbytes, p.level, g_bits, st);
+    HIPC(hipEventRecord(ctx->ev[EE_BLOCKS_READY], st));
     // checksums: the CRC of every block's text (format 6: the whole file, oversize records included) on a stream of its own, from
     // the line index; taken in at the end of the call
     const bool crc_pass = ctx->crc_on && !priors_only;
@@ -1304,7 +1312,8 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     const u32 nblocks_r = (nblocks + KR - 1) / KR * KR;
     ModelArgs a;
     u32* tickets = nullptr;
-    auto setup_tables = [&]() -> int {
+    // (tst: the stream that clears the ticket counters -- their first reader's)
+    auto setup_tables = [&](hipStream_t tst) -> int {
         int rc;
         if ((rc = ensure_tables(ctx, nblocks_r, q_rows, (u32)g_bits, frozen ? (models & ~(SFQ_M_QLT | SFQ_M_GEN)) : models, &slots))) return rc;
         if (p.kernel == 0) {
@@ -1317,7 +1326,7 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
         a.rec_map = n_over ? (const u32*)ctx->orecmap.p : nullptr;
         // Default kernels are persistent: one workgroup per pair of table slots, blocks handed out through ticket counters.
         if ((rc = reserve(ctx, ctx->tickets, 64))) return rc;
-        HIPC(hipMemsetAsync(ctx->tickets.p, 0, 64, st));
+        HIPC(hipMemsetAsync(ctx->tickets.p, 0, 64, tst));
         tickets = (u32*)ctx->tickets.p;
         return SFQ_OK;
     };
@@ -1344,7 +1353,8 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
         prior_step = (u32)std::min<u64>((u64)prior_step * std::max<u32>(1u, ctx->sample_scale), 0x7FFFFFFFull);
     // The histogram of the quality sample goes FIRST and alone: its workgroups take 64 KiB of LDS each, and beside the other models'
     // early passes -- thousands of small workgroups that keep every CU's LDS in use -- they wait for room: 0.5 ms alone, 6.7 ms
-    // beside them, and the quality chains wait for it.  Everything else forks behind it (EE_TEXT_FORK below).
+    // beside them, and the quality chains wait for it.  What would crowd it forks behind it (EE_TEXT_FORK below); the match model's
+    // verdict -- a handful of small kernels with next to no LDS -- forks in front of it (EE_BLOCKS_READY) and runs beside it.
     bool hist_launched = false;
     if (frozen && !given && !counted && prior_step && (models & SFQ_M_QLT)) {
         if ((rc = ensure_prior_buffers(ctx, q_rows))) return rc;
@@ -1372,6 +1382,25 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     const bool gm = frozen && !exc_classic;            // bases: the match model (gm.hip); sfq_params.kernel = 2 keeps round 4's generation tables
     u32 seg_len = 0;                                   // chains that are segments of one record (chains.hip "segments")
     std::vector<u32> seg_blk;                          // ... and how many each block has ("chn.idx")
+    bool gm_split = false;                             // the base chains have a size list of their own (gm_csz)
+    // the blocks' first headers as a blob: lengths, their scan (tmp: the scan's scratch), the gather
+    const u64 blob_cap = std::min<u64>(nbytes, (u64)nblocks * SFQ_MAX_ID_LLEN);
+    const u64 blob_guess = std::min<u64>(blob_cap, (u64)nblocks * 256);      // what of it goes home before its size is known
+    auto first_hdrs_queue = [&](hipStream_t fst, u64* tmp) {
+        launch_first_hdr_lens((const BlockDesc*)ctx->blocks.p, nblocks, (u32*)ctx->lens.p, fst);
+        launch_scan_u32((const u32*)ctx->lens.p, (u64*)ctx->blob_off.p, nblocks, tmp, fst);
+        launch_gather_first_hdrs((const BlockDesc*)ctx->blocks.p, nblocks, d_fastq, (const u64*)ctx->blob_off.p, (u8*)ctx->blob.p, blob_cap, fst);
+    };
+    // what comes back to the host at the end lands in page-locked memory: [totals][block descriptors][blob offsets][the blob's guessed
+    // part (match model only: elsewhere it goes straight to ctx->first_hdrs)][chain sizes]
+    const size_t p2_hb = 128, p2_off = p2_hb + (((size_t)nblocks * sizeof(BlockDesc) + 63) & ~(size_t)63);
+    const size_t p2_blob = p2_off + ((((size_t)nblocks + 1) * 8 + 63) & ~(size_t)63);
+    size_t p2_csz = p2_blob, p2_sizes = 0;             // where the chain sizes land, and for how many of them there is room
+    auto pin2_reserve = [&](size_t n_sizes, bool with_blob) -> int {
+        p2_csz = p2_blob + (with_blob ? (((size_t)blob_guess + 63) & ~(size_t)63) : 0);
+        p2_sizes = n_sizes;
+        return reserve_pinned_buf(ctx, ctx->pin2, ctx->pin2_cap, p2_csz + n_sizes * 4 + 64);
+    };
     if (frozen) {
         u32 cr = p.chain_reads ? p.chain_reads : (u32)default_chain_reads(nrec, nbytes);
         if (p.chain_reads & SFQ_CHAIN_SEGMENT_FLAG) { seg_len = p.chain_reads & ~SFQ_CHAIN_SEGMENT_FLAG; cr = 1; if (!seg_len) return fail(ctx, SFQ_E_ARG, "SFQ_CHAIN_SEGMENT(0)"); }
@@ -1433,8 +1462,10 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
             ca.rgeo.cpb = (block_reads + rcr - 1) / rcr;
             nsub = ca.rgeo.nchains = (u32)((u64)(nblocks - 1) * ca.rgeo.cpb + (last_nrec + rcr - 1) / rcr);
         }
+        // the chains' size lists start from zero.  Under the match model every list is cleared on a stream that reaches its writers
+        // (below, at the fork), not here: the context's stream carries nothing between the histogram and EE_TEXT_FORK
         if ((rc = reserve(ctx, ctx->csz, ((size_t)nchains * 2 + (size_t)nsub * 2) * 4))) return rc;
-        HIPC(hipMemsetAsync(ctx->csz.p, 0, ((size_t)nchains * 2 + (size_t)nsub * 2) * 4, st));
+        if (!gm) HIPC(hipMemsetAsync(ctx->csz.p, 0, ((size_t)nchains * 2 + (size_t)nsub * 2) * 4, st));
         // The base chains of a call that takes the match model (gm.hip) are SHORTER than the quality chains.  A decoder walks the generations one after the other and each takes as long as ONE lane needs for
         // its chain -- 6.6 ms at 49 records whatever the generation's size, seven times over; at 12 records the same call decodes in
         // 30 ms instead of 60 and is 0.13 % larger (bench.py --kind 3 --chain-reads 12 / 49, profiles/r05g).  Known only with the
@@ -1454,25 +1485,61 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
             if (ngc > 0x7FFFFFFFull || ggeo.chain_reads >= ca.geo.chain_reads) ggeo = ca.geo;
             else {
                 ggeo.nchains = (u32)ngc;
-                if ((rc = reserve(ctx, ctx->gm_csz, (size_t)ggeo.nchains * 4))) return rc;
-                HIPC(hipMemsetAsync(ctx->gm_csz.p, 0, (size_t)ggeo.nchains * 4, st));
+                if ((rc = reserve(ctx, ctx->gm_csz, (size_t)ggeo.nchains * 4))) return rc;       // (cleared below, with the base chains' other list)
+                gm_split = true;
             }
         }
         if ((rc = reserve_pinned(ctx, PIN_BYTES + (size_t)q_rows * 66 * 4))) return rc;
-        if ((rc = setup_tables())) return rc;
+        if (gm && !priors_only) {
+            // the passes that run beside the chains and the packing (first headers here; the "chn.idx" bytes and the copies home at the
+            // tail) get their buffers now, sized for the larger of the two numbers of base chains the verdict can leave
+            const size_t sizes_most = (size_t)nchains + std::max(nchains, ggeo.nchains) + (size_t)nsub * 2;
+            if ((rc = reserve(ctx, ctx->lens, (size_t)nblocks * 4))) return rc;
+            if ((rc = reserve(ctx, ctx->blob_off, ((size_t)nblocks + 1) * 8))) return rc;
+            if ((rc = reserve(ctx, ctx->blob, blob_cap))) return rc;
+            if ((rc = reserve(ctx, ctx->side_scan, (sizes_most / 1024 + 4) * 8 + 65536))) return rc;
+            if ((rc = pin2_reserve(sizes_most, true))) return rc;
+        }
+        // (the ticket counters are cleared on the stream of their one reader here, the exception pass)
+        if ((rc = setup_tables(gm ? mst[2] : st))) return rc;
         // the pass over the N / quality-0 / case exceptions looks only at the records the framing has marked (frame.hip
         // k_write_newlines: the text is in registers there anyway) and runs beside the counting passes, while the chip is
         // mostly idle.  (Round 2 had the quality and base chains mark them -- the pass then ran BEHIND the chains, 2.5 ms at
         // the call's tail; a marking pass of its own over the text was measured too: it costs more than those 2.5 ms.)
+        //
+        // EE_TEXT_FORK follows the histogram directly.  What forks there must not crowd the histogram's 64-KiB workgroups: the header
+        // sample (41 KiB of LDS a workgroup), the generation tables' counting passes (LDS bins).  The match model's verdict -- stage,
+        // index, price: 0 - 1 KiB of LDS a workgroup, and all they read is the text, the line index and the block descriptors -- does
+        // not wait for it: its stream forks at EE_BLOCKS_READY, in FRONT of the histogram, and runs beside it.
         HIPC(hipEventRecord(ctx->ev[EE_TEXT_FORK], st));
+        if (gm) HIPC(hipMemsetAsync(ctx->csz.p, 0, (size_t)nchains * 4, st));                       // the quality chains' sizes
         if (!priors_only) {
-            for (int m = 1; m < 4; m++) { HIPC(hipStreamWaitEvent(mst[m], ctx->ev[EE_TEXT_FORK], 0)); HIPC(hipEventRecord(ev_model_begin(ctx, m), mst[m])); }
+            for (int m = 1; m < 4; m++) {
+                HIPC(hipStreamWaitEvent(mst[m], ctx->ev[gm && m == 3 ? EE_BLOCKS_READY : EE_TEXT_FORK], 0));
+                HIPC(hipEventRecord(ev_model_begin(ctx, m), mst[m]));
+            }
             a.batch0 = 0; a.nbatch = std::min(slots, nblocks_r);
             ca.m = a;
+            // (the verdict's passes first: the host decision the chains wait for longest.  The base chains' size lists -- both -- are
+            //  cleared beside them on the exception pass's stream, idle until the chains: in front of the verdict's passes they were 0.1 ms
+            //  of its path; the base chains' stream waits for them behind the verdict's copy home)
+            if (gm && (models & SFQ_M_GEN)) { if ((rc = gm_begin(ctx, ca, nblocks, nrec, max_line, mst[3], gmplan))) return rc; }
+            if (gm) {
+                HIPC(hipMemsetAsync((u32*)ctx->csz.p + nchains, 0, (size_t)nchains * 4, mst[2]));
+                if (gm_split) HIPC(hipMemsetAsync(ctx->gm_csz.p, 0, (size_t)ggeo.nchains * 4, mst[2]));
+                HIPC(hipEventRecord(ctx->ev[EE_GEN_SIZES_CLEAR], mst[2]));
+                HIPC(hipStreamWaitEvent(mst[3], ctx->ev[EE_GEN_SIZES_CLEAR], 0));
+                HIPC(hipMemsetAsync((u32*)ctx->csz.p + 2 * (size_t)nchains, 0, (size_t)nsub * 2 * 4, mst[1]));     // the header chains', in front of its writers
+            }
             if (models & SFQ_M_REC) { if ((rc = rec_prior_begin(ctx, a, nrec, given, counted, mst[1], max_hdr))) return rc; }
-            if (models & SFQ_M_GEN) {
-                if (gm) { if ((rc = gm_begin(ctx, ca, nblocks, nrec, max_line, mst[3], gmplan))) return rc; }
-                else if ((rc = gen_tables_begin(ctx, ca, nblocks, (u32)g_bits, max_line, mst[3], gplan))) return rc;
+            if (!gm && (models & SFQ_M_GEN)) { if ((rc = gen_tables_begin(ctx, ca, nblocks, (u32)g_bits, max_line, mst[3], gplan))) return rc; }
+            // the blocks' first headers, gathered and on their way home beside the head: all they need is the text and k_block_prepare's
+            // descriptors (frame.hip: nothing behind it writes first_hdr_off / first_hdr_len).  On the exception pass's stream, in front
+            // of that pass, so the context's stream has them joined with it well before the packing.
+            if (gm) {
+                first_hdrs_queue(mst[2], (u64*)ctx->side_scan.p);
+                HIPC(hipMemcpyAsync((u8*)ctx->pin2 + p2_off, ctx->blob_off.p, ((size_t)nblocks + 1) * 8, hipMemcpyDeviceToHost, mst[2]));
+                if (blob_guess) HIPC(hipMemcpyAsync((u8*)ctx->pin2 + p2_blob, ctx->blob.p, (size_t)blob_guess, hipMemcpyDeviceToHost, mst[2]));
             }
             // (the pass over the exceptions and the framing exceptions are queued behind the chains' launches below: beside the two
             //  counting passes the host waits for they made those take 1.7-1.9 ms instead of 0.3)
@@ -1552,7 +1619,7 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
             HIPC(hipEventRecord(ctx->ev[EE_HEAD_END], st));
         }
     }
-    if (!frozen) { if ((rc = setup_tables())) return rc; }
+    if (!frozen) { if ((rc = setup_tables(st))) return rc; }
     if (priors_only) {
         if (ctx->prior_on && !given) {                      // (packed while the header sample is still being counted)
             if ((rc = qlt_prior_blob_now(ctx, h_rows66, q_rows, st))) return rc;
@@ -1683,6 +1750,13 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     HIPC(hipEventRecord(ctx->ev[EE_PACK_BEGIN], st));
 
     // ---- pack ----------------------------------------------------------------------------------
+    // On the context's stream behind the chains: the blocks' sizes, the offsets, the totals' copy, the gate and the packing kernels.
+    // What the host wants besides and the packing does not -- the "chn.idx" bytes (they need the chains' sizes, not their places)
+    // and the copies home -- runs beside the packing where the match model's schedule is taken (side): on the exception pass's
+    // stream, which forks here and is joined in front of EE_PACK_END.  The first headers came home with the head.
+    const bool side = gm;
+    hipStream_t sst = side ? mst[2] : st;
+    if (side) HIPC(hipStreamWaitEvent(sst, ctx->ev[EE_PACK_BEGIN], 0));
     if ((rc = reserve(ctx, ctx->blk_stream_off, (size_t)nblocks * SFQ_NSTREAMS * 8))) return rc;
     if ((rc = reserve(ctx, ctx->stream_total, 2 * SFQ_NSTREAMS * 8 + 64))) return rc;                  // totals, bases, the packing's gate
     u32 chain_streams = 0;                             // streams packed chain by chain
@@ -1696,17 +1770,15 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
         }
     }
     launch_block_stream_offsets((BlockDesc*)ctx->blocks.p, nblocks, (u64*)ctx->blk_stream_off.p, (u64*)ctx->stream_total.p, st);
-    // first headers -> blob
-    if ((rc = reserve(ctx, ctx->lens, (size_t)nblocks * 4))) return rc;
-    if ((rc = reserve(ctx, ctx->blob_off, ((size_t)nblocks + 1) * 8))) return rc;
-    const u64 blob_cap = std::min<u64>(nbytes, (u64)nblocks * SFQ_MAX_ID_LLEN);
-    if ((rc = reserve(ctx, ctx->blob, blob_cap))) return rc;
-    launch_first_hdr_lens((const BlockDesc*)ctx->blocks.p, nblocks, (u32*)ctx->lens.p, st);
-    launch_scan_u32((const u32*)ctx->lens.p, (u64*)ctx->blob_off.p, nblocks, (u64*)ctx->scan_tmp.p, st);
-    launch_gather_first_hdrs((const BlockDesc*)ctx->blocks.p, nblocks, d_fastq, (const u64*)ctx->blob_off.p, (u8*)ctx->blob.p, blob_cap, st);
-    // what comes back to the host at the end lands in page-locked memory: [totals][block descriptors][blob offsets][chain sizes]
-    const size_t p2_hb = 128, p2_off = p2_hb + (((size_t)nblocks * sizeof(BlockDesc) + 63) & ~(size_t)63);
-    const size_t p2_csz = p2_off + ((((size_t)nblocks + 1) * 8 + 63) & ~(size_t)63);
+    // (the descriptors are final here: the packing kernels only read them)
+    if (side) HIPC(hipEventRecord(ctx->ev[EE_SIZES_SET], st));
+    else {
+        // first headers -> blob
+        if ((rc = reserve(ctx, ctx->lens, (size_t)nblocks * 4))) return rc;
+        if ((rc = reserve(ctx, ctx->blob_off, ((size_t)nblocks + 1) * 8))) return rc;
+        if ((rc = reserve(ctx, ctx->blob, blob_cap))) return rc;
+        first_hdrs_queue(st, (u64*)ctx->scan_tmp.p);
+    }
     const u32 ngc = frozen ? ggeo.nchains : 0;             // base chains (the quality chains' number unless the match model cut its own)
     const bool gsplit = frozen && ngc != nchains;
     const size_t n_sizes = (size_t)nchains + ngc + (size_t)nsub * 2;
@@ -1714,13 +1786,14 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     if (gsplit) {
         if ((rc = reserve(ctx, ctx->gm_idx, n_sizes * 4 + 64))) return rc;
         u32* di = (u32*)ctx->gm_idx.p;
-        HIPC(hipMemcpyAsync(di, ctx->csz.p, (size_t)nchains * 4, hipMemcpyDeviceToDevice, st));
-        HIPC(hipMemcpyAsync(di + nchains, ctx->gm_csz.p, (size_t)ngc * 4, hipMemcpyDeviceToDevice, st));
-        HIPC(hipMemcpyAsync(di + nchains + ngc, (const u32*)ctx->csz.p + 2 * (size_t)nchains, (size_t)nsub * 2 * 4, hipMemcpyDeviceToDevice, st));
+        HIPC(hipMemcpyAsync(di, ctx->csz.p, (size_t)nchains * 4, hipMemcpyDeviceToDevice, sst));
+        HIPC(hipMemcpyAsync(di + nchains, ctx->gm_csz.p, (size_t)ngc * 4, hipMemcpyDeviceToDevice, sst));
+        HIPC(hipMemcpyAsync(di + nchains + ngc, (const u32*)ctx->csz.p + 2 * (size_t)nchains, (size_t)nsub * 2 * 4, hipMemcpyDeviceToDevice, sst));
         d_sizes = di;
     }
-    const size_t p2_end = p2_csz + n_sizes * 4 + 64;
-    if ((rc = reserve_pinned_buf(ctx, ctx->pin2, ctx->pin2_cap, p2_end))) return rc;
+    // (side: the page-locked buffer stands since the head -- the first headers are in it)
+    if (!side) { if ((rc = pin2_reserve(n_sizes, false))) return rc; }
+    else if (n_sizes > p2_sizes) return fail(ctx, SFQ_E_HIP, "chain sizes: %zu where the head made room for %zu", n_sizes, p2_sizes);
     u64* totals = (u64*)ctx->pin2;
     HIPC(hipMemcpyAsync(totals, ctx->stream_total.p, SFQ_NSTREAMS * 8, hipMemcpyDeviceToHost, st));
     // host work that needs nothing of what is still running -- "qlt.pri", 0.7 ms -- is done while the chains are coded, and behind
@@ -1742,10 +1815,9 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     const size_t chn_eager = std::min<size_t>((size_t)chn_n * 5, n_sizes * 4 + 64 - 16);
     // The packing follows the sizes on the device: k_stream_gate places the streams and holds the packing back where a block has
     // failed or the caller's buffer is too small (the host reports that below, from the same numbers) -- no host round trip between
-    // the chains and the packing.  Everything the host wants comes back behind it in one go; the first headers too, as far as a
-    // guess at their size reaches.
+    // the chains and the packing.  Everything the host wants comes back behind it in one go (side: beside it); the first headers
+    // too, as far as a guess at their size reaches.
     u32* d_gate = (u32*)((u64*)ctx->stream_total.p + 2 * SFQ_NSTREAMS);
-    const u64 blob_guess = std::min<u64>(blob_cap, (u64)nblocks * 256);
     launch_stream_gate((const BlockDesc*)ctx->blocks.p, nblocks, (const u64*)ctx->stream_total.p, out_cap, (u64*)ctx->stream_total.p + SFQ_NSTREAMS, d_gate, st);
     launch_compact((const BlockDesc*)ctx->blocks.p, nblocks, (const u8*)ctx->arena.p, (const u64*)ctx->blk_stream_off.p,
                    (const u64*)ctx->stream_total.p + SFQ_NSTREAMS, d_out, chain_streams, st, d_gate);
@@ -1758,25 +1830,37 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
             launch_compact_chains(ca, ca.rgeo, SFQ_S_REC, 3, 2, (const u32*)ctx->csz.p + 2 * (size_t)nchains, (const u64*)ctx->blk_stream_off.p, (const u64*)ctx->stream_total.p + SFQ_NSTREAMS, d_out, st, d_gate);
         // "chn.idx": the size lists come back as the bytes the blob holds (chains.hip launch_chain_index_bytes: made from half a
         // million sizes on the host they were 1.0 ms of every call's tail), as far as a guess at their number reaches
+        // (side: with a scan scratch of their own -- scan_tmp is the packing's and the segment scans')
         {
             const u32 b1 = nchains, b2 = nchains + ngc, b3 = rec_chains ? nchains + ngc + nsub : chn_n;
             if ((rc = reserve(ctx, ctx->chn_len, (size_t)chn_n * 4 + 16))) return rc;
             if ((rc = reserve(ctx, ctx->chn_off, ((size_t)chn_n + 4) * 8))) return rc;
             if ((rc = reserve(ctx, ctx->chn_out, (size_t)chn_n * 5 + 64))) return rc;
-            if ((rc = reserve(ctx, ctx->scan_tmp, ((size_t)chn_n / 1024 + 4) * 8 + 65536))) return rc;
+            DevBuf& chn_scan = side ? ctx->side_scan : ctx->scan_tmp;
+            if ((rc = reserve(ctx, chn_scan, ((size_t)chn_n / 1024 + 4) * 8 + 65536))) return rc;
             u64* d_info = (u64*)ctx->chn_off.p + chn_n + 1;
-            launch_chain_index_bytes(d_sizes, chn_n, b1, b2 > chn_n ? chn_n : b2, b3, (u32*)ctx->chn_len.p, (u64*)ctx->chn_off.p, (u64*)ctx->scan_tmp.p,
-                                     (u8*)ctx->chn_out.p, d_info, st);
-            HIPC(hipMemcpyAsync(h_csz, d_info, 16, hipMemcpyDeviceToHost, st));
-            if (chn_eager) HIPC(hipMemcpyAsync((u8*)h_csz + 16, ctx->chn_out.p, chn_eager, hipMemcpyDeviceToHost, st));
+            launch_chain_index_bytes(d_sizes, chn_n, b1, b2 > chn_n ? chn_n : b2, b3, (u32*)ctx->chn_len.p, (u64*)ctx->chn_off.p, (u64*)chn_scan.p,
+                                     (u8*)ctx->chn_out.p, d_info, sst);
+            HIPC(hipMemcpyAsync(h_csz, d_info, 16, hipMemcpyDeviceToHost, sst));
+            if (chn_eager) HIPC(hipMemcpyAsync((u8*)h_csz + 16, ctx->chn_out.p, chn_eager, hipMemcpyDeviceToHost, sst));
         }
     }
+    if (side) {
+        // the block descriptors' copy home, behind the sizes; then the context's stream joins: EE_PACK_END stands behind the last of
+        // what the host waits for
+        HIPC(hipStreamWaitEvent(sst, ctx->ev[EE_SIZES_SET], 0));
+        HIPC(hipMemcpyAsync(hb, ctx->blocks.p, (size_t)nblocks * sizeof(BlockDesc), hipMemcpyDeviceToHost, sst));
+        HIPC(hipEventRecord(ctx->ev[EE_SIDE_END], sst));
+        HIPC(hipStreamWaitEvent(st, ctx->ev[EE_SIDE_END], 0));
+    }
     HIPC(hipEventRecord(ctx->ev[EE_PACK_END], st));
-    if ((rc = pack_prior_now())) return rc;               // (before the copy into pageable memory below: that one returns when the stream has reached it)
-    ctx->first_hdrs.resize((size_t)blob_guess);
-    if (blob_guess) HIPC(hipMemcpyAsync(ctx->first_hdrs.data(), ctx->blob.p, (size_t)blob_guess, hipMemcpyDeviceToHost, st));
-    HIPC(hipMemcpyAsync(hb, ctx->blocks.p, (size_t)nblocks * sizeof(BlockDesc), hipMemcpyDeviceToHost, st));
-    HIPC(hipMemcpyAsync(hboff, ctx->blob_off.p, ((size_t)nblocks + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (!side) {
+        if ((rc = pack_prior_now())) return rc;               // (before the copy into pageable memory below: that one returns when the stream has reached it)
+        ctx->first_hdrs.resize((size_t)blob_guess);
+        if (blob_guess) HIPC(hipMemcpyAsync(ctx->first_hdrs.data(), ctx->blob.p, (size_t)blob_guess, hipMemcpyDeviceToHost, st));
+        HIPC(hipMemcpyAsync(hb, ctx->blocks.p, (size_t)nblocks * sizeof(BlockDesc), hipMemcpyDeviceToHost, st));
+        HIPC(hipMemcpyAsync(hboff, ctx->blob_off.p, ((size_t)nblocks + 1) * 8, hipMemcpyDeviceToHost, st));
+    }
     ht.mark("packing queued");
     if ((rc = pack_prior_now())) return rc;
     ht.mark("priors packed");
@@ -1794,6 +1878,11 @@ static int encode_body(sfq_ctx* ctx, const u8* d_fastq_in, u64 nbytes_in, const 
     ht.mark("  statuses looked at");
     if (run > out_cap) return fail(ctx, SFQ_E_OVERFLOW, "output needs %llu bytes, caller gave %llu", (unsigned long long)run, (unsigned long long)out_cap);
     if (hboff[nblocks] > blob_cap) return fail(ctx, SFQ_E_OVERFLOW, "first-header blob overflow");
+    if (side) {                                                      // (they came home to page-locked memory with the head)
+        const size_t got = (size_t)std::min<u64>(hboff[nblocks], blob_guess);
+        ctx->first_hdrs.resize(got);
+        if (got) memcpy(ctx->first_hdrs.data(), (const u8*)ctx->pin2 + p2_blob, got);
+    }
     if (hboff[nblocks] > blob_guess) {                               // (long first headers: the rest of them)
         ctx->first_hdrs.resize((size_t)hboff[nblocks]);
         HIPC(hipMemcpyAsync(ctx->first_hdrs.data() + blob_guess, (const u8*)ctx->blob.p + blob_guess, (size_t)(hboff[nblocks] - blob_guess), hipMemcpyDeviceToHost, st));
