@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void k_qlt_frozen_rows(const u32* __restrict__
     u32 S = x;
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) S += (u32)__shfl_xor((int)S, d, 64);
-    u32 g = (x << 16) / S;                                  // x <= 65536: no overflow
+    u32 g = (u32)(((u64)x << 16) / S);                      // x <= 65536 (a frequency of 65535, the most "qlt.pri" holds): the product needs 33 bits
     g = g ? g : 1u;
     u32 sum = g, best = (g << 6) | (63u - lane);             // largest g, lowest symbol first
 #pragma unroll
