@@ -940,6 +940,114 @@ int sfq_ctx_set_screen(sfq_ctx* ctx, const sfq_screen* rule);
 /* 1: the last decode call screened, *out = what it found; 0: it did not (*out zeroed) */
 int sfq_get_screen(const sfq_ctx* ctx, sfq_screen_report* out);
 
+/* ---- demultiplexed records ----------------------------------------------------------------------------------------------------
+ * The first step of read preparation: a lane's reads split by SAMPLE, while the text is on the device (dmx.hip).  A unit carries a
+ * barcode in the index field of its header ("... 1:N:0:ATCACG", "...:ATCACG+TTAGGC") or inline at the start of its bases; the unit goes
+ * to the sample whose barcode is nearest, within a mismatch allowance.  Text to text like the distinct records, whose line starts and
+ * copy the pass uses; no stream, coder or block format knows of it.  Unlike every other pass it does not keep or drop records in
+ * place: it is a stable multi-way partition.
+ * Lines and records: they are sfq_pick_lines' own.  A line ends at '\n'; '\r' is a byte like any other.  Line lengths exclude the '\n'.
+ * Units: with pairs == 0 a unit is a record.  With pairs == 1 a unit is (record first_record + 2k, record first_record + 2k + 1),
+ *   mate 0 and mate 1.  The range is (first_record, n_records), n_records = UINT64_MAX: to the last record.  Records outside the
+ *   range are dropped.
+ * Barcode parts: a sample's barcode has one or two parts, part 0 then part 1, of len0 + len1 = B bases, 1 <= B <= 32, len0 >= 1;
+ *   part 1 is ABSENT where its len is 0 (its other fields are then not looked at).  A part says where its observed bytes come from:
+ *   SFQ_DEMUX_HEADER: of line 1 of the unit's record `mate`.  F = the bytes of line 1 behind its LAST ':'.  Subfield 0 = F up to its
+ *     first '+', or all of F without one; subfield 1 = what lies behind that '+'.  The observed bytes are subfield[sub][pos, pos + len);
+ *     what lies behind them is ignored.  The part is SHORT when line 1 holds no ':', when sub == 1 and F holds no '+', or when the
+ *     subfield has fewer than pos + len bytes.
+ *   SFQ_DEMUX_BASES: the observed bytes are line2[pos, pos + len) of the unit's record `mate`; the part is SHORT where line 2 is
+ *     shorter than pos + len.  sub must be 0.
+ * Distance: the comparison ignores letter case; an observed byte that is none of ACGTacgt mismatches every barcode base (the trim's
+ *   convention).  d(s) = the mismatching positions among all B positions of sample s (part 0's, then part 1's).
+ * Verdict of a unit, in this order: SHORT: some part is short.  Otherwise m = min over s of d(s).  FAR: m > max_mm.  AMBIGUOUS:
+ *   m <= max_mm and two or more samples attain m.  ASSIGNED to s: exactly one s attains m <= max_mm; PERFECT: assigned with m == 0.
+ *   Every unit that is not assigned goes to the UNASSIGNED part.
+ * Clip (clip != 0): of an ASSIGNED unit, record R loses the first c_R bytes of its lines 2 and 4, c_R = the largest pos + len among
+ *   the SFQ_DEMUX_BASES parts read from R (0 where there is none).  Lines 1 and 3 and every '\n' stay.  Unassigned units are never
+ *   clipped.  With clip a record of the range whose lines 2 and 4 differ in length is SFQ_E_FORMAT (sfq_last_error names the
+ *   smallest such record and its byte offset, as the trim does).  bases_clipped = the bytes that the lines 2 lost.
+ * Result: ONE buffer of NP parts back to back with nothing between them.  Without split_mates NP = n_samples + 1: part s < n_samples
+ *   holds sample s's units, part n_samples the unassigned ones.  With pairs and split_mates NP = 2 (n_samples + 1): part 2 s holds the
+ *   first mates and part 2 s + 1 the second mates of what part s would be.  Inside every part the records are whole (but for the
+ *   clip) and in their original order.  part_off[0 .. NP] are the boundaries, part_off[0] = 0, part_off[NP] = *out_bytes;
+ *   part_units[0 .. n_samples] the units of every sample, the unassigned last.  The result is never larger than the text: out_cap = n
+ *   always suffices.
+ * Final line end: a text that does not end in '\n' is SFQ_E_FORMAT -- its last record may land in the middle of the result (as
+ *   sfq_interleave refuses an A that does not end in one).  A decode's texts end in '\n'.
+ * Order of the refusals: the lines' count, the final '\n', the range, an odd count under pairs, a record of 4 GiB, the clip's unequal
+ *   lines, the output's room.
+ * Determinism: the result is a function of the text, the rule and the barcodes, never of scheduling: no atomic decides a place. */
+#define SFQ_DEMUX_HEADER 1
+#define SFQ_DEMUX_BASES  2
+#define SFQ_DEMUX_MAX_SAMPLES 4096
+typedef struct sfq_demux_part { uint32_t src, mate, sub, pos, len; } sfq_demux_part;
+/* src: SFQ_DEMUX_HEADER | SFQ_DEMUX_BASES; mate: 0 / 1, which record of the unit (0 without pairs) */
+typedef struct sfq_demux {
+    uint64_t first_record, n_records;   /* n_records = UINT64_MAX: to the last record */
+    uint32_t pairs, split_mates, max_mm, clip;
+    sfq_demux_part part[2];
+    uint32_t n_samples, reserved;       /* 1 .. SFQ_DEMUX_MAX_SAMPLES */
+} sfq_demux;
+typedef struct sfq_demux_report {
+    uint64_t n_in_range, n_units, n_assigned, n_perfect, n_short, n_far, n_ambiguous;   /* assigned + short + far + ambiguous == units */
+    uint64_t text_bytes, out_bytes, bases_clipped;
+} sfq_demux_report;
+/* host only, no GPU.  h_barcodes: n_samples rows of B = part[0].len + part[1].len bytes, part 0's bases then part 1's.  SFQ_OK, or
+ * SFQ_E_ARG for a null pointer, n_records == 0, pairs > 1, an odd first_record with pairs, split_mates without pairs, a mate != 0
+ * without pairs or > 1, a sub > 1 or != 0 on a SFQ_DEMUX_BASES part, an unknown src, pos + len beyond 32 bits, part[0].len == 0, B
+ * outside 1 .. 32, max_mm > B, n_samples outside 1 .. SFQ_DEMUX_MAX_SAMPLES, a barcode byte outside ACGT (upper case), two equal rows. */
+int sfq_demux_check(const sfq_demux* rule, const uint8_t* h_barcodes);
+/* host only: the terms of the CLI's -X into *rule: "SHEET[,term...]".  The FIRST term is the sample sheet's path and is skipped, as are
+ * the file terms out=PREFIX and counts=FILE.  mm=N: max_mm (default 1); hdr (the default): part 0 from header subfield 0, part 1
+ * from header subfield 1; inline[=POS]: part 0 from mate 0's bases at POS (default 0); inline2[=POS]: with inline, part 1 from mate
+ * 1's bases; hdr2: with inline, part 1 from header subfield 0; clip.  The parts' lengths are left 0: they are the sheet's; the range
+ * is (0, UINT64_MAX), pairs, split_mates and n_samples 0.  SFQ_E_ARG for a null pointer, an unknown term, a bad number, hdr with inline,
+ * inline2 or hdr2 without inline, or both; err (may be NULL) then says which. */
+int sfq_demux_parse(const char* spec, sfq_demux* rule, char* err, uint64_t err_cap);
+/* host only: a sample sheet text[0, n).  Lines end at '\n' (a '\r' in front of it is dropped); empty lines and lines that begin with
+ * '#' are skipped.  A data line is name<TAB>BARCODE, name<TAB>BARCODE0+BARCODE1 or name<TAB>BARCODE0<TAB>BARCODE1; barcodes in
+ * either case of ACGT, stored upper case.  All rows have the same len0 >= 1 and len1 (0: one part), len0 + len1 <= 32.  Names are 1 ..
+ * 64 bytes of [A-Za-z0-9._-], unique, none equal to "unassigned".  names_out: max_samples rows of 65 bytes, NUL-terminated;
+ * barcodes_out: max_samples rows of 32 bytes' room, of which the first n_samples * (len0 + len1) are written: row s at s * (len0 +
+ * len1), what sfq_demux_check and sfq_demux_records take.  SFQ_E_ARG for a null pointer (err may be NULL), max_samples == 0, a sheet
+ * without data lines or with more than min(max_samples, SFQ_DEMUX_MAX_SAMPLES), a malformed line, a bad name, unequal lengths, a
+ * duplicate name or barcode; err then names the line, counted from 1. */
+int sfq_demux_sheet(const char* text, uint64_t n, uint32_t max_samples, char* names_out, uint8_t* barcodes_out,
+                    uint32_t* n_samples, uint32_t* len0, uint32_t* len1, char* err, uint64_t err_cap);
+/* The units of d_text[0, n) by sample into d_out; *out_bytes = the bytes of the result (on SFQ_E_OVERFLOW: the size needed).
+ * part_off: host, NP + 1 entries; part_units: host, n_samples + 1 entries, may be NULL; report may be NULL.
+ * SFQ_E_ARG: a null pointer, n == 0, what sfq_demux_check refuses, a range that ends behind the last record.  SFQ_E_FORMAT: lines
+ * that are no multiple of four, a text without a final '\n', with pairs an odd record count in the range, with clip a record whose
+ * lines 2 and 4 differ in length.  SFQ_E_UNSUPPORTED: a record of 4 GiB or more.  SFQ_E_OVERFLOW: a result larger than out_cap.
+ * Every refusal is decided on the device before the copy: a refused call writes nothing to d_out.  A call that succeeds writes
+ * d_out[0, *out_bytes) and nothing else; the text is never written.  d_out must not overlap the text; both may lie at any byte
+ * alignment.  The call runs on the context's stream and synchronises once.  Like the other side passes, it may read the whole aligned
+ * 16-byte units that hold the text's first and last byte.  All offsets are 64-bit.  Working memory: like the other side passes the
+ * call lays its arrays out BEFORE the records are counted, for one record per 64 bytes of text (or the most records an earlier call on
+ * the context met; a text with more runs twice): about 75 bytes per such record, with clip 127 -- 1.2 and 2.0 times the text's size in
+ * the context's working buffer, whatever n_samples is: the partition sorts by digits of the class and keeps 256 counters per 1024
+ * records, not a counter per tile and class. */
+int sfq_demux_records(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, const sfq_demux* rule, const uint8_t* h_barcodes,
+                      uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* part_off, uint64_t* part_units,
+                      sfq_demux_report* report);
+/* rule != NULL: sfq_decode_blocks_host and sfq_decode_block_range_host hand back the PARTITIONED text of what they decoded (rule and
+ * barcodes are copied; SFQ_E_ARG, and the setting stays, where sfq_demux_check refuses them); NULL: off (default).  Order: the trim,
+ * the overlap, the selection, the screen, the dedup, THE DEMUX: it is the call's last pass.  The CRCs stay those of the decoded text.
+ * out_cap keeps sizing the DECODED text.  Costs one more device buffer of the text's size, held while the switch is on, and
+ * sfq_demux_records' working memory (above) in the buffer the passes share.  SFQ_E_ARG at the decode call while the merge, the pick
+ * or the pair split is on, and from sfq_decode_pair_range_host (split_mates is the split; the others are not combined with the
+ * demux); SFQ_E_ARG too where a selection, a screen or a dedup in front has pairs == 0 and the demux pairs == 1, or the other way
+ * round: the mates would fall out of step.  With nothing left by a pass in front the _host entries return SFQ_OK and 0 bytes as
+ * they do today, and sfq_get_demux answers 0.  The device-pointer decode entries are not affected.  Default off: nothing is
+ * launched, allocated or copied that is not today. */
+int sfq_ctx_set_demux(sfq_ctx* ctx, const sfq_demux* rule, const uint8_t* h_barcodes);
+/* 1: the last decode call demultiplexed: *report (may be NULL) = what it found, part_off[0 .. NP] and part_units[0 .. n_samples] (either
+ * may be NULL) as sfq_demux_records gives them, where cap_entries >= NP + 1; 0: it did not (*report zeroed).  SFQ_E_ARG for a null context
+ * and for a cap_entries below NP + 1 with either array given: the context is const here as for the sibling getters, so this refusal
+ * leaves no message and sfq_last_error keeps what it said before. */
+int sfq_get_demux(const sfq_ctx* ctx, sfq_demux_report* report, uint64_t* part_off, uint64_t* part_units, uint64_t cap_entries);
+
 /* ---- the ".sfq" container (host only) ----------------------------------------------------------
  * Replaces FilerSave + the info page (filer.cpp:217-242, config.cpp:334-347) for hosts that assemble an archive
  * themselves: info_text is the info page ("key=value\n" lines), then n_streams named byte streams (names of at most

@@ -48,6 +48,7 @@ EXPORTS = [
     "sfq_ctx_set_dedup", "sfq_get_dedup",
     "sfq_screen_check", "sfq_screen_parse", "sfq_fasta_sequences", "sfq_screen_set_create", "sfq_screen_set_add", "sfq_screen_set_clear",
     "sfq_screen_set_destroy", "sfq_screen_set_info", "sfq_screen_records", "sfq_ctx_set_screen", "sfq_get_screen",
+    "sfq_demux_check", "sfq_demux_parse", "sfq_demux_sheet", "sfq_demux_records", "sfq_ctx_set_demux", "sfq_get_demux",
 ]
 
 
@@ -199,6 +200,83 @@ def screen_parse(spec: str):
     if lib().sfq_screen_parse(spec.encode(), C.byref(rule), C.byref(k), err, len(err)):
         raise ValueError(err.value.decode())
     return rule, int(k.value)
+
+
+DEMUX_HEADER, DEMUX_BASES, DEMUX_MAX_SAMPLES = 1, 2, 4096
+
+
+class DemuxPart(C.Structure):
+    """sfq_demux_part: where a barcode part's observed bytes come from.  len 0: the part is absent."""
+    _fields_ = [("src", C.c_uint32), ("mate", C.c_uint32), ("sub", C.c_uint32), ("pos", C.c_uint32), ("len", C.c_uint32)]
+
+    def __init__(self, src=0, mate=0, sub=0, pos=0, len=0):
+        super().__init__(int(src), int(mate), int(sub), int(pos), int(len))
+
+
+class Demux(C.Structure):
+    """sfq_demux: the rule of a demultiplexing (dmx.hip).  parts: one or two DemuxPart."""
+    _fields_ = [("first_record", C.c_uint64), ("n_records", C.c_uint64), ("pairs", C.c_uint32), ("split_mates", C.c_uint32),
+                ("max_mm", C.c_uint32), ("clip", C.c_uint32), ("part", DemuxPart * 2), ("n_samples", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, parts=(), n_samples=0, max_mm=1, pairs=0, split_mates=0, clip=0, first_record=0, n_records=None):
+        super().__init__()
+        self.first_record, self.n_records = first_record, SELECT_TO_END if n_records is None else n_records
+        self.pairs, self.split_mates, self.max_mm, self.clip, self.n_samples = int(pairs), int(split_mates), int(max_mm), int(clip), int(n_samples)
+        for i, p in enumerate(parts):
+            self.part[i] = p
+
+    @property
+    def n_parts(self):
+        """NP: the parts of the result."""
+        return (2 if self.split_mates else 1) * (self.n_samples + 1)
+
+
+class DemuxReport(C.Structure):
+    """sfq_demux_report: what a demultiplexing found."""
+    _fields_ = [("n_in_range", C.c_uint64), ("n_units", C.c_uint64), ("n_assigned", C.c_uint64), ("n_perfect", C.c_uint64),
+                ("n_short", C.c_uint64), ("n_far", C.c_uint64), ("n_ambiguous", C.c_uint64), ("text_bytes", C.c_uint64),
+                ("out_bytes", C.c_uint64), ("bases_clipped", C.c_uint64)]
+
+
+def _barcode_rows(barcodes, rule=None) -> bytes:
+    """the rows as the library takes them; with a rule, a ValueError unless they are its n_samples rows of B bytes (the library reads that many)"""
+    rows = bytes(barcodes) if isinstance(barcodes, (bytes, bytearray)) else b"".join(barcodes)
+    if rule is not None:
+        want = rule.n_samples * (rule.part[0].len + rule.part[1].len)
+        if len(rows) != want:
+            raise ValueError("barcodes: %d bytes, the rule's %d samples of %d bases are %d" % (len(rows), rule.n_samples, rule.part[0].len + rule.part[1].len, want))
+    return rows
+
+
+def demux_check(rule, barcodes) -> int:
+    """sfq_demux_check (no GPU): 0, or E_ARG for a rule or barcodes the library refuses.  barcodes: the rows, a list of bytes or
+    one bytes object of n_samples * B bytes; None: a null pointer."""
+    try:
+        rows = None if barcodes is None else _barcode_rows(barcodes, rule)
+    except ValueError:
+        return -1                                                       # rows that are not the rule's: E_ARG, and the library is not shown them
+    return int(lib().sfq_demux_check(None if rule is None else C.byref(rule), rows))
+
+
+def demux_parse(spec: str):
+    """sfq_demux_parse (no GPU): the Demux of the terms of the CLI's -X (lengths and samples are the sheet's); a ValueError
+    carries the library's message."""
+    rule, err = Demux(), C.create_string_buffer(256)
+    if lib().sfq_demux_parse(spec.encode(), C.byref(rule), err, len(err)):
+        raise ValueError(err.value.decode())
+    return rule
+
+
+def demux_sheet(text: bytes, max_samples=DEMUX_MAX_SAMPLES):
+    """sfq_demux_sheet (no GPU): (names, barcodes, len0, len1) of a sample sheet's bytes, barcodes a list of bytes rows (part 0's
+    bases, then part 1's); a ValueError carries the library's message, which names the line."""
+    names, codes = C.create_string_buffer(65 * max_samples), C.create_string_buffer(32 * max_samples)
+    n, l0, l1, err = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.create_string_buffer(256)
+    if lib().sfq_demux_sheet(text, len(text), int(max_samples), names, codes, C.byref(n), C.byref(l0), C.byref(l1), err, len(err)):
+        raise ValueError(err.value.decode())
+    B = l0.value + l1.value
+    return ([names.raw[65 * s:65 * s + 65].split(b"\0", 1)[0].decode() for s in range(n.value)],
+            [codes.raw[B * s:B * s + B] for s in range(n.value)], int(l0.value), int(l1.value))
 
 
 def fasta_sequences(fasta: bytes, cap=None, size_only=False):
@@ -473,6 +551,13 @@ def lib():
         L.sfq_screen_records.argtypes = [vp, vp, u64, C.POINTER(Screen), vp, u64, u64p, C.POINTER(ScreenReport)]
         L.sfq_ctx_set_screen.argtypes = [vp, C.POINTER(Screen)]
         L.sfq_get_screen.argtypes = [vp, C.POINTER(ScreenReport)]
+        L.sfq_demux_check.argtypes = [C.POINTER(Demux), C.c_char_p]
+        L.sfq_demux_parse.argtypes = [C.c_char_p, C.POINTER(Demux), C.c_char_p, u64]
+        L.sfq_demux_sheet.argtypes = [C.c_char_p, u64, C.c_uint32, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                      C.POINTER(C.c_uint32), C.c_char_p, u64]
+        L.sfq_demux_records.argtypes = [vp, vp, u64, C.POINTER(Demux), C.c_char_p, vp, u64, u64p, u64p, u64p, C.POINTER(DemuxReport)]
+        L.sfq_ctx_set_demux.argtypes = [vp, C.POINTER(Demux), C.c_char_p]
+        L.sfq_get_demux.argtypes = [vp, C.POINTER(DemuxReport), u64p, u64p, u64]
         _lib = L
     return _lib
 
@@ -932,6 +1017,41 @@ class Context:
         if rc < 0:
             self._check(rc)
         return rep if rc == 1 else None
+
+    def demux_records(self, d_text, nbytes, rule, barcodes, d_out, out_cap):
+        """The units (records, or pairs) of the FASTQ text in the device buffer at d_text sorted by the sample whose barcode they
+        carry, every sample's in their original order, the unassigned last, into the one at d_out (sfq_demux_records); returns
+        (bytes written, part offsets [NP + 1], units per sample [n_samples + 1], DemuxReport).  An SfqError of code E_OVERFLOW
+        carries the size needed as .needed."""
+        n, rep = C.c_uint64(), DemuxReport()
+        off, units = (C.c_uint64 * (rule.n_parts + 1))(), (C.c_uint64 * (rule.n_samples + 1))()
+        rc = lib().sfq_demux_records(self._h, C.c_void_p(d_text), int(nbytes), C.byref(rule), _barcode_rows(barcodes, rule), C.c_void_p(d_out),
+                                     int(out_cap), C.byref(n), off, units, C.byref(rep))
+        try:
+            self._check(rc)
+        except SfqError as e:
+            e.needed = int(n.value)
+            raise
+        return int(n.value), list(off), list(units), rep
+
+    def set_demux(self, rule=None, barcodes=None):
+        """A Demux and its barcode rows: decode_host and decode_range_host return the text they decoded partitioned by sample,
+        behind the dedup, as the call's last pass (get_demux() says where the parts lie); None: off."""
+        self._check(lib().sfq_ctx_set_demux(self._h, None if rule is None else C.byref(rule),
+                                            None if barcodes is None else _barcode_rows(barcodes, rule)))
+        self._demux_entries = 0 if rule is None else rule.n_parts + 1
+        self._demux_samples = 0 if rule is None else rule.n_samples
+
+    def get_demux(self):
+        """(DemuxReport, part offsets, units per sample) of the last decode call; None where it did not demultiplex."""
+        rep, cap = DemuxReport(), max(getattr(self, "_demux_entries", 0), 1)
+        off, units = (C.c_uint64 * cap)(), (C.c_uint64 * cap)()
+        rc = lib().sfq_get_demux(self._h, C.byref(rep), off, units, cap)
+        if rc < 0:
+            self._check(rc)
+        if rc != 1:
+            return None
+        return rep, list(off), list(units)[:getattr(self, "_demux_samples", 0) + 1]
 
     def screen_records(self, d_text, nbytes, rule, d_out, out_cap):
         """The units (records, or pairs) of the FASTQ text in the device buffer at d_text that the rule keeps -- those whose base

@@ -238,6 +238,10 @@ struct sfq_ctx {
     bool sset_on = false; u32 sset_k = 0;             // sfq_screen_set_create: the one set of k-mers: its slot table, its counter, the piece of a sequence text on its way up
     DevBuf sset_slots, sset_info, sset_stage;
     u64 sset_nslots = 0, sset_max = 0, sset_kmers = 0;
+    // demultiplexed records (dmx.hip): works in pair_work and reports through pair_pin too; nothing of this exists until the switch is on
+    bool dmx_on = false; sfq_demux dmx{}; std::vector<u8> dmx_codes;      // sfq_ctx_set_demux: the rule and its barcode rows
+    DevBuf dmx_out;                                   // the partitioned text of a decoded one (while the switch is on)
+    bool dmx_done = false; sfq_demux_report dmx_report{}; std::vector<u64> dmx_off, dmx_units;   // the last decode call's
     u32 scr_lanes = 8;                                // k_scr_count's lanes a record (SFQ_SCR_LANES: profiles/screen_pass.py's layout comparison)
 };
 
@@ -1003,7 +1007,7 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
         &ctx->oflags, &ctx->okbytes, &ctx->ofpos, &ctx->okoff, &ctx->ofilt, &ctx->orecmap, &ctx->olist, &ctx->line_off_o, &ctx->ono, &ctx->opiece,
         &ctx->otxt[0], &ctx->otxt[1], &ctx->otxt[2], &ctx->osize_all, &ctx->oroff_all, &ctx->oroff_k, &ctx->ocnt,
         &ctx->crc_tab, &ctx->crc_tiles, &ctx->crc_grps, &ctx->crc_bounds, &ctx->crc_out, &ctx->stats_acc, &ctx->qmap_dev,
-        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out, &ctx->pick_out, &ctx->sel_out, &ctx->trim_out, &ctx->ovl_out, &ctx->mrg_out, &ctx->dd_out, &ctx->scr_out };
+        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out, &ctx->pick_out, &ctx->sel_out, &ctx->trim_out, &ctx->ovl_out, &ctx->mrg_out, &ctx->dd_out, &ctx->scr_out, &ctx->dmx_out };
     for (DevBuf* b : all) release(*b);
     (void)sfq_dedup_set_destroy(ctx);
     (void)sfq_screen_set_destroy(ctx);
@@ -3337,6 +3341,267 @@ int sfq_get_screen(const sfq_ctx* ctx, sfq_screen_report* out) {
     return 1;
 }
 
+// ---- demultiplexed records (dmx.hip) -----------------------------------------------------------------------------------------------
+int sfq_demux_check(const sfq_demux* d, const uint8_t* h_barcodes) {
+    if (!d || !h_barcodes) return SFQ_E_ARG;
+    if (!d->n_records || d->pairs > 1 || (d->pairs && (d->first_record & 1)) || (d->split_mates && !d->pairs)) return SFQ_E_ARG;
+    if (!d->part[0].len) return SFQ_E_ARG;
+    for (int p = 0; p < 2; p++) {
+        const sfq_demux_part& P = d->part[p];
+        if (!P.len) continue;                                  // part 1: absent
+        if (P.src != SFQ_DEMUX_HEADER && P.src != SFQ_DEMUX_BASES) return SFQ_E_ARG;
+        if (P.mate > 1 || (P.mate && !d->pairs)) return SFQ_E_ARG;
+        if (P.sub > 1 || (P.sub && P.src == SFQ_DEMUX_BASES)) return SFQ_E_ARG;
+        if ((u64)P.pos + P.len > 0xFFFFFFFFull) return SFQ_E_ARG;
+    }
+    const u64 B = (u64)d->part[0].len + d->part[1].len;
+    if (B < 1 || B > 32 || d->max_mm > B) return SFQ_E_ARG;
+    if (d->n_samples < 1 || d->n_samples > SFQ_DEMUX_MAX_SAMPLES) return SFQ_E_ARG;
+    std::vector<std::string> rows(d->n_samples);
+    for (u32 s = 0; s < d->n_samples; s++) {
+        for (u64 i = 0; i < B; i++) {
+            const u8 c = h_barcodes[s * B + i];
+            if (c != 'A' && c != 'C' && c != 'G' && c != 'T') return SFQ_E_ARG;
+        }
+        rows[s].assign((const char*)h_barcodes + s * B, (size_t)B);
+    }
+    std::sort(rows.begin(), rows.end());
+    for (u32 s = 1; s < d->n_samples; s++) if (rows[s] == rows[s - 1]) return SFQ_E_ARG;
+    return SFQ_OK;
+}
+// "SHEET,term,term,...": see slimfastq_amd.h
+int sfq_demux_parse(const char* spec, sfq_demux* rule, char* err, uint64_t err_cap) {
+    auto bad = [&](const char* fmt, const std::string& what) {
+        if (err && err_cap) snprintf(err, (size_t)err_cap, fmt, what.c_str());
+        return SFQ_E_ARG;
+    };
+    if (!spec || !rule) return SFQ_E_ARG;
+    memset(rule, 0, sizeof *rule);
+    rule->n_records = ~0ull; rule->max_mm = 1;
+    bool hdr = false, in1 = false, in2 = false, hdr2 = false;
+    u64 pos1 = 0, pos2 = 0;
+    const std::string all = spec;
+    if (all.empty()) return bad("an empty list of terms%s", "");
+    bool first = true;
+    for (size_t at = 0; at <= all.size(); first = false) {
+        const size_t comma = std::min(all.find(',', at), all.size());
+        const std::string term = all.substr(at, comma - at);
+        at = comma + 1;
+        if (first) { if (term.empty()) return bad("the first term is the sample sheet's file%s", ""); continue; }
+        const size_t eq = term.find('=');
+        const std::string key = term.substr(0, eq), val = eq == std::string::npos ? "" : term.substr(eq + 1);
+        const bool has = eq != std::string::npos;
+        u64 v = 0;
+        if ((key == "out" || key == "counts") && has) { if (val.empty()) return bad("%s: a file name is missing", term); }
+        else if (key == "mm" && has) { if (!number(val, 32, &v)) return bad("mm=%s: a number of mismatches of 0 to 32", val); rule->max_mm = (u32)v; }
+        else if (term == "hdr") hdr = true;
+        else if (term == "hdr2") hdr2 = true;
+        else if (term == "clip") rule->clip = 1;
+        else if (key == "inline") { if (has && !number(val, 0xFFFFFFFFull, &pos1)) return bad("inline=%s: a position in the bases", val); in1 = true; }
+        else if (key == "inline2") { if (has && !number(val, 0xFFFFFFFFull, &pos2)) return bad("inline2=%s: a position in the bases", val); in2 = true; }
+        else return bad("%s: no such term (mm= hdr inline[=] inline2[=] hdr2 clip out= counts=)", term);
+    }
+    if (hdr && in1) return bad("hdr and inline: part 0 comes from one of them%s", "");
+    if ((in2 || hdr2) && !in1) return bad("%s: only with inline", in2 ? "inline2" : "hdr2");
+    if (in2 && hdr2) return bad("inline2 and hdr2: part 1 comes from one of them%s", "");
+    rule->part[0] = in1 ? sfq_demux_part{ SFQ_DEMUX_BASES, 0, 0, (u32)pos1, 0 } : sfq_demux_part{ SFQ_DEMUX_HEADER, 0, 0, 0, 0 };
+    if (in2) rule->part[1] = sfq_demux_part{ SFQ_DEMUX_BASES, 1, 0, (u32)pos2, 0 };
+    else if (hdr2) rule->part[1] = sfq_demux_part{ SFQ_DEMUX_HEADER, 0, 0, 0, 0 };
+    else if (!in1) rule->part[1] = sfq_demux_part{ SFQ_DEMUX_HEADER, 0, 1, 0, 0 };
+    return SFQ_OK;
+}
+int sfq_demux_sheet(const char* text, uint64_t n, uint32_t max_samples, char* names_out, uint8_t* barcodes_out,
+                    uint32_t* n_samples, uint32_t* len0, uint32_t* len1, char* err, uint64_t err_cap) {
+    u64 line = 0;
+    auto bad = [&](const char* what) {
+        if (err && err_cap) snprintf(err, (size_t)err_cap, "sample sheet, line %llu: %s", (unsigned long long)line, what);
+        return SFQ_E_ARG;
+    };
+    if (n_samples) *n_samples = 0;
+    if (len0) *len0 = 0;
+    if (len1) *len1 = 0;
+    if (!text || !names_out || !barcodes_out || !n_samples || !len0 || !len1 || !max_samples) return bad("a null argument");
+    const u32 most = std::min<u32>(max_samples, SFQ_DEMUX_MAX_SAMPLES);
+    std::vector<std::string> names, codes;
+    u32 l0 = 0, l1 = 0;
+    for (u64 at = 0; at < n; ) {
+        const char* nl = (const char*)memchr(text + at, '\n', (size_t)(n - at));
+        u64 end = nl ? (u64)(nl - text) : n;
+        const u64 next = end + 1;
+        if (end > at && text[end - 1] == '\r') end--;
+        const std::string row(text + at, (size_t)(end - at));
+        at = next; line++;
+        if (row.empty() || row[0] == '#') continue;
+        const size_t t1 = row.find('\t');
+        if (t1 == std::string::npos) return bad("no TAB behind the name");
+        const std::string name = row.substr(0, t1);
+        std::string b0 = row.substr(t1 + 1), b1;
+        const size_t sep = b0.find_first_of("+\t");
+        if (sep != std::string::npos) { b1 = b0.substr(sep + 1); b0.resize(sep); if (b1.empty()) return bad("an empty second barcode"); }
+        if (name.empty() || name.size() > 64) return bad("a name of 1 to 64 bytes");
+        for (char c : name) if (!isalnum((unsigned char)c) && c != '.' && c != '_' && c != '-') return bad("a name of [A-Za-z0-9._-]");
+        if (name == "unassigned") return bad("the name \"unassigned\" is the part of the units no sample takes");
+        std::string code = b0 + b1;
+        for (char& c : code) {
+            c = (char)toupper((unsigned char)c);
+            if (c != 'A' && c != 'C' && c != 'G' && c != 'T') return bad("a barcode of ACGT (one '+' or TAB between two)");
+        }
+        if (b0.empty() || code.size() > 32) return bad("a barcode of 1 to 32 bases");
+        if (names.empty()) { l0 = (u32)b0.size(); l1 = (u32)b1.size(); }
+        else if (l0 != b0.size() || l1 != b1.size()) return bad("barcode lengths that differ from the first row's");
+        if (names.size() == most) return bad("more samples than the call takes");
+        if (std::find(names.begin(), names.end(), name) != names.end()) return bad("a name that an earlier row has");
+        if (std::find(codes.begin(), codes.end(), code) != codes.end()) return bad("a barcode that an earlier row has");
+        names.push_back(name); codes.push_back(code);
+    }
+    if (names.empty()) return bad("no sample");
+    const u32 B = l0 + l1;
+    for (size_t s = 0; s < names.size(); s++) {
+        memset(names_out + s * 65, 0, 65);
+        memcpy(names_out + s * 65, names[s].data(), names[s].size());
+        memcpy(barcodes_out + s * B, codes[s].data(), B);
+    }
+    *n_samples = (u32)names.size(); *len0 = l0; *len1 = l1;
+    return SFQ_OK;
+}
+// dedup_run's shape: one pass on the context's stream, one synchronise, in pair_run's working buffers and with its sizing; only a
+// text with more records than the arrays were laid out for runs twice.  part_off: np + 1 entries, part_units: n_samples + 1 or null.
+static int demux_run(sfq_ctx* ctx, const u8* text, u64 n, const sfq_demux& d, const u8* barcodes, u8* out, u64 out_cap,
+                     u64* part_off, u64* part_units, sfq_demux_report* rep) {
+    int rc;
+    memset(rep, 0, sizeof *rep);
+    const u32 ns = d.n_samples, np = (d.split_mates ? 2 : 1) * (ns + 1), B = d.part[0].len + d.part[1].len;
+    auto up = [](u64 v) { return (v + 15) & ~15ull; };
+    const size_t info_bytes = up(std::max({ sizeof(PairInfo), sizeof(PickInfo), sizeof(SelInfo), sizeof(DdInfo), sizeof(ScrInfo), sizeof(DmxInfo) }));
+    const size_t codes_bytes = up((u64)ns * 8), bounds_bytes = up(2 * (u64)(np + 1) * 8);
+    if ((rc = reserve_pinned_buf(ctx, ctx->pair_pin, ctx->pair_pin_cap, info_bytes + codes_bytes + bounds_bytes))) return rc;
+    DmxJob job{ d.first_record, d.n_records, out_cap, d.pairs, d.split_mates ? 1u : 0u, d.max_mm, d.clip ? 1u : 0u, ns, np, 0, 0, {} };
+    for (int p = 0; p < 2; p++) {
+        const sfq_demux_part& P = d.part[p];
+        job.part[p] = DmxPart{ P.len ? P.src : 0u, P.len ? P.mate : 0u, P.sub, P.pos, P.len };
+        if (d.clip && P.len && P.src == SFQ_DEMUX_BASES) {
+            u32& c = P.mate ? job.clip1 : job.clip0;
+            c = std::max(c, P.pos + P.len);
+        }
+    }
+    u64* h_codes = (u64*)((u8*)ctx->pair_pin + info_bytes);    // two bits a base, (byte >> 1) & 3: base i in bits 2 i, 2 i + 1
+    for (u32 s = 0; s < ns; s++) {
+        u64 c = 0;
+        for (u32 i = 0; i < B; i++) c |= (u64)((barcodes[(u64)s * B + i] >> 1) & 3) << (2 * i);
+        h_codes[s] = c;
+    }
+    const u64* h_bounds = (const u64*)((u8*)ctx->pair_pin + info_bytes + codes_bytes);
+    DmxInfo got;
+    for (int attempt = 0; ; attempt++) {
+        const u64 cap = std::max<u64>(ctx->pair_cap, n / 64 + 1024);
+        const u64 nlens = std::min(d.n_records, cap);
+        const u64 ucap = d.pairs ? (nlens + 1) / 2 : nlens;
+        const u64 ntiles = (nlens + DMX_TILE - 1) / DMX_TILE, pcap = d.clip ? 3 * nlens : nlens;
+        u64 at = info_bytes;
+        const u64 sc = at; at += up(qmap_scratch(text, n).bytes);
+        const u64 ls = at; at += up((4 * cap + 1) * 8);
+        const u64 codes = at; at += codes_bytes;
+        const u64 cls = at; at += up(nlens * 4);
+        const u64 ord_a = at; at += up(nlens * 8);
+        const u64 ord_b = at; at += up(np > 256 ? nlens * 8 : 0);
+        const u64 hist = at; at += up(256 * ntiles * 4);
+        const u64 hoff = at; at += up((256 * ntiles + 1) * 8);
+        const u64 cnt = at; at += up(d.clip ? nlens * 4 : 0);
+        const u64 ato = at; at += up(d.clip ? (nlens + 1) * 8 : 0);
+        const u64 lens = at; at += up(pcap * 4);
+        const u64 from = at; at += up(pcap * 8);
+        const u64 dst = at; at += up((pcap + 1) * 8);
+        const u64 tmp = at; at += up((std::max(pcap, 256 * ntiles) / 1024 + 2) * 8);
+        const u64 bounds = at; at += bounds_bytes;
+        if ((rc = reserve(ctx, ctx->pair_work, (size_t)at))) return rc;
+        u8* w = (u8*)ctx->pair_work.p;
+        DmxInfo* info = (DmxInfo*)w;
+        HIPC(hipMemsetAsync(info, 0, sizeof(DmxInfo), ctx->st));
+        HIPC(hipMemcpyAsync(w + codes, h_codes, (size_t)ns * 8, hipMemcpyHostToDevice, ctx->st));
+        const PairText t{ text, n, w + sc, nullptr };
+        const DmxArrays A{ (u64*)(w + ls), (const u64*)(w + codes), (u32*)(w + cls), (u64*)(w + ord_a), (u64*)(w + ord_b), (u32*)(w + hist), (u64*)(w + hoff),
+                           (u32*)(w + cnt), (u64*)(w + ato), (u32*)(w + lens), (u64*)(w + from), (u64*)(w + dst), (u64*)(w + tmp), (u64*)(w + bounds),
+                           cap, nlens, ucap, ntiles, pcap };
+        launch_demux(t, A, job, out, info, ctx->st);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(ctx->pair_pin, info, sizeof(DmxInfo), hipMemcpyDeviceToHost, ctx->st));
+        HIPC(hipMemcpyAsync((void*)h_bounds, w + bounds, 2 * (size_t)(np + 1) * 8, hipMemcpyDeviceToHost, ctx->st));
+        HIPC(hipStreamSynchronize(ctx->st));
+        memcpy(&got, ctx->pair_pin, sizeof(DmxInfo));
+        if (got.status != DMX_CAP) break;
+        if (attempt) return fail(ctx, SFQ_E_HIP, "demultiplexed records: the records did not fit twice");
+        ctx->pair_cap = got.recs;
+    }
+    rep->text_bytes = n;
+    const unsigned long long r0 = d.first_record, nr = d.n_records, recs = got.recs;
+    switch (got.status) {
+    case DMX_OK: break;
+    case DMX_LINES: return fail(ctx, SFQ_E_FORMAT, "demultiplexed records: the text holds %llu lines, not a multiple of four", (unsigned long long)got.lines);
+    case DMX_END: return fail(ctx, SFQ_E_FORMAT, "demultiplexed records: the text does not end in a line end: its last record could not stand in front of another");
+    case DMX_RANGE:
+        if (d.n_records == ~0ull) return fail(ctx, SFQ_E_ARG, "demultiplexed records: record %llu lies behind the text's %llu records", r0, recs);
+        return fail(ctx, SFQ_E_ARG, "demultiplexed records: records %llu..+%llu end behind the text's %llu records", r0, nr, recs);
+    case DMX_ODD: return fail(ctx, SFQ_E_FORMAT, "demultiplexed records: the range holds an odd number of records, which are no pairs (records %llu.. of %llu)", r0, recs);
+    case DMX_LONG: return fail(ctx, SFQ_E_UNSUPPORTED, "demultiplexed records: a record of 4 GiB or more");
+    case DMX_CLIP:
+        return fail(ctx, SFQ_E_FORMAT, "demultiplexed records: record %llu (at byte %llu) has base and quality lines of different lengths: the clip cuts both alike",
+                    (unsigned long long)got.bad_first, (unsigned long long)got.bad_off);
+    case DMX_ROOM:
+        rep->out_bytes = got.copy.nout;
+        return fail(ctx, SFQ_E_OVERFLOW, "demultiplexed records: the result needs %llu bytes", (unsigned long long)got.copy.nout);
+    default: return fail(ctx, SFQ_E_HIP, "demultiplexed records: status %u", got.status);
+    }
+    rep->n_in_range = got.nr; rep->n_units = got.units; rep->n_assigned = got.n_assigned; rep->n_perfect = got.n_perfect;
+    rep->n_short = got.n_short; rep->n_far = got.n_far; rep->n_ambiguous = got.n_ambiguous; rep->out_bytes = got.copy.nout;
+    rep->bases_clipped = got.n_assigned * ((u64)job.clip0 + job.clip1);
+    for (u32 c = 0; c <= np; c++) part_off[c] = h_bounds[c];
+    if (part_units) {
+        const u64* first = h_bounds + np + 1;                  // the sorted position of every part's first record
+        for (u32 s = 0; s <= ns; s++)
+            part_units[s] = d.split_mates ? first[2 * s + 1] - first[2 * s] : (first[s + 1] - first[s]) >> (d.pairs ? 1 : 0);
+    }
+    return SFQ_OK;
+}
+int sfq_demux_records(sfq_ctx* ctx, const uint8_t* d_text, uint64_t n, const sfq_demux* rule, const uint8_t* h_barcodes,
+                      uint8_t* d_out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* part_off, uint64_t* part_units,
+                      sfq_demux_report* report) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!d_text || !d_out || !out_bytes || !rule || !h_barcodes || !part_off) return fail(ctx, SFQ_E_ARG, "null argument");
+    *out_bytes = 0;
+    if (report) memset(report, 0, sizeof *report);
+    if (!n) return fail(ctx, SFQ_E_ARG, "demultiplexed records: an empty text");
+    if (sfq_demux_check(rule, h_barcodes)) return fail(ctx, SFQ_E_ARG, "demultiplexed records: a rule or barcodes that sfq_demux_check refuses");
+    HIPC(hipSetDevice(ctx->dev));
+    Settle settle(ctx);
+    sfq_demux_report rep;
+    const int rc = demux_run(ctx, d_text, n, *rule, h_barcodes, d_out, out_cap, part_off, part_units, &rep);
+    if (rc == SFQ_E_OVERFLOW) *out_bytes = rep.out_bytes;
+    if (rc) return rc;
+    *out_bytes = rep.out_bytes;
+    if (report) *report = rep;
+    settle.ok = true;
+    return SFQ_OK;
+}
+int sfq_ctx_set_demux(sfq_ctx* ctx, const sfq_demux* rule, const uint8_t* h_barcodes) {
+    if (!ctx) return SFQ_E_ARG;
+    if (rule && sfq_demux_check(rule, h_barcodes)) return fail(ctx, SFQ_E_ARG, "demultiplexed records: a rule or barcodes that sfq_demux_check refuses");
+    ctx->dmx_on = rule != nullptr;
+    if (rule) {
+        ctx->dmx = *rule;
+        ctx->dmx_codes.assign(h_barcodes, h_barcodes + (size_t)rule->n_samples * (rule->part[0].len + rule->part[1].len));
+    } else { release(ctx->dmx_out); ctx->dmx_codes.clear(); }
+    return SFQ_OK;
+}
+int sfq_get_demux(const sfq_ctx* ctx, sfq_demux_report* report, uint64_t* part_off, uint64_t* part_units, uint64_t cap_entries) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!ctx->dmx_done) { if (report) memset(report, 0, sizeof *report); return 0; }
+    if ((part_off || part_units) && cap_entries < ctx->dmx_off.size()) return SFQ_E_ARG;
+    if (report) *report = ctx->dmx_report;
+    if (part_off) std::copy(ctx->dmx_off.begin(), ctx->dmx_off.end(), part_off);
+    if (part_units) std::copy(ctx->dmx_units.begin(), ctx->dmx_units.end(), part_units);
+    return 1;
+}
+
 int sfq_get_block_index(sfq_ctx* ctx, sfq_block_info* h_blocks, uint32_t cap) {
     if (!ctx || !h_blocks) return SFQ_E_ARG;
     if (cap < ctx->index.size()) return fail(ctx, SFQ_E_ARG, "index has %zu blocks", ctx->index.size());
@@ -3417,7 +3682,7 @@ static int decode_device(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_inf
     Settle settle(ctx);
     drop_encode_blobs(ctx);                             // whatever an encode left behind is not this archive's
     ctx->crcs.clear(); ctx->text_crc = 0;
-    ctx->pair_split_done = false; ctx->pick_done = 0; ctx->sel_done = false; ctx->trim_done = false; ctx->ovl_done = false; ctx->mrg_done = false; ctx->dd_done = false; ctx->scr_done = false;
+    ctx->pair_split_done = false; ctx->pick_done = 0; ctx->sel_done = false; ctx->trim_done = false; ctx->ovl_done = false; ctx->mrg_done = false; ctx->dd_done = false; ctx->scr_done = false; ctx->dmx_done = false;
     if (w.ranged && ctx->pair_split_on && !w.pairs)
         return fail(ctx, SFQ_E_UNSUPPORTED, "a window of blocks may start at a second mate and is not split: sfq_ctx_set_pair_split(ctx, 0) comes first");
     const bool check = ex.set;
@@ -4189,6 +4454,17 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
         if (w.pairs && (ctx->dd.first_record || ctx->dd.n_records != ~0ull))
             return fail(ctx, SFQ_E_ARG, "distinct records: a window of pairs is the range: the rule's own must be (0, UINT64_MAX)");
     }
+    if (ctx->dmx_on) {                                     // the call's last pass, and alone behind the dedup: split_mates is its split
+        if (ctx->mrg_on) return fail(ctx, SFQ_E_ARG, "demultiplexed records: the merge is on as well: the two are not combined");
+        if (ctx->pick_what) return fail(ctx, SFQ_E_ARG, "demultiplexed records: the pick is on as well: the two are not combined");
+        if (ctx->pair_split_on) return fail(ctx, SFQ_E_ARG, "demultiplexed records: the pair split is on as well: split_mates splits every sample's mates");
+        if (w.pairs) return fail(ctx, SFQ_E_ARG, "demultiplexed records: a window of pairs is not combined with the demux");
+        const bool dp = ctx->dmx.pairs != 0;
+        if ((ctx->sel_on && (ctx->sel.pairs != 0) != dp) || (ctx->scr_on && (ctx->scr.pairs != 0) != dp) || (ctx->dd_on && (ctx->dd.pairs != 0) != dp))
+            return fail(ctx, SFQ_E_ARG, "demultiplexed records: the %s in front has pairs %s and the demux pairs %s: the mates would fall out of step",
+                        ctx->sel_on && (ctx->sel.pairs != 0) != dp ? "selection" : ctx->scr_on && (ctx->scr.pairs != 0) != dp ? "screen" : "dedup",
+                        dp ? "== 0" : "!= 0", dp ? "== 1" : "== 0");
+    }
     HIPC(hipSetDevice(ctx->dev));
     int rc;
     // the index is untrusted: every stream's blocks must lie inside the bytes handed over (the device entry point cannot
@@ -4297,6 +4573,21 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
         d_text = (const u8*)ctx->dd_out.p;
         *out_bytes = ctx->dd_report.kept_bytes;
         if (!*out_bytes) return SFQ_OK;                    // nothing kept (the set knew every key): as behind a selection that keeps nothing
+    }
+    if (ctx->dmx_on) {                                     // the last pass: what goes back is the parts, back to back
+        if (!*out_bytes) return fail(ctx, SFQ_E_FORMAT, "demultiplexed records: an empty text");
+        if ((rc = reserve(ctx, ctx->dmx_out, (size_t)*out_bytes + 16))) return rc;
+        const u32 np = (ctx->dmx.split_mates ? 2 : 1) * (ctx->dmx.n_samples + 1);
+        ctx->dmx_off.assign(np + 1, 0); ctx->dmx_units.assign(ctx->dmx.n_samples + 1, 0);
+        Settle settle(ctx);
+        if ((rc = demux_run(ctx, d_text, *out_bytes, ctx->dmx, ctx->dmx_codes.data(), (u8*)ctx->dmx_out.p, *out_bytes, ctx->dmx_off.data(), ctx->dmx_units.data(), &ctx->dmx_report)))
+            return rc;
+        settle.ok = true;
+        ctx->dmx_done = true;
+        *out_bytes = ctx->dmx_report.out_bytes;
+        HIPC(hipMemcpyAsync(h_out, ctx->dmx_out.p, (size_t)*out_bytes, hipMemcpyDeviceToHost, ctx->st));
+        HIPC(hipStreamSynchronize(ctx->st));
+        return SFQ_OK;
     }
     const bool cut = selected || screened || distinct;     // a pass in front has cut the text to a window's pairs
     if (ctx->mrg_on) {

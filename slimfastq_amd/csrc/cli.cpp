@@ -25,8 +25,11 @@
 //   -G terms  : with -d: the reads screened against reference sequences on the GPU -- those that share k-mers with the FASTA files
 //               named by ref=PATH dropped (phiX, adapters, rRNA, a host genome), or with the term keep only those kept (baits); one
 //               set of k-mers in device memory lasts the run; behind -k, in front of -D, merge=, -p and -x
+//   -X terms  : with -d: the reads demultiplexed on the GPU -- sorted by the sample of a sheet whose barcode they carry in the header's
+//               index field or inline, within mm= mismatches, a file a sample (out=PREFIX), the rest to -u (and -p); behind -D, last
 // All model / coder work happens in libslimfastq_amd.so on the GPU; this file parses arguments, reads and
 // writes files and fills the info page.
+#include <sys/resource.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -161,6 +164,16 @@ static void usage() {
            "                   term both, when both mates are.  Behind -c, -o and -k, in front of -D, merge=, -p and -x; under -R / -W only\n"
            "                   the window's records count; goes with -R, -p, -W, -x, -k, -c, -o, -D and -K, not with -s or -b; without\n"
            "                   -q the last line on stderr says what was matched and kept\n"
+           "-X sheet[,terms] : with -d: demultiplex the reads on the GPU before the text comes back.  sheet: a file of lines name<TAB>BARCODE or\n"
+           "                   name<TAB>BARCODE+BARCODE ('#' lines are comments).  out=PREFIX (required): sample files PREFIX<name>.fastq, with\n"
+           "                   -p PREFIX<name>_R1.fastq and _R2.fastq; the units no sample takes go to -u (and -p).  mm=N: mismatches allowed\n"
+           "                   (default 1; a unit whose nearest barcode is not unique is unassigned); hdr (the default): the barcode is the\n"
+           "                   last ':' field of the header, a second part behind its '+'; inline[=POS]: it is in the read's bases at POS (a\n"
+           "                   second part follows it); inline2[=POS]: the second part in the second mate's bases (needs -p); hdr2: the second\n"
+           "                   part in the header's field; clip: inline barcodes are cut from the reads of assigned units; counts=FILE:\n"
+           "                   name<TAB>barcode<TAB>units per sample.  Behind -c, -o, -k, -G and -D, the last pass; goes with -R, -p, -k, -c,\n"
+           "                   -o, -D, -G and -K, not with -x, -W, -o merge=, -s, -b or a -B 0 archive; without -q the last line on stderr\n"
+           "                   says how many units were assigned\n"
            "-M               : with -p on a compress run: compare the names of every pair of mates on the GPU before it is coded (the\n"
            "                   header's first word, without a final /1 or /2); a pair that differs ends the run with its index and both\n"
            "                   names, and no archive is written\n"
@@ -207,6 +220,9 @@ struct Opts {
     std::string ovl_merge;                                             // ... and the merge=PATH: the pairs are merged, not cut
     bool dedup = false;                                                // -D
     bool screen = false; std::string screen_spec; sfq_screen screen_rule; uint32_t screen_k = 27;       // -G terms, and the rule and k they parse to
+    bool demux = false; std::string demux_spec; sfq_demux demux_rule;  // -X terms, and the rule they and the sheet give
+    std::vector<std::string> demux_names; std::vector<uint8_t> demux_codes;       // ... the sheet's samples: names, barcode rows
+    std::string demux_out, demux_counts;                               // ... out=PREFIX, counts=FILE
     std::vector<std::vector<uint8_t>> screen_seqs;                     // ... and the sequence text of every ref=PATH, read before anything is decoded
 };
 // "FIRST:COUNT", both decimal, COUNT > 0
@@ -691,6 +707,8 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     const int version = (int)a.get_long("version", 0);
     if (version > kBlockVersion) croak("%s was compressed with slimfastq version %d. My version is %d. Please upgrade me before decoing", fil.c_str(), version, kBlockVersion);
     const int level = clamp_level((int)a.get_long("config.level", 2));       // config.cpp:359
+    if (o.demux && version < kBlockVersionMin)
+        croak("-X: %s is a format-%d file (-B 0), which decodes on one lane and is not sorted by sample: write the archive in the block format", fil.c_str(), version);
     std::vector<sfq_block_info> blocks;
     std::vector<uint8_t> first;
     std::vector<sfqc::Segment> segs;
@@ -796,7 +814,25 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     p.level = level; p.version = version >= kBlockVersionMin ? kInternalVersion : (uint32_t)version;
     // (a -b worker keeps its context from job to job: a -K encode before this job left the pass on; installed checksums run it)
     if (sfq_ctx_set_checksums(ctx, 0)) croak("%s", sfq_last_error(ctx));
-    if (sfq_ctx_set_pair_split(ctx, paired ? 1 : 0)) croak("%s", sfq_last_error(ctx));
+    if (sfq_ctx_set_pair_split(ctx, paired && !o.demux ? 1 : 0)) croak("%s", sfq_last_error(ctx));      // (-X splits every sample's mates itself)
+    // -X: a file a part, opened now and appended to segment by segment; the unassigned units go to -u (and -p)
+    const bool dmx_pairs = o.demux && (paired || a.get_long("usr.pair", 0) == 1);
+    std::vector<FILE*> dmx_files;
+    std::vector<uint64_t> dmx_units(o.demux_names.size() + 1, 0), dmx_off, dmx_got;
+    sfq_demux_report dmx_sum; memset(&dmx_sum, 0, sizeof dmx_sum);
+    if (sfq_ctx_set_demux(ctx, nullptr, nullptr)) croak("%s", sfq_last_error(ctx));
+    if (o.demux) {
+        for (const std::string& nm : o.demux_names)
+            for (int g = 0; g < (paired ? 2 : 1); g++) {
+                const std::string f = o.demux_out + nm + (paired ? (g ? "_R2" : "_R1") : "") + ".fastq";
+                FILE* h = fopen(f.c_str(), "wb");
+                if (!h) croak("-X: can't write file '%s'", f.c_str());
+                dmx_files.push_back(h);
+            }
+        dmx_files.push_back(of);
+        if (paired) dmx_files.push_back(of2);
+        dmx_off.resize(dmx_files.size() + 1); dmx_got.resize(dmx_files.size() + 1);
+    }
     if (sfq_ctx_set_pick(ctx, o.pick)) croak("%s", sfq_last_error(ctx));
     if (sfq_ctx_set_select(ctx, nullptr)) croak("%s", sfq_last_error(ctx));       // (set per segment: the range and the index base are the segment's)
     uint64_t sel_kept = 0, sel_seen = 0, sel_bytes = 0, sel_text = 0;
@@ -991,6 +1027,25 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
             }
             if (sfq_ctx_set_dedup(ctx, &rule)) croak("-D: %s", sfq_last_error(ctx));
         }
+        if (o.demux) {
+            // the range: the segment's share of -R, as -D's (behind -k, -G or -D the text that they kept)
+            sfq_demux rule = o.demux_rule;
+            rule.pairs = dmx_pairs ? 1 : 0; rule.split_mates = paired ? 1 : 0;
+            const uint64_t text0 = rec0 + sb[w0].first_record;
+            if (o.range && !o.select && !o.screen && !o.dedup) {
+                uint64_t wrecs = 0;
+                for (uint32_t b = w0; b < w0 + wn; b++) wrecs += sb[b].n_records;
+                const uint64_t lo = std::max(r_lo, text0), hi = std::min(r_hi, text0 + wrecs);
+                rule.first_record = lo - text0; rule.n_records = hi - lo;
+            }
+            if (dmx_pairs && !o.select && !o.screen && !o.dedup) {
+                if (text0 & 1) croak("-X: the blocks of %s hold odd numbers of records, so that a decoded text begins at a second mate (record %llu): "
+                                     "pairs are sorted by sample in archives written with an even -B", fil.c_str(), (unsigned long long)text0);
+                if (rule.first_record & 1) croak("-X: -R begins at record %llu, a second mate: the units of an archive written from paired files are pairs, "
+                                                 "and a range begins at a first mate", (unsigned long long)(text0 + rule.first_record));
+            }
+            if (sfq_ctx_set_demux(ctx, &rule, o.demux_codes.data())) croak("-X: %s", sfq_last_error(ctx));
+        }
         sfq_result res;
         int rc = 0;
         uint8_t* dst = nullptr;
@@ -1062,6 +1117,23 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
                 for (size_t i = 0; i <= 2 * SFQ_OVERLAP_MAX_LEN; i++) ovl_sum.insert_hist[i] += rep.insert_hist[i];
             }
         }
+        if (o.demux) {                                                 // the parts, one behind the other: each to its file
+            sfq_demux_report rep;
+            const int had = sfq_get_demux(ctx, &rep, dmx_off.data(), dmx_got.data(), dmx_off.size());       // (0: a pass in front left nothing)
+            if (had < 0) croak("-X: the library did not sort the records");
+            writer.join();
+            if (wbad) croak("USR: Error writing output");
+            if (had == 1) {
+                for (size_t c = 0; c < dmx_files.size(); c++)
+                    if (fwrite(dst + dmx_off[c], 1, (size_t)(dmx_off[c + 1] - dmx_off[c]), dmx_files[c]) != dmx_off[c + 1] - dmx_off[c]) croak("USR: Error writing output");
+                for (size_t i = 0; i < dmx_units.size(); i++) dmx_units[i] += dmx_got[i];
+                dmx_sum.n_units += rep.n_units; dmx_sum.n_assigned += rep.n_assigned; dmx_sum.n_perfect += rep.n_perfect; dmx_sum.n_short += rep.n_short;
+                dmx_sum.n_far += rep.n_far; dmx_sum.n_ambiguous += rep.n_ambiguous; dmx_sum.bases_clipped += rep.bases_clipped;
+            }
+            tick("write output");
+            b0 += g.nblocks; pri_off += g.prior_bytes; chn_off += g.chain_bytes; rpr_off += g.recpri_bytes;
+            continue;
+        }
         if (o.range && !o.select && !merging && !o.dedup && !o.screen) {                        // the window's first and last block, cut to records: rec_lines lines each
             const uint64_t wrec0 = rec0 + (uint64_t)w0 * sb[0].n_records;
             const uint64_t lo = std::max(r_lo, wrec0), hi = std::min(r_hi, wrec0 + res.n_records);
@@ -1089,6 +1161,25 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     }
     writer.join();
     if (wbad) croak("USR: Error writing output");
+    if (o.demux) {
+        if (sfq_ctx_set_demux(ctx, nullptr, nullptr)) croak("%s", sfq_last_error(ctx));
+        for (size_t c = 0; c < o.demux_names.size() * (paired ? 2 : 1); c++) if (fclose(dmx_files[c])) croak("-X: error writing a sample's file");
+        if (!o.demux_counts.empty()) {
+            FILE* cf = fopen(o.demux_counts.c_str(), "w");
+            if (!cf) croak("-X counts=%s: can't write the file", o.demux_counts.c_str());
+            const size_t B = o.demux_rule.part[0].len + o.demux_rule.part[1].len, l0 = o.demux_rule.part[0].len;
+            for (size_t s = 0; s < o.demux_names.size(); s++) {
+                const std::string code((const char*)o.demux_codes.data() + s * B, B);
+                fprintf(cf, "%s\t%s%s%s\t%llu\n", o.demux_names[s].c_str(), code.substr(0, l0).c_str(), B > l0 ? "+" : "", code.substr(l0).c_str(), (unsigned long long)dmx_units[s]);
+            }
+            fprintf(cf, "unassigned\t\t%llu\n", (unsigned long long)dmx_units.back());
+            if (fclose(cf)) croak("-X counts=%s: error writing the file", o.demux_counts.c_str());
+        }
+        if (!o.quiet)
+            fprintf(stderr, "demultiplexed %llu %s: %llu assigned (%llu perfect), %llu short, %llu far, %llu ambiguous\n", (unsigned long long)dmx_sum.n_units,
+                    dmx_pairs ? "pairs" : "reads", (unsigned long long)dmx_sum.n_assigned, (unsigned long long)dmx_sum.n_perfect, (unsigned long long)dmx_sum.n_short,
+                    (unsigned long long)dmx_sum.n_far, (unsigned long long)dmx_sum.n_ambiguous);
+    }
     if (of != stdout) fclose(of); else fflush(stdout);
     if (of2) fclose(of2);
     if (of3 && fclose(of3)) croak("-o merge=%s: error writing the file", o.ovl_merge.c_str());
@@ -1139,7 +1230,7 @@ int main(int argc, char** argv) {
     Opts o;
     bool statistics = false;
     if (argc == 1) usage();
-    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKYMD1234u:f:l:B:g:S:T:C:t:R:Q:p:W:x:k:c:o:G:")) != -1;) {
+    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKYMD1234u:f:l:B:g:S:T:C:t:R:Q:p:W:x:k:c:o:G:X:")) != -1;) {
         switch (opt) {
         case 'u': g_usr = optarg; break;
         case 'f': fil = optarg; break;
@@ -1183,6 +1274,7 @@ int main(int argc, char** argv) {
         case 'o': o.ovl = true; o.ovl_spec = optarg; break;
         case 'D': o.dedup = true; break;
         case 'G': o.screen = true; o.screen_spec = optarg; break;
+        case 'X': o.demux = true; o.demux_spec = optarg; break;
         case 'C': o.chain_reads = strtol(optarg, 0, 0); break;
         case 't': o.io_threads = std::min(64, std::max(1, atoi(optarg))); break;
         case 'v': printf("Version %s\nInternal format version=%u (block format %u)\n", kUserVersion, kInternalVersion, kBlockVersion); exit(0);
@@ -1342,6 +1434,78 @@ int main(int argc, char** argv) {
         fprintf(stderr, "slimfastq: -D (distinct records) goes with -d: it drops the duplicates of what a decode writes%s\n",
                 statistics ? "; -s writes no text" : g_batch ? "; it does not go with -b" : "");
         return 1;
+    }
+
+    if (o.demux) {
+        // the sheet (the first term) and the file terms are the CLI's own: the library checks the others (and skips these)
+        char err[256] = "";
+        if (g_encode || statistics || g_batch) {
+            fprintf(stderr, "slimfastq: -X (demultiplexed records) goes with -d: it sorts the records a decode writes by sample%s\n",
+                    statistics ? "; -s writes no text" : g_batch ? "; it does not go with -b" : "");
+            return 1;
+        }
+        if (o.pick || o.window || !o.ovl_merge.empty()) {
+            fprintf(stderr, "slimfastq: -X (demultiplexed records) does not go with %s\n", o.pick ? "-x: the sample files are whole records" :
+                    o.window ? "-W: a window of pairs is not sorted by sample" : "-o merge=: merged pairs are not sorted by sample");
+            return 1;
+        }
+        if (sfq_demux_parse(o.demux_spec.c_str(), &o.demux_rule, err, sizeof err)) {
+            fprintf(stderr, "slimfastq: -X %s: %s\n", o.demux_spec.c_str(), err[0] ? err : "not a list of terms");
+            return 1;
+        }
+        std::string sheet;
+        for (size_t at = 0, i = 0; at <= o.demux_spec.size(); i++) {
+            const size_t comma = std::min(o.demux_spec.find(',', at), o.demux_spec.size());
+            const std::string term = o.demux_spec.substr(at, comma - at);
+            at = comma + 1;
+            if (!i) sheet = term;
+            else if (term.compare(0, 4, "out=") == 0) o.demux_out = term.substr(4);
+            else if (term.compare(0, 7, "counts=") == 0) o.demux_counts = term.substr(7);
+        }
+        if (o.demux_out.empty()) { fprintf(stderr, "slimfastq: -X %s: names no sample files (out=PREFIX)\n", o.demux_spec.c_str()); return 1; }
+        FILE* sf = fopen(sheet.c_str(), "rb");
+        if (!sf) { fprintf(stderr, "slimfastq: -X: can't read the sample sheet '%s'\n", sheet.c_str()); return 1; }
+        std::string text;
+        char buf[1 << 16];
+        for (size_t got; (got = fread(buf, 1, sizeof buf, sf)) > 0; ) text.append(buf, got);
+        fclose(sf);
+        std::vector<char> names((size_t)SFQ_DEMUX_MAX_SAMPLES * 65);
+        o.demux_codes.resize((size_t)SFQ_DEMUX_MAX_SAMPLES * 32);
+        uint32_t ns = 0, l0 = 0, l1 = 0;
+        if (sfq_demux_sheet(text.data(), text.size(), SFQ_DEMUX_MAX_SAMPLES, names.data(), o.demux_codes.data(), &ns, &l0, &l1, err, sizeof err)) {
+            fprintf(stderr, "slimfastq: -X %s: %s\n", sheet.c_str(), err);
+            return 1;
+        }
+        for (uint32_t i = 0; i < ns; i++) o.demux_names.push_back(names.data() + (size_t)i * 65);
+        sfq_demux& d = o.demux_rule;
+        d.n_samples = ns;
+        d.part[0].len = l0;
+        if (l1 && d.part[1].src == 0) d.part[1] = sfq_demux_part{ SFQ_DEMUX_BASES, 0, 0, d.part[0].pos + l0, 0 };      // inline alone: part 1 follows part 0
+        d.part[1].len = l1;
+        const bool paired = !o.pair.empty();
+        if (d.part[1].len && d.part[1].mate && !paired) { fprintf(stderr, "slimfastq: -X inline2 reads the second mates: it needs -p\n"); return 1; }
+        d.pairs = paired ? 1 : 0; d.split_mates = d.pairs;
+        if (sfq_demux_check(&d, o.demux_codes.data())) {
+            fprintf(stderr, "slimfastq: -X %s: the library refuses the rule (mm=%u with barcodes of %u bases?)\n", o.demux_spec.c_str(), d.max_mm, l0 + l1);
+            return 1;
+        }
+        d.pairs = 0;                                                   // (decided per archive: units are pairs where -D's are)
+        // the files: two a sample with -p, the unassigned ones' (-u, -p), the counts
+        struct rlimit rl;
+        const unsigned long long files = (unsigned long long)ns * (paired ? 2 : 1) + (paired ? 2 : 1) + (o.demux_counts.empty() ? 0 : 1);
+        if (getrlimit(RLIMIT_NOFILE, &rl) == 0 && rl.rlim_cur != RLIM_INFINITY && files + 16 > (unsigned long long)rl.rlim_cur) {
+            fprintf(stderr, "slimfastq: -X: %llu files are more than this process may hold open (%llu, of which 16 are kept back): raise the limit (ulimit -n)\n",
+                    files, (unsigned long long)rl.rlim_cur);
+            return 1;
+        }
+        if (!o.overwrite) {
+            std::vector<std::string> all;
+            for (const std::string& nm : o.demux_names)
+                for (int g = 0; g < (paired ? 2 : 1); g++) all.push_back(o.demux_out + nm + (paired ? (g ? "_R2" : "_R1") : "") + ".fastq");
+            if (!o.demux_counts.empty()) all.push_back(o.demux_counts);
+            for (const std::string& f : all)
+                if (access(f.c_str(), F_OK) == 0) { fprintf(stderr, "Can't write file '%s': File exists\n", f.c_str()); return 1; }
+        }
     }
 
     if (!o.pair.empty() && g_batch) {

@@ -531,3 +531,39 @@ void launch_screen_add(const u8* seq, u64 n, const ScrSetDev& S, u64 max_kmers, 
 // t.starts is not used; info: zeroed by the caller.  out: job.out_cap bytes, of which info->copy.nout are written, and none unless
 // info->status and info->copy.status stay 0.  The set is never written.
 void launch_screen(const PairText& t, const ScrArrays& A, const ScrJob& job, const ScrSetDev& S, u32 lanes, u8* out, ScrInfo* info, hipStream_t st);
+
+// Demultiplexed records (dmx.hip): the units (records; under pairs, pairs) of [r0, r0 + nr) sorted STABLY into NP parts by the sample
+// whose barcode the unit's observed bytes match (slimfastq_amd.h "demultiplexed records"), the parts back to back.  Like dd.hip the
+// pass finds the lines itself, decides every refusal on the device and copies with pick.hip's copy; what is new is the classifier and
+// the stable multi-way partition, an LSD radix sort of the records by class over digits of 8 bits.
+enum DmxStatus : u32 {
+    DMX_OK = 0,
+    DMX_LINES,              // the text's lines are no multiple of four
+    DMX_END,                // the text does not end in '\n'
+    DMX_RANGE,              // records that end behind the text's last record
+    DMX_ODD,                // pairs: an odd number of records in the range
+    DMX_CAP,                // more records than the arrays hold: info->recs says how many, nothing else was done
+    DMX_LONG,               // a record of 4 GiB or more
+    DMX_CLIP,               // clip: a record of the range whose lines 2 and 4 differ in length: info->bad_first, bad_off
+    DMX_ROOM                // the parts need more than the output holds: info->copy.nout says how much
+};
+constexpr u32 DMX_TILE = 1024;                                 // records a workgroup ranks in one digit pass
+constexpr u32 DMX_MAX_SAMPLES = 4096;
+struct DmxPart { u32 src, mate, sub, pos, len; };              // sfq_demux_part
+// copy: what k_pick_copy reads, as SelInfo's.  units: the range's; the verdicts' counts; bad_first: the smallest record the clip refuses
+struct DmxInfo { PickInfo copy; u64 lines, recs, r0, nr; u32 status, pad; u64 units, n_assigned, n_perfect, n_short, n_far, n_ambiguous, bad_first, bad_off; };
+// np: the parts, n_samples + 1 or twice that with split; clip0, clip1: what an assigned unit's mate 0 and mate 1 lose in front (0 without clip)
+struct DmxJob { u64 r0, nr, out_cap; u32 pairs, split, max_mm, clip, n_samples, np, clip0, clip1; DmxPart part[2]; };
+// ls[4 cap + 1] as SelArrays'; codes[n_samples]: the barcodes, two bits a base ((byte >> 1) & 3), base i in bits 2 i, 2 i + 1; cls[nlens]:
+// the class of every record of the range; ord_a, ord_b[nlens]: the records (counted from r0) sorted by the class's low digit, by the
+// class; hist[256 ntiles], hoff one more: the digit counts of every tile, DIGIT-major, and their scan; cnt[nlens], at[nlens + 1] (clip
+// alone): the pieces of the record at every sorted position and their scan; lens, from: pcap entries (pcap = nlens, with clip 3 nlens),
+// dst one more; tmp as launch_scan_u32 wants it for max(pcap, 256 ntiles); bounds[2 (np + 1)]: part_off[np + 1], then for every
+// part the sorted position of its first record (np + 1 entries, the last = nr); ntiles = ceil(nlens / DMX_TILE), nlens = min(nr, cap)
+struct DmxArrays {
+    u64* ls; const u64* codes; u32* cls; u64* ord_a; u64* ord_b; u32* hist; u64* hoff; u32* cnt; u64* at; u32* lens; u64* from; u64* dst; u64* tmp; u64* bounds;
+    u64 cap, nlens, ucap, ntiles, pcap;
+};
+// t.starts is not used; info: zeroed by the caller.  out: job.out_cap bytes, of which info->copy.nout are written, and none unless
+// info->status and info->copy.status stay 0.
+void launch_demux(const PairText& t, const DmxArrays& A, const DmxJob& job, u8* out, DmxInfo* info, hipStream_t st);
