@@ -1048,6 +1048,50 @@ int sfq_ctx_set_demux(sfq_ctx* ctx, const sfq_demux* rule, const uint8_t* h_barc
  * leaves no message and sfq_last_error keeps what it said before. */
 int sfq_get_demux(const sfq_ctx* ctx, sfq_demux_report* report, uint64_t* part_off, uint64_t* part_units, uint64_t cap_entries);
 
+/* ---- BGZF: blocked gzip, deflated on the GPU (bgz.hip) --------------------------
+ * A text in device memory as BGZF (the SAM specification's blocked gzip, what bgzip writes): a plain concatenation of gzip members,
+ * which every gzip reader reads.  The text is given in parts, as sfq_crc32 takes its ranges; every part is cut into pieces of
+ * SFQ_BGZF_PIECE bytes (the last may be shorter), a piece is one member, and no member crosses a part's bound -- the result can be cut
+ * where the parts meet.  A part of zero bytes has no member.  A member is 18 header bytes (1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6,
+ * 'B' 'C' 02 00, BSIZE = the member's size - 1), one raw deflate stream -- one dynamic-Huffman block over an LZ77 parse of the piece, or
+ * one stored block where that would be larger than the piece + 5 bytes -- the piece's CRC-32 and its size.  The same piece gives the
+ * same member whatever else the call holds and wherever the piece lies in memory.  The pass writes no end-of-file block: a file ends
+ * with sfq_bgzf_eof's 28 bytes, written once by whoever closes it. */
+#define SFQ_BGZF_PIECE 65280
+typedef struct sfq_bgzf_report {
+    uint64_t text_bytes;       /* the text's */
+    uint64_t out_bytes;        /* the result's; on SFQ_E_OVERFLOW the size needed */
+    uint64_t members;
+    uint64_t stored_members;   /* of them, those that hold a stored block */
+} sfq_bgzf_report;
+/* what the members of n bytes of text in n_parts parts hold at most: n + 31 * (n / 65280 + n_parts) */
+uint64_t sfq_bgzf_bound(uint64_t n, uint32_t n_parts);
+/* the specification's empty member, which ends a file; returns 28 */
+int sfq_bgzf_eof(uint8_t out[28]);
+/* Part i of the text is d_text[h_bounds[i], h_bounds[i + 1]), i < n_parts; part i of the result is d_out[h_part_off[i],
+ * h_part_off[i + 1]).  The contract is sfq_pick_lines': any alignment of d_text and d_out; SFQ_E_ARG for a null pointer, n_parts == 0
+ * or decreasing bounds; SFQ_E_OVERFLOW with the size needed in report->out_bytes where the result exceeds out_cap, decided before
+ * anything is written to d_out; a successful call writes d_out[0, report->out_bytes) and nothing else; d_out must not overlap the
+ * text; one synchronise; reads may extend to the aligned 16-byte units of the text's ends.  A text of zero bytes is fine: no member,
+ * every offset 0.  report may be NULL. */
+int sfq_bgzf_deflate(sfq_ctx* ctx, const uint8_t* d_text, const uint64_t* h_bounds, uint32_t n_parts, uint8_t* d_out, uint64_t out_cap,
+                     uint64_t* h_part_off /* n_parts + 1 */, sfq_bgzf_report* report);
+/* on != 0: sfq_decode_blocks_host, sfq_decode_block_range_host and sfq_decode_pair_range_host hand back BGZF bytes instead of text.
+ * It is the call's last pass, behind everything, the pick and the demultiplexing included, and its parts are what that exit has: one
+ * text; first mates | second mates; merged | rest (the rest's mates split: three parts); the demultiplexing's parts.  Every byte
+ * offset into the returned buffer -- *split, sfq_get_pair_split's first_bytes, sfq_get_demux's part_off, sfq_get_merge's merged_bytes --
+ * becomes an offset into the compressed result; record and unit counts do not change, and checksums stay those of the decoded text.
+ * out_cap keeps sizing the decoded text; a result larger than out_cap (text that does not compress) is SFQ_E_OVERFLOW with the size
+ * needed in *out_bytes.  A call whose passes keep nothing returns 0 bytes, as without the switch.  While it is on the context holds a
+ * device buffer of 65536 bytes per member (1.004 bytes per byte of text) and the tokens' buffer (four bytes per byte of the pieces in
+ * flight, 134 MB on a 256-CU device whatever the text's size).  The device-pointer decode entries are not affected.  Default off:
+ * nothing is launched, allocated or copied that is not today. */
+int sfq_ctx_set_bgzf(sfq_ctx* ctx, int on);
+/* 1: the last decode call deflated: *report (may be NULL), part_off[0 .. NP] = the parts' offsets in the returned bytes and
+ * text_part_bytes[0 .. NP) = the text-side sizes of the same parts (either may be NULL), where cap >= NP + 1; 0: it did not (*report
+ * zeroed).  SFQ_E_ARG for a null context and for a cap below NP + 1 with either array given. */
+int sfq_get_bgzf(const sfq_ctx* ctx, sfq_bgzf_report* report, uint64_t* part_off, uint64_t* text_part_bytes, uint64_t cap);
+
 /* ---- the ".sfq" container (host only) ----------------------------------------------------------
  * Replaces FilerSave + the info page (filer.cpp:217-242, config.cpp:334-347) for hosts that assemble an archive
  * themselves: info_text is the info page ("key=value\n" lines), then n_streams named byte streams (names of at most

@@ -49,6 +49,7 @@ EXPORTS = [
     "sfq_screen_check", "sfq_screen_parse", "sfq_fasta_sequences", "sfq_screen_set_create", "sfq_screen_set_add", "sfq_screen_set_clear",
     "sfq_screen_set_destroy", "sfq_screen_set_info", "sfq_screen_records", "sfq_ctx_set_screen", "sfq_get_screen",
     "sfq_demux_check", "sfq_demux_parse", "sfq_demux_sheet", "sfq_demux_records", "sfq_ctx_set_demux", "sfq_get_demux",
+    "sfq_bgzf_bound", "sfq_bgzf_eof", "sfq_bgzf_deflate", "sfq_ctx_set_bgzf", "sfq_get_bgzf",
 ]
 
 
@@ -236,6 +237,27 @@ class DemuxReport(C.Structure):
     _fields_ = [("n_in_range", C.c_uint64), ("n_units", C.c_uint64), ("n_assigned", C.c_uint64), ("n_perfect", C.c_uint64),
                 ("n_short", C.c_uint64), ("n_far", C.c_uint64), ("n_ambiguous", C.c_uint64), ("text_bytes", C.c_uint64),
                 ("out_bytes", C.c_uint64), ("bases_clipped", C.c_uint64)]
+
+
+BGZF_PIECE = 65280
+
+
+class BgzfReport(C.Structure):
+    """sfq_bgzf_report: what a BGZF pass wrote."""
+    _fields_ = [("text_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("members", C.c_uint64), ("stored_members", C.c_uint64)]
+
+
+def bgzf_bound(n, n_parts=1) -> int:
+    """sfq_bgzf_bound (no GPU): what the members of n bytes of text in n_parts parts hold at most."""
+    return int(lib().sfq_bgzf_bound(int(n), int(n_parts)))
+
+
+def bgzf_eof() -> bytes:
+    """sfq_bgzf_eof (no GPU): the 28 bytes that end a BGZF file."""
+    buf = C.create_string_buffer(28)
+    if lib().sfq_bgzf_eof(buf) != 28:
+        raise SfqError(E_ARG, "sfq_bgzf_eof")
+    return buf.raw
 
 
 def _barcode_rows(barcodes, rule=None) -> bytes:
@@ -558,6 +580,12 @@ def lib():
         L.sfq_demux_records.argtypes = [vp, vp, u64, C.POINTER(Demux), C.c_char_p, vp, u64, u64p, u64p, u64p, C.POINTER(DemuxReport)]
         L.sfq_ctx_set_demux.argtypes = [vp, C.POINTER(Demux), C.c_char_p]
         L.sfq_get_demux.argtypes = [vp, C.POINTER(DemuxReport), u64p, u64p, u64]
+        L.sfq_bgzf_bound.restype = C.c_uint64
+        L.sfq_bgzf_bound.argtypes = [u64, C.c_uint32]
+        L.sfq_bgzf_eof.argtypes = [C.c_char_p]
+        L.sfq_bgzf_deflate.argtypes = [vp, vp, u64p, C.c_uint32, vp, u64, u64p, C.POINTER(BgzfReport)]
+        L.sfq_ctx_set_bgzf.argtypes = [vp, C.c_int]
+        L.sfq_get_bgzf.argtypes = [vp, C.POINTER(BgzfReport), u64p, u64p, u64]
         _lib = L
     return _lib
 
@@ -1106,6 +1134,45 @@ class Context:
         if rc < 0:
             self._check(rc)
         return rep if rc == 1 else None
+
+    def bgzf_deflate(self, d_text, bounds, d_out, out_cap):
+        """The parts [bounds[i], bounds[i + 1]) of the device buffer at d_text as BGZF members into the one at d_out
+        (sfq_bgzf_deflate); returns (part offsets [n_parts + 1], BgzfReport).  bounds: at least two non-decreasing integers, a
+        ValueError otherwise.  An SfqError of code E_OVERFLOW carries the size needed as .needed."""
+        bounds = [int(x) for x in bounds]
+        if len(bounds) < 2:
+            raise ValueError("bounds: %d entries, a part has two" % len(bounds))
+        if any(b < 0 for b in bounds) or any(b < a for a, b in zip(bounds, bounds[1:])):
+            raise ValueError("bounds: negative or decreasing")
+        n = len(bounds) - 1
+        b = (C.c_uint64 * (n + 1))(*bounds)
+        off, rep = (C.c_uint64 * (n + 1))(), BgzfReport()
+        rc = lib().sfq_bgzf_deflate(self._h, C.c_void_p(d_text), b, n, C.c_void_p(d_out), int(out_cap), off, C.byref(rep))
+        try:
+            self._check(rc)
+        except SfqError as e:
+            e.needed = int(rep.out_bytes)
+            raise
+        return list(off), rep
+
+    def set_bgzf(self, on=True):
+        """decode_host, decode_range_host and decode_pair_range_host return BGZF bytes instead of text, as the call's last pass
+        (get_bgzf() says where the parts lie); False: off."""
+        self._check(lib().sfq_ctx_set_bgzf(self._h, int(bool(on))))
+
+    def get_bgzf(self, max_parts=8200):
+        """(BgzfReport, part offsets [NP + 1], text bytes per part [NP]) of the last decode call; None where it did not deflate."""
+        rep, cap = BgzfReport(), int(max_parts) + 1
+        off, text = (C.c_uint64 * cap)(), (C.c_uint64 * cap)()
+        for i in range(cap):
+            off[i] = 0xFFFFFFFFFFFFFFFF
+        rc = lib().sfq_get_bgzf(self._h, C.byref(rep), off, text, cap)
+        if rc < 0:
+            self._check(rc)
+        if rc != 1:
+            return None
+        np_ = next((i for i in range(cap) if off[i] == 0xFFFFFFFFFFFFFFFF), cap) - 1
+        return rep, list(off)[:np_ + 1], list(text)[:np_]
 
     def set_block_checksums(self, crcs):
         """The expected CRCs of the next decode call's blocks (consumed by it)."""

@@ -242,6 +242,11 @@ struct sfq_ctx {
     bool dmx_on = false; sfq_demux dmx{}; std::vector<u8> dmx_codes;      // sfq_ctx_set_demux: the rule and its barcode rows
     DevBuf dmx_out;                                   // the partitioned text of a decoded one (while the switch is on)
     bool dmx_done = false; sfq_demux_report dmx_report{}; std::vector<u64> dmx_off, dmx_units;   // the last decode call's
+    // BGZF members (bgz.hip): nothing of this exists until sfq_bgzf_deflate is called or the switch is on
+    bool bgz_on = false;                              // sfq_ctx_set_bgzf
+    DevBuf bgz_slots, bgz_toks, bgz_work, bgz_out;    // the members' slots, the tokens, the pass's arrays; the decode entries' result
+    void* bgz_pin = nullptr; size_t bgz_pin_cap = 0;  // the PickInfo, the stored members' count and the members' offsets on their way out
+    bool bgz_done = false; sfq_bgzf_report bgz_report{}; std::vector<u64> bgz_off, bgz_text;     // the last decode call's
     u32 scr_lanes = 8;                                // k_scr_count's lanes a record (SFQ_SCR_LANES: profiles/screen_pass.py's layout comparison)
 };
 
@@ -1007,7 +1012,8 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
         &ctx->oflags, &ctx->okbytes, &ctx->ofpos, &ctx->okoff, &ctx->ofilt, &ctx->orecmap, &ctx->olist, &ctx->line_off_o, &ctx->ono, &ctx->opiece,
         &ctx->otxt[0], &ctx->otxt[1], &ctx->otxt[2], &ctx->osize_all, &ctx->oroff_all, &ctx->oroff_k, &ctx->ocnt,
         &ctx->crc_tab, &ctx->crc_tiles, &ctx->crc_grps, &ctx->crc_bounds, &ctx->crc_out, &ctx->stats_acc, &ctx->qmap_dev,
-        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out, &ctx->pick_out, &ctx->sel_out, &ctx->trim_out, &ctx->ovl_out, &ctx->mrg_out, &ctx->dd_out, &ctx->scr_out, &ctx->dmx_out };
+        &ctx->pair_work, &ctx->pair_in, &ctx->pair_out, &ctx->pick_out, &ctx->sel_out, &ctx->trim_out, &ctx->ovl_out, &ctx->mrg_out, &ctx->dd_out, &ctx->scr_out, &ctx->dmx_out,
+        &ctx->bgz_slots, &ctx->bgz_toks, &ctx->bgz_work, &ctx->bgz_out };
     for (DevBuf* b : all) release(*b);
     (void)sfq_dedup_set_destroy(ctx);
     (void)sfq_screen_set_destroy(ctx);
@@ -1019,6 +1025,7 @@ void sfq_ctx_destroy(sfq_ctx* ctx) {
     if (ctx->stats_pin) (void)hipHostFree(ctx->stats_pin);
     if (ctx->qmap_pin) (void)hipHostFree(ctx->qmap_pin);
     if (ctx->pair_pin) (void)hipHostFree(ctx->pair_pin);
+    if (ctx->bgz_pin) (void)hipHostFree(ctx->bgz_pin);
     for (auto& e : ctx->stats_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->st_stats) (void)hipStreamDestroy(ctx->st_stats);
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
@@ -3682,7 +3689,7 @@ static int decode_device(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_inf
     Settle settle(ctx);
     drop_encode_blobs(ctx);                             // whatever an encode left behind is not this archive's
     ctx->crcs.clear(); ctx->text_crc = 0;
-    ctx->pair_split_done = false; ctx->pick_done = 0; ctx->sel_done = false; ctx->trim_done = false; ctx->ovl_done = false; ctx->mrg_done = false; ctx->dd_done = false; ctx->scr_done = false; ctx->dmx_done = false;
+    ctx->pair_split_done = false; ctx->pick_done = 0; ctx->sel_done = false; ctx->trim_done = false; ctx->ovl_done = false; ctx->mrg_done = false; ctx->dd_done = false; ctx->scr_done = false; ctx->dmx_done = false; ctx->bgz_done = false;
     if (w.ranged && ctx->pair_split_on && !w.pairs)
         return fail(ctx, SFQ_E_UNSUPPORTED, "a window of blocks may start at a second mate and is not split: sfq_ctx_set_pair_split(ctx, 0) comes first");
     const bool check = ex.set;
@@ -4402,6 +4409,92 @@ static int decode_body(sfq_ctx* ctx, const sfq_params* pp, const sfq_block_info*
     return SFQ_OK;
 }
 
+// ---- BGZF members (bgz.hip) ---------------------------------------------------------------------------------------------------------
+// One pass on the context's stream, one synchronise: the parts [hb[i], hb[i + 1]) of a device text cut into members, crc.hip's range
+// pass over the members' pieces, the deflater, the scan of the sizes, pick.hip's copy into out.  part_off[i]: where part i's first
+// member went (part_off[n_parts] = the result's bytes).
+static int bgzf_run(sfq_ctx* ctx, const u8* text, const u64* hb, u32 n_parts, u8* out, u64 out_cap, u64* part_off, sfq_bgzf_report* rep) {
+    std::vector<u64> mb(1, hb[0]);
+    std::vector<u64> first((size_t)n_parts + 1);
+    for (u32 i = 0; i < n_parts; i++) {
+        first[i] = mb.size() - 1;
+        for (u64 a = hb[i]; a < hb[i + 1]; a += SFQ_BGZF_PIECE) mb.push_back(std::min<u64>(a + SFQ_BGZF_PIECE, hb[i + 1]));
+    }
+    first[n_parts] = mb.size() - 1;
+    const u64 M64 = mb.size() - 1;
+    memset(rep, 0, sizeof *rep);
+    rep->text_bytes = hb[n_parts] - hb[0];
+    for (u32 i = 0; i <= n_parts; i++) part_off[i] = 0;
+    if (!M64) return SFQ_OK;
+    if (M64 >> 31) return fail(ctx, SFQ_E_UNSUPPORTED, "bgzf: %llu members in one call", (unsigned long long)M64);
+    const u32 M = (u32)M64;
+    int rc;
+    if ((rc = crc_reserve(ctx, text, hb[0], hb[n_parts], M))) return rc;
+    const u32 wgs = bgz_workgroups(M, ctx->wave_slots / 32);
+    if ((rc = reserve(ctx, ctx->bgz_toks, (size_t)bgz_token_bytes(wgs)))) return rc;
+    if ((rc = reserve(ctx, ctx->bgz_slots, (size_t)bgz_slot_bytes(M)))) return rc;
+    auto up = [](u64 v) { return (v + 15) & ~15ull; };
+    const u64 head = up(sizeof(PickInfo)) + 16;                // the PickInfo, then the stored members' count
+    u64 at = head;
+    const u64 msize = at; at += up((u64)M * 4);
+    const u64 from = at; at += up((u64)M * 8);
+    const u64 dst = at; at += up(((u64)M + 1) * 8);
+    const u64 tmp = at; at += up(((u64)M / 1024 + 2) * 8);
+    if ((rc = reserve(ctx, ctx->bgz_work, (size_t)at))) return rc;
+    if ((rc = reserve_pinned_buf(ctx, ctx->bgz_pin, ctx->bgz_pin_cap, (size_t)(head + ((u64)M + 1) * 8)))) return rc;
+    u8* w = (u8*)ctx->bgz_work.p;
+    PickInfo* info = (PickInfo*)w;
+    u32* n_stored = (u32*)(w + up(sizeof(PickInfo)));
+    HIPC(hipMemsetAsync(w, 0, (size_t)head, ctx->st));
+    HIPC(hipMemcpyAsync(ctx->crc_bounds.p, mb.data(), ((size_t)M + 1) * 8, hipMemcpyHostToDevice, ctx->st));
+    launch_crc32(text, (const u64*)ctx->crc_bounds.p, M, 0, hb[0], hb[n_parts], (u32*)ctx->crc_tiles.p, (u32*)ctx->crc_grps.p, (u32*)ctx->crc_out.p,
+                 (const u32*)ctx->crc_tab.p, ctx->st);
+    launch_bgz_deflate(text, (const u64*)ctx->crc_bounds.p, M, (const u32*)ctx->crc_out.p, wgs, (u32*)ctx->bgz_toks.p, (u8*)ctx->bgz_slots.p, (u32*)(w + msize),
+                       (u64*)(w + from), (u64*)(w + dst), (u64*)(w + tmp), n_stored, out_cap, out, info, ctx->st);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(ctx->bgz_pin, w, (size_t)head, hipMemcpyDeviceToHost, ctx->st));
+    HIPC(hipMemcpyAsync((u8*)ctx->bgz_pin + head, w + dst, ((size_t)M + 1) * 8, hipMemcpyDeviceToHost, ctx->st));
+    HIPC(hipStreamSynchronize(ctx->st));
+    PickInfo got;
+    memcpy(&got, ctx->bgz_pin, sizeof got);
+    u32 stored;
+    memcpy(&stored, (const u8*)ctx->bgz_pin + up(sizeof(PickInfo)), 4);
+    rep->out_bytes = got.nout; rep->members = M; rep->stored_members = stored;
+    if (got.status == PICK_ROOM) return fail(ctx, SFQ_E_OVERFLOW, "bgzf: the result needs %llu bytes", (unsigned long long)got.nout);
+    if (got.status) return fail(ctx, SFQ_E_HIP, "bgzf: status %u", got.status);
+    const u64* d = (const u64*)((const u8*)ctx->bgz_pin + head);
+    for (u32 i = 0; i <= n_parts; i++) part_off[i] = d[first[i]];
+    return SFQ_OK;
+}
+// The decode entries' last pass: the groups' parts -- a group is one device text and the bounds of its parts -- as BGZF, one group's
+// members behind the other's, into h_out.  Leaves the parts' offsets and text sizes in the context (sfq_get_bgzf).
+struct BgzGroup { const u8* p; std::vector<u64> bounds; };
+static int bgzf_finish(sfq_ctx* ctx, const BgzGroup* g, int ng, u8* h_out, u64 out_cap, u64* out_bytes) {
+    u64 text = 0; u32 np = 0;
+    for (int i = 0; i < ng; i++) { text += g[i].bounds.back() - g[i].bounds.front(); np += (u32)g[i].bounds.size() - 1; }
+    const u64 room = sfq_bgzf_bound(text, np);
+    int rc;
+    if ((rc = reserve(ctx, ctx->bgz_out, (size_t)room + 16))) return rc;
+    ctx->bgz_off.assign(1, 0); ctx->bgz_text.clear();
+    sfq_bgzf_report sum{};
+    Settle settle(ctx);
+    for (int i = 0; i < ng; i++) {
+        const u32 n = (u32)g[i].bounds.size() - 1;
+        std::vector<u64> off((size_t)n + 1);
+        sfq_bgzf_report rep;
+        if ((rc = bgzf_run(ctx, g[i].p, g[i].bounds.data(), n, (u8*)ctx->bgz_out.p + sum.out_bytes, room - sum.out_bytes, off.data(), &rep))) return rc;
+        for (u32 k = 0; k < n; k++) { ctx->bgz_off.push_back(sum.out_bytes + off[k + 1]); ctx->bgz_text.push_back(g[i].bounds[k + 1] - g[i].bounds[k]); }
+        sum.text_bytes += rep.text_bytes; sum.out_bytes += rep.out_bytes; sum.members += rep.members; sum.stored_members += rep.stored_members;
+    }
+    settle.ok = true;
+    *out_bytes = sum.out_bytes;
+    if (sum.out_bytes > out_cap) return fail(ctx, SFQ_E_OVERFLOW, "bgzf: the result needs %llu bytes, the output holds %llu", (unsigned long long)sum.out_bytes, (unsigned long long)out_cap);
+    HIPC(hipMemcpyAsync(h_out, ctx->bgz_out.p, (size_t)sum.out_bytes, hipMemcpyDeviceToHost, ctx->st));
+    HIPC(hipStreamSynchronize(ctx->st));
+    ctx->bgz_report = sum; ctx->bgz_done = true;               // (only a call that handed the bytes back has deflated)
+    return SFQ_OK;
+}
+
 static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_info* h_blocks, uint32_t n_blocks,
                        const uint8_t* h_first_hdrs, uint64_t first_hdr_bytes,
                        const uint8_t* h_streams, uint64_t streams_bytes, const uint64_t stream_offset[SFQ_NSTREAMS],
@@ -4585,6 +4678,12 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
         settle.ok = true;
         ctx->dmx_done = true;
         *out_bytes = ctx->dmx_report.out_bytes;
+        if (ctx->bgz_on && *out_bytes) {                   // the parts' offsets become the compressed ones
+            const BgzGroup g{ (const u8*)ctx->dmx_out.p, ctx->dmx_off };
+            if ((rc = bgzf_finish(ctx, &g, 1, h_out, out_cap, out_bytes))) return rc;
+            ctx->dmx_off = ctx->bgz_off;
+            return SFQ_OK;
+        }
         HIPC(hipMemcpyAsync(h_out, ctx->dmx_out.p, (size_t)*out_bytes, hipMemcpyDeviceToHost, ctx->st));
         HIPC(hipStreamSynchronize(ctx->st));
         return SFQ_OK;
@@ -4638,6 +4737,14 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
             if (split) *split = ctx->pair_first;
         }
         *out_bytes = size[0] + size[1];
+        if (ctx->bgz_on && *out_bytes) {                   // merged | rest, the rest's mates apart where it is split
+            BgzGroup g[2] = { { part[0], { 0, size[0] } }, { part[1], { 0, size[1] } } };
+            if (splits) g[1].bounds = { 0, first, size[1] };
+            if ((rc = bgzf_finish(ctx, g, 2, h_out, out_cap, out_bytes))) return rc;
+            ctx->mrg_first = ctx->bgz_off[1];
+            if (splits) { ctx->pair_first = ctx->bgz_off[2]; if (split) *split = ctx->pair_first; }
+            return SFQ_OK;
+        }
         if (size[0]) HIPC(hipMemcpyAsync(h_out, part[0], (size_t)size[0], hipMemcpyDeviceToHost, ctx->st));
         if (size[1]) HIPC(hipMemcpyAsync(h_out + size[0], part[1], (size_t)size[1], hipMemcpyDeviceToHost, ctx->st));
         HIPC(hipStreamSynchronize(ctx->st));
@@ -4685,6 +4792,13 @@ static int decode_host(sfq_ctx* ctx, const sfq_params* params, const sfq_block_i
         if (ctx->pair_split_done) { ctx->pair_first = got.mark_off; if (split) *split = got.mark_off; }
         d_text = (const u8*)ctx->pick_out.p;
         *out_bytes = got.nout;
+    }
+    if (ctx->bgz_on && *out_bytes) {                       // one text, or first mates | second mates
+        BgzGroup g{ d_text, { 0, *out_bytes } };
+        if (ctx->pair_split_done) g.bounds = { 0, ctx->pair_first, *out_bytes };
+        if ((rc = bgzf_finish(ctx, &g, 1, h_out, out_cap, out_bytes))) return rc;
+        if (ctx->pair_split_done) { ctx->pair_first = ctx->bgz_off[1]; if (split) *split = ctx->pair_first; }
+        return SFQ_OK;
     }
     HIPC(hipMemcpyAsync(h_out, d_text, (size_t)*out_bytes, hipMemcpyDeviceToHost, ctx->st));
     HIPC(hipStreamSynchronize(ctx->st));
@@ -4754,6 +4868,46 @@ int sfq_crc32(sfq_ctx* ctx, const uint8_t* d_data, const uint64_t* h_bounds, uin
     HIPC(hipStreamSynchronize(ctx->st));
     settle.ok = true;
     return SFQ_OK;
+}
+uint64_t sfq_bgzf_bound(uint64_t n, uint32_t n_parts) { return n + 31 * (n / SFQ_BGZF_PIECE + n_parts); }
+int sfq_bgzf_eof(uint8_t out[28]) {
+    static const u8 eof[28] = { 0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    if (!out) return SFQ_E_ARG;
+    memcpy(out, eof, 28);
+    return 28;
+}
+int sfq_bgzf_deflate(sfq_ctx* ctx, const uint8_t* d_text, const uint64_t* h_bounds, uint32_t n_parts, uint8_t* d_out, uint64_t out_cap,
+                     uint64_t* h_part_off, sfq_bgzf_report* report) {
+    if (!ctx) return SFQ_E_ARG;
+    if (report) memset(report, 0, sizeof *report);
+    if (!d_text || !h_bounds || !d_out || !h_part_off) return fail(ctx, SFQ_E_ARG, "null argument");
+    if (!n_parts) return fail(ctx, SFQ_E_ARG, "bgzf: no parts");
+    for (u32 i = 0; i < n_parts; i++)
+        if (h_bounds[i + 1] < h_bounds[i]) return fail(ctx, SFQ_E_ARG, "bgzf: bounds[%u] = %llu after bounds[%u] = %llu", i + 1,
+                                                       (unsigned long long)h_bounds[i + 1], i, (unsigned long long)h_bounds[i]);
+    HIPC(hipSetDevice(ctx->dev));
+    Settle settle(ctx);
+    sfq_bgzf_report rep;
+    const int rc = bgzf_run(ctx, d_text, h_bounds, n_parts, d_out, out_cap, h_part_off, &rep);
+    if (report) *report = rep;
+    if (rc) return rc;
+    settle.ok = true;
+    return SFQ_OK;
+}
+int sfq_ctx_set_bgzf(sfq_ctx* ctx, int on) {
+    if (!ctx) return SFQ_E_ARG;
+    ctx->bgz_on = on != 0;
+    if (!on) { release(ctx->bgz_out); release(ctx->bgz_slots); release(ctx->bgz_toks); release(ctx->bgz_work); }
+    return SFQ_OK;
+}
+int sfq_get_bgzf(const sfq_ctx* ctx, sfq_bgzf_report* report, uint64_t* part_off, uint64_t* text_part_bytes, uint64_t cap) {
+    if (!ctx) return SFQ_E_ARG;
+    if (!ctx->bgz_done) { if (report) memset(report, 0, sizeof *report); return 0; }
+    if ((part_off || text_part_bytes) && cap < ctx->bgz_off.size()) return SFQ_E_ARG;
+    if (report) *report = ctx->bgz_report;
+    if (part_off) memcpy(part_off, ctx->bgz_off.data(), ctx->bgz_off.size() * 8);
+    if (text_part_bytes && !ctx->bgz_text.empty()) memcpy(text_part_bytes, ctx->bgz_text.data(), ctx->bgz_text.size() * 8);
+    return 1;
 }
 uint32_t sfq_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) { return crc32_combine_host(crc_a, crc_b, len_b); }
 int sfq_ctx_set_checksums(sfq_ctx* ctx, int on) {

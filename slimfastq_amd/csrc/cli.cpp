@@ -180,6 +180,12 @@ static void usage() {
            "-S mbytes        : input is compressed in slabs of this many MiB, one archive segment each (default 512 for a\n"
            "                   regular file, read ahead while the GPU codes the slab before; 2048 for a pipe)\n"
            "-t threads       : threads reading a slab (default 6)\n"
+           "-Z               : with -d: every FASTQ, FASTA or line file the run writes is BGZF (blocked gzip, what bgzip writes; any gzip\n"
+           "                   reader reads it), deflated on the GPU as the call's last pass: -u, -p, merge=PATH, the outputs of -x and the\n"
+           "                   sample files of -X, whose names gain .gz; the names of -u and -p are taken as given.  Every file ends with\n"
+           "                   the end-of-file block, an empty result is that block alone (28 bytes).  hist= and counts= stay text.  Not\n"
+           "                   with -R, which cuts the decoded text on the host (-W cuts on the device and works); without -q the last\n"
+           "                   line on stderr says text bytes, compressed bytes and members\n"
            "-z               : print the time of every phase on stderr\n"
            "-g device        : HIP device index (default 0)\n"
            "-T percent       : share of the device memory this process may use for model tables (several processes on one GPU)\n"
@@ -220,6 +226,7 @@ struct Opts {
     std::string ovl_merge;                                             // ... and the merge=PATH: the pairs are merged, not cut
     bool dedup = false;                                                // -D
     bool screen = false; std::string screen_spec; sfq_screen screen_rule; uint32_t screen_k = 27;       // -G terms, and the rule and k they parse to
+    bool bgzf = false;                                                 // -Z: every text file a decode writes is BGZF
     bool demux = false; std::string demux_spec; sfq_demux demux_rule;  // -X terms, and the rule they and the sheet give
     std::vector<std::string> demux_names; std::vector<uint8_t> demux_codes;       // ... the sheet's samples: names, barcode rows
     std::string demux_out, demux_counts;                               // ... out=PREFIX, counts=FILE
@@ -824,7 +831,7 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     if (o.demux) {
         for (const std::string& nm : o.demux_names)
             for (int g = 0; g < (paired ? 2 : 1); g++) {
-                const std::string f = o.demux_out + nm + (paired ? (g ? "_R2" : "_R1") : "") + ".fastq";
+                const std::string f = o.demux_out + nm + (paired ? (g ? "_R2" : "_R1") : "") + (o.bgzf ? ".fastq.gz" : ".fastq");
                 FILE* h = fopen(f.c_str(), "wb");
                 if (!h) croak("-X: can't write file '%s'", f.c_str());
                 dmx_files.push_back(h);
@@ -834,6 +841,8 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         dmx_off.resize(dmx_files.size() + 1); dmx_got.resize(dmx_files.size() + 1);
     }
     if (sfq_ctx_set_pick(ctx, o.pick)) croak("%s", sfq_last_error(ctx));
+    if (sfq_ctx_set_bgzf(ctx, o.bgzf ? 1 : 0)) croak("%s", sfq_last_error(ctx));
+    sfq_bgzf_report bgz_sum; memset(&bgz_sum, 0, sizeof bgz_sum);
     if (sfq_ctx_set_select(ctx, nullptr)) croak("%s", sfq_last_error(ctx));       // (set per segment: the range and the index base are the segment's)
     uint64_t sel_kept = 0, sel_seen = 0, sel_bytes = 0, sel_text = 0;
     if (sfq_ctx_set_trim(ctx, o.trim ? &o.trim_rule : nullptr)) croak("-c: %s", sfq_last_error(ctx));
@@ -1076,6 +1085,12 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
         if (rc) croak("%s", sfq_last_error(ctx));
         tick("sfq_decode_blocks_host");
         const bool in_out = dst == out.p;                              // (not a page-locked buffer: written before the next segment reuses it)
+        if (o.bgzf) {
+            sfq_bgzf_report rep;
+            const int did = sfq_get_bgzf(ctx, &rep, nullptr, nullptr, 0);      // (0: the passes in front left nothing)
+            if (did < 0) croak("-Z: the library did not deflate");
+            if (did == 1) { bgz_sum.text_bytes += rep.text_bytes; bgz_sum.out_bytes += rep.out_bytes; bgz_sum.members += rep.members; bgz_sum.stored_members += rep.stored_members; }
+        }
         if (o.select) {
             sfq_select_report rep;
             if (sfq_get_select(ctx, &rep) != 1) croak("-k: the library did not select");
@@ -1161,6 +1176,15 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
     }
     writer.join();
     if (wbad) croak("USR: Error writing output");
+    if (o.bgzf) {                                                      // every file ends with the end-of-file block, once
+        uint8_t eof[28];
+        sfq_bgzf_eof(eof);
+        std::vector<FILE*> all(dmx_files.begin(), dmx_files.end());
+        if (!o.demux) { all.push_back(of); if (of2) all.push_back(of2); }
+        if (of3) all.push_back(of3);
+        for (FILE* f : all) if (fwrite(eof, 1, 28, f) != 28) croak("USR: Error writing output");
+        if (sfq_ctx_set_bgzf(ctx, 0)) croak("%s", sfq_last_error(ctx));
+    }
     if (o.demux) {
         if (sfq_ctx_set_demux(ctx, nullptr, nullptr)) croak("%s", sfq_last_error(ctx));
         for (size_t c = 0; c < o.demux_names.size() * (paired ? 2 : 1); c++) if (fclose(dmx_files[c])) croak("-X: error writing a sample's file");
@@ -1217,6 +1241,9 @@ static void decode_file(sfq_ctx* ctx, const Opts& o, const std::string& usr, con
                     scr_pairs ? "pairs" : "reads", (unsigned long long)matched, scr_units ? 100.0 * (double)matched / (double)scr_units : 0.0,
                     (unsigned long long)scr_kept, (unsigned long long)scr_kmers, o.screen_k);
     }
+    if (o.bgzf && !o.quiet)
+        fprintf(stderr, "deflated %llu bytes of text to %llu bytes in %llu members (%llu stored)\n", (unsigned long long)bgz_sum.text_bytes,
+                (unsigned long long)bgz_sum.out_bytes, (unsigned long long)bgz_sum.members, (unsigned long long)bgz_sum.stored_members);
     if (o.dedup) {
         if (sfq_ctx_set_dedup(ctx, nullptr) || sfq_dedup_set_destroy(ctx)) croak("%s", sfq_last_error(ctx));
         if (!o.quiet)
@@ -1230,7 +1257,7 @@ int main(int argc, char** argv) {
     Opts o;
     bool statistics = false;
     if (argc == 1) usage();
-    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzAFKYMD1234u:f:l:B:g:S:T:C:t:R:Q:p:W:x:k:c:o:G:X:")) != -1;) {
+    for (int opt; (opt = getopt(argc, argv, "qPsvhdObzZAFKYMD1234u:f:l:B:g:S:T:C:t:R:Q:p:W:x:k:c:o:G:X:")) != -1;) {
         switch (opt) {
         case 'u': g_usr = optarg; break;
         case 'f': fil = optarg; break;
@@ -1246,6 +1273,7 @@ int main(int argc, char** argv) {
         case 'T': o.table_pct = std::min(90, std::max(1, atoi(optarg))); break;
         case 'b': g_batch = true; break;
         case 'z': g_timing = true; break;
+        case 'Z': o.bgzf = true; break;
         case 'A': o.adaptive = true; break;
         case 'F': o.force_frozen = true; break;
         case 'K': o.checksum = true; break;
@@ -1298,6 +1326,15 @@ int main(int argc, char** argv) {
         return 1;
     }
 
+    if (o.bgzf && (g_encode || statistics)) {
+        fprintf(stderr, "slimfastq: -Z (BGZF output) goes with -d: it compresses the text a decode writes%s\n", statistics ? "; -s writes no text" : "");
+        return 1;
+    }
+    if (o.bgzf && o.range) {
+        fprintf(stderr, "slimfastq: -Z does not go with -R: -R cuts the decoded text to its records on the host, and compressed bytes cannot be cut there "
+                        "(-W cuts on the device and goes with -Z)\n");
+        return 1;
+    }
     if (o.range && g_encode) {
         fprintf(stderr, "slimfastq: -R (a range of records) goes with -d: it picks what a decode writes\n");
         return 1;

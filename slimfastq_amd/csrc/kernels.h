@@ -567,3 +567,15 @@ struct DmxArrays {
 // t.starts is not used; info: zeroed by the caller.  out: job.out_cap bytes, of which info->copy.nout are written, and none unless
 // info->status and info->copy.status stay 0.
 void launch_demux(const PairText& t, const DmxArrays& A, const DmxJob& job, u8* out, DmxInfo* info, hipStream_t st);
+
+// BGZF members (bgz.hip): member m of n_members holds text[mb[m], mb[m + 1]), 1 .. 65280 bytes; crc[m]: its CRC-32 (crc.hip's range
+// pass over the same bounds).  A wavefront deflates a member into slot m of slots (bgz_slot_bytes), through the workgroup's piece of
+// toks (bgz_token_bytes(workgroups)); msize[m] = the member's bytes, dst[n_members + 1] their scan (scan_tmp as launch_scan_u32 wants
+// it), from[m] = where the member lies in slots; *n_stored (zeroed by the caller) counts the members that hold a stored block.  Then
+// pick.hip's copy packs the members into out: info (zeroed by the caller) ends up with pieces = n_members, nout = their bytes and
+// status = PICK_ROOM where they exceed out_cap -- nothing is written to out then.
+u32  bgz_workgroups(u32 n_members, u32 cus);
+u64  bgz_token_bytes(u32 workgroups);
+u64  bgz_slot_bytes(u32 n_members);
+void launch_bgz_deflate(const u8* text, const u64* mb, u32 n_members, const u32* crc, u32 workgroups, u32* toks, u8* slots, u32* msize, u64* from,
+                        u64* dst, u64* scan_tmp, u32* n_stored, u64 out_cap, u8* out, PickInfo* info, hipStream_t st);
